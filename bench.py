@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- withdraw proofs/sec on MI355X (BASELINE.json metric), one process per GPU.
 
-    python bench.py --gpus N --steps K --warmup W [--workload prove|msm26|tree20] [--batch B] [--no-cpu] ...
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR] [--workload prove|msm26|tree20] [--batch B] [--no-cpu] ...
 
 --workload prove (default; BASELINE.json configs[1], and configs[3] when N > 1)
     A "step" proves one batch of withdraw statements end to end on the GPU: batched MiMC7 witness generation -> R1CS
@@ -10,10 +10,13 @@
     paths, blinding) are synthetic and resident in HBM when the timed region starts; the key comes from fixed toxic
     waste.  `value` is measured on the BASELINE-shaped circuit: dense padding, every wire has an A and a B base (two
     density rows, owshen_amd/circuit.py), i.e. the 0.9 x 2^20 G1 + 2^18 G2 points per proof that BASELINE.md section 2
-    quotes.  The same line carries `sparse_padding` (the padding gates' natural query density: A ~50 %, B ~45 % of the
-    wires have a base -- a lighter workload, reported for continuity with rounds 1-2), `roofline` (HBM, the contract's
-    object) and `roofline_valu` (the bound that actually binds: VALU issue), and two short legs the driver thereby
-    times as well: `msm26` (configs[2]) and `tree20` (configs[4]).
+    quotes.  A plain run sets up, warms up, times the K steps and prints the headline (`metric`, `value`, `ms_per_step`,
+    per-step times, the configuration).  With --full the same line also carries `sparse_padding` (the padding gates'
+    natural query density: A ~50 %, B ~45 % of the wires have a base -- a lighter workload, reported for continuity with
+    rounds 1-2), `roofline` (HBM, the contract's object) and `roofline_valu` (the bound that actually binds: VALU issue),
+    og_verify of the last step, the CPU baseline, the latency / natural / deposit / zkey legs and two short legs:
+    `msm26` (configs[2]) and `tree20` (configs[4]).
+    --dump-outputs DIR writes the last timed step's proofs and public inputs (bytes as float32) as DIR/<name>.npy.
     N > 1: proofs are independent units -- each rank proves its own batch with a replicated key, no data-path
     collective (weak scaling); time = max over ranks between barriers.
 --workload msm26 (configs[2])  one BN254 G1 MSM over 2^26 points (--log-n to shrink); N > 1: window-sharded
@@ -77,6 +80,12 @@ def parse_args():
     ap.add_argument("--precomp", action="store_true", help="msm26: per-window precomputed tables (round 3's form) instead of plain bases")
     ap.add_argument("--precomp-too", action="store_true", help="msm26: time the per-window-table variant beside the plain-bases headline")
     ap.add_argument("--no-precomp", action="store_true", help="(accepted for compatibility: plain bases are the default since round 4)")
+    ap.add_argument("--full", action="store_true", help="prove: after the headline, everything else the line can carry (stage times and "
+                    "rooflines, clock / power, og_verify of the last step, the CPU baseline, the serial step, the other padding variant, "
+                    "the batch-512 / latency / in-process / window-sharded / natural / deposit / zkey legs and the msm26 / tree20 legs); "
+                    "without it the run only sets up, warms up, times the steps and prints the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step computed "
+                    "as DIR/<name>.npy (float32; proof and public-input bytes one per element, at most 64 MB in all)")
     return ap.parse_args()
 
 
@@ -366,6 +375,33 @@ def timed(dist, fn, warmup, steps, drain=None, period=1):
     if period > 1 and len(blobs) > 1 and blobs[0] == blobs[1]:
         sys.exit("bench.py: two steps over DIFFERENT inputs produced the same bytes -- the run is invalid")
     return dist.max_time(dt), out
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(args, dist, **arrays):
+    """--dump-outputs DIR: the last timed step's results as DIR/<name>.npy, float32 (every value is a byte or a small integer:
+    exact), so that two builds can be compared output for output.  Inputs are seeded, so the same arguments give the same
+    arrays.  Above the 64 MB budget an array keeps a fixed, seeded sample of its rows (DIR/<name>_rows.npy lists them).  With
+    several ranks every rank writes its own share as <name>_rank<g>.npy."""
+    import numpy as np
+    out_dir = getattr(args, "dump_outputs", None)
+    if not out_dir:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f"_rank{dist.rank}" if dist.world > 1 else ""
+    share = DUMP_BUDGET_BYTES // max(1, len(arrays)) // max(1, dist.world)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        rows = None
+        if a.size * 4 > share and a.ndim > 0:
+            per_row = max(1, a[0].size * 4)
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], max(1, share // per_row), replace=False))
+            a = a[rows]
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a.astype(np.float32))
+        if rows is not None:
+            np.save(os.path.join(out_dir, f"{name}_rows{suffix}.npy"), rows.astype(np.float64))
 
 
 def step_stats(ms):
@@ -909,6 +945,7 @@ def run_prove_in_process(args, dist, ctx, make_multi=None):
     state["n"] = 0
     dt, proofs = timed(dist, step, 0, args.steps, None, period=2)
     assert proofs is not None and proofs.any()
+    dump_outputs(args, dist, proofs=proofs, public_inputs=state["pub"][state["last"]])
 
     class _St:
         pass
@@ -972,6 +1009,7 @@ def run_prove_window_sharded(args, dist, ctx):
     dt, proofs = timed(dist, step, 0, args.steps, None, period=2)
     telemetry = tele.stop()
     assert proofs is not None and proofs.any()
+    dump_outputs(args, dist, proofs=proofs, public_inputs=st.public[st.last_set])
     digest = int.from_bytes(__import__("hashlib").sha256(proofs.tobytes()).digest()[:6], "big")
     digests = [int(x) for x in dist.all_values(digest)]
     assert len(set(digests)) == 1, f"the ranks assembled different proofs: {digests}"
@@ -1038,14 +1076,18 @@ def run_prove(args, dist, ctx):
         st.step()
     st.drain()
     st.n_steps = 0
-    ctx.profile(True)
-    ident = device_identity(dist.torch, dist.device)
-    tele = GpuTelemetry(ident.get("pci")).start()   # a host thread reading sysfs: clock and power WHILE the timed steps run
+    full = getattr(args, "full", False)
+    if full:
+        ctx.profile(True)
+        ident = device_identity(dist.torch, dist.device)
+        tele = GpuTelemetry(ident.get("pci")).start()   # a host thread reading sysfs: clock and power WHILE the timed steps run
     dt, proofs = timed(dist, st.step, 0, args.steps, st.drain, period=2)
-    telemetry = tele.stop()
-    prof = ctx.profile_read()
-    ctx.profile(False)
+    if full:
+        telemetry = tele.stop()
+        prof = ctx.profile_read()
+        ctx.profile(False)
     assert proofs is not None and proofs.any(), "prover returned empty proofs"
+    dump_outputs(args, dist, proofs=proofs, public_inputs=st.public[st.last_set])
     proved_inputs_d, proved_rs = st.sets[st.last_set]   # the batch `proofs` belongs to (the CPU leg re-proves a sample of it)
     proved_public = st.public[st.last_set].copy()
     step_ms = list(dist.last_step_ms)
@@ -1058,6 +1100,44 @@ def run_prove(args, dist, ctx):
     plan_mode, plan_sizes = st.pk.plan(B)
     log(f"[bench] rank {rank}: batch {B}, {plan_mode} {plan_sizes}; HBM: key {key_bytes / 2**30:.2f} GiB, scratch {mem['scratch_bytes'] / 2**30:.1f} GiB "
         f"in {mem['scratch_buffers']} buffers, device {(mem['device_total_bytes'] - mem['device_free_bytes']) / 2**30:.1f} of {mem['device_total_bytes'] / 2**30:.0f} GiB in use")
+    g1, g2 = st.points()
+    cfg_density = dict(st.density)
+    m, d = st.m, st.d
+    pad_text = {"dense": "dense padding: every wire has an A and a B base", "sparse": "padding density as built: see n_dense", "none": "no padding"}[pad_name]
+    config = {"workload": ("natural depth-%d withdraw circuit" % args.depth) if args.natural else
+              f"BASELINE.json configs[1]: batch of {B} withdraw proofs per GPU, depth-{args.depth} MiMC7 Merkle circuit sized to "
+              f"n_wires=2^18 / NTT 2^17 with synthetic padding gates ({pad_text}); "
+              f"{g1} G1 + {g2} G2 MSM points accumulated per proof after density compaction",
+              "batch_per_gpu": B, "batch_total": sum(batches), "n_wires": m, "domain": d, "merkle_depth": args.depth,
+              "sub_batch_plan": {"mode": plan_mode, "sizes": plan_sizes},
+              "hbm": {"key_bytes": key_bytes, "scratch_bytes_reserved": mem["scratch_bytes"], "scratch_buffers": mem["scratch_buffers"],
+                      "device_in_use_bytes": mem["device_total_bytes"] - mem["device_free_bytes"], "device_total_bytes": mem["device_total_bytes"],
+                      "note": "after the timed steps: the resident key (CSR + per-window query tables) and the prover's scratch arena "
+                              "(two sub-batch slots + call-level buffers), og_mem_info / og_pk_bytes"},
+              "n_dense": cfg_density, "g1_points_per_proof": g1, "g2_points_per_proof": g2,
+              "query_window_bits": dict(st.windows),
+              "padding": {"dense": "dense (every wire in A and B: BASELINE.md section 2's point counts)", "none": "none",
+                          "sparse": "sparse (A ~50 %, B ~45 % of the wires)"}[pad_name],
+              "calls": "one blocking og_withdraw_prove_batch_d per step" if not args.ahead else
+              "a step submits its batch (og_withdraw_prove_batch_submit_d) and waits for the previous step's: one call kept ahead; "
+              "all K batches complete inside the timed region",
+              "parallelism": f"proofs sharded across {world} GPU(s), key replicated, no data-path collective"
+              + (f" (barriers / max-time over {dist.backend})" if dist.backend else "")}
+    headline = {
+        "metric": "withdraw proofs/sec (batch=1024)" if args.batch_total is None else f"withdraw proofs/sec (batch of {args.batch_total} over {world} GPU(s))",
+        "value": round(value, 3), "unit": "proofs/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": DTYPE, "data": "synthetic",
+    }
+    if not full:
+        # the plain run: the headline and what describes it; everything measured or checked beyond it is --full's
+        st.close()
+        if rank != 0:
+            return None
+        return {**headline, "ranks": {"backend": dist.backend, "world": world, "per_rank_batch": batches},
+                "step_ms": step_stats(step_ms),
+                "repeatability": {"results_compared": steps_compared, "byte_identical": True, "input_sets": 2},
+                "config": config, "full": False}
     rank_scratch = [int(x) for x in dist.all_values(mem["scratch_bytes"])]
     rank_in_use = [int(x) for x in dist.all_values(mem["device_total_bytes"] - mem["device_free_bytes"])]
     pmc = pmc_profile().get(pad_name if pad_name != "none" else "sparse", {})
@@ -1079,10 +1159,7 @@ def run_prove(args, dist, ctx):
     if rank == 0 and world == 1 and not args.no_cpu:
         from owshen_amd import circuit
         cpu = cpu_baseline_prove(ctx, st, proved_inputs_d, proved_rs, proofs, args.cpu_seconds, plan_sizes=plan_sizes if plan_mode == "stage pipeline" else None)
-    g1, g2 = st.points()
-    cfg_density = dict(st.density)
     alg_mb = st.algorithmic_bytes_per_proof() / 1e6
-    m, d = st.m, st.d
     leg512 = None
     if world == 1 and B == 1024 and not args.natural and not args.no_legs:
         # BASELINE.json configs[3] is "a batch of 4096 over 8 GPUs" = 512 proofs per GPU per call: the per-GPU rate at THAT
@@ -1253,6 +1330,7 @@ def run_prove(args, dist, ctx):
         dist.torch.cuda.empty_cache()
         la = copy.copy(args)
         la.steps, la.warmup, la.no_cpu, la.log_n, la.precomp, la.precomp_too = 2, 1, True, None, False, True
+        la.dump_outputs = None                      # the outputs of this run are the headline's
         ctx.release_scratch()
         legs["msm26"] = compact_leg(run_msm(la, dist, ctx))
         ctx.release_scratch()
@@ -1265,12 +1343,8 @@ def run_prove(args, dist, ctx):
         return None
     distinct = len({(i.get("host"), i.get("uuid") or i.get("pci") or i.get("index")) for i in identities})
     acc_iso = (breakdown_isolated or {}).get("accumulate_g1")
-    pad_text = {"dense": "dense padding: every wire has an A and a B base", "sparse": "padding density as built: see n_dense", "none": "no padding"}[pad_name]
     out = {
-        "metric": "withdraw proofs/sec (batch=1024)" if args.batch_total is None else f"withdraw proofs/sec (batch of {args.batch_total} over {world} GPU(s))",
-        "value": round(value, 3), "unit": "proofs/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": DTYPE, "data": "synthetic",
+        **headline,
         "ranks": {**dist.collective_info(), "per_rank_proofs_per_s": [round(b * args.steps / t, 2) for b, t in zip(batches, rank_times)],
                   "per_rank_batch": batches, "per_rank_scratch_bytes": rank_scratch, "per_rank_hbm_in_use_bytes": rank_in_use,
                   "devices": identities, "distinct_devices": distinct,
@@ -1296,25 +1370,7 @@ def run_prove(args, dist, ctx):
                                   "repeat step k - 2 byte for byte and differ from step k - 1, or the run aborts; after the clock stops every "
                                   "proof of the last step goes through og_verify with the public inputs the call returned, and the C "
                                   "restatement re-proves the first and last proof of every sub-batch of the plan (byte equality)"},
-        "config": {"workload": ("natural depth-%d withdraw circuit" % args.depth) if args.natural else
-                   f"BASELINE.json configs[1]: batch of {B} withdraw proofs per GPU, depth-{args.depth} MiMC7 Merkle circuit sized to "
-                   f"n_wires=2^18 / NTT 2^17 with synthetic padding gates ({pad_text}); "
-                   f"{g1} G1 + {g2} G2 MSM points accumulated per proof after density compaction",
-                   "batch_per_gpu": B, "batch_total": sum(batches), "n_wires": m, "domain": d, "merkle_depth": args.depth,
-                   "sub_batch_plan": {"mode": plan_mode, "sizes": plan_sizes},
-                   "hbm": {"key_bytes": key_bytes, "scratch_bytes_reserved": mem["scratch_bytes"], "scratch_buffers": mem["scratch_buffers"],
-                           "device_in_use_bytes": mem["device_total_bytes"] - mem["device_free_bytes"], "device_total_bytes": mem["device_total_bytes"],
-                           "note": "after the timed steps: the resident key (CSR + per-window query tables) and the prover's scratch arena "
-                                   "(two sub-batch slots + call-level buffers), og_mem_info / og_pk_bytes"},
-                   "n_dense": cfg_density, "g1_points_per_proof": g1, "g2_points_per_proof": g2,
-                   "query_window_bits": dict(st.windows),
-                   "padding": {"dense": "dense (every wire in A and B: BASELINE.md section 2's point counts)", "none": "none",
-                               "sparse": "sparse (A ~50 %, B ~45 % of the wires)"}[pad_name],
-                   "calls": "one blocking og_withdraw_prove_batch_d per step" if not args.ahead else
-                   "a step submits its batch (og_withdraw_prove_batch_submit_d) and waits for the previous step's: one call kept ahead; "
-                   "all K batches complete inside the timed region",
-                   "parallelism": f"proofs sharded across {world} GPU(s), key replicated, no data-path collective"
-                   + (f" (barriers / max-time over {dist.backend})" if dist.backend else "")},
+        "config": config,
         "roofline": roofline,
         "roofline_valu": roofline_valu,
         "roofline_isolated": roofline_isolated,
@@ -1572,6 +1628,8 @@ def run_msm(args, dist, ctx):
         ms = dt / args.steps * 1e3
         step_ms = list(dist.last_step_ms)
         gots.append(bytes(got.tobytes()))
+        if precomp == modes[0]:
+            dump_outputs(args, dist, msm_point=np.frombuffer(gots[-1], dtype=np.uint8))
         bases.close()
         ctx.release_scratch()
         acc_n = prof["accumulate_g1"][1]
@@ -1704,6 +1762,7 @@ def run_tree(args, dist, ctx):
     tele = GpuTelemetry(device_identity(torch, dist.device).get("pci"), period=0.005).start()
     dt, root = timed(dist, step, 0, args.steps)
     telemetry = tele.stop()
+    dump_outputs(args, dist, root=np.frombuffer(bytes(root), dtype=np.uint8))
     ms = dt / args.steps * 1e3
     step_ms = list(dist.last_step_ms)
     alg = 32 * n + 32 * (n - 1)

@@ -186,3 +186,69 @@ def test_single_gpu_fallback_rewrites_the_command(monkeypatch):
     assert bench.single_gpu_fallback(2) == {"value": 1}
     assert seen["cmd"][2:] == ["--gpus", "1", "--steps", "20", "--warmup", "5", "--batch", "512"]
     assert "WORLD_SIZE" not in seen["env"] and "RANK" not in seen["env"] and seen["env"]["HIP_VISIBLE_DEVICES"] == "6"
+
+
+def _load_bench(name):
+    import importlib.util
+    spec = importlib.util.spec_from_file_location(name, BENCH)
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+class _OneRank(_FakeDist):
+    rank, world, backend, device = 0, 1, None, 0
+
+    def all_values(self, x):
+        return [float(x)]
+
+
+def test_plain_run_prints_the_headline_and_dumps_what_it_proved(tmp_path, monkeypatch):
+    """a plain prove run (no --full) on the CPU interpreter: the headline fields and no leg, exactly --steps timed steps;
+    --dump-outputs writes the last step's proofs and public inputs as float32 byte values, and og_verify accepts them"""
+    import argparse
+    monkeypatch.setenv("OG_WITNESS_W9", "0")   # (the lane-local witness walk: the interpreter's fast one)
+    from tests import emu
+    from owshen_amd import groth16
+    bench = _load_bench("bench_plain")
+    setups = []
+
+    class _Recorded(bench.ProveSetup):
+        def __init__(self, *a, **k):
+            super().__init__(*a, **k)
+            setups.append(self)
+
+    monkeypatch.setattr(bench, "ProveSetup", _Recorded)
+    args = argparse.Namespace(gpus=1, batch=2, batch_total=None, depth=1, natural=True, sparse=False, dense=False, steps=3, warmup=1,
+                              in_process=False, shard="proofs", ahead=False, full=False, dump_outputs=str(tmp_path / "out"))
+    ctx = emu.Ctx()
+    try:
+        line = bench.run_prove(args, _OneRank(), ctx)
+    finally:
+        ctx.close()
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line, k
+    assert line["steps"] == 3 and line["step_ms"]["n"] == 3 and line["full"] is False and line["value"] > 0
+    assert not {"roofline", "cpu_baseline", "box", "natural", "latency", "msm26", "tree20"} & set(line)
+    assert len(setups) == 1                      # the headline's circuit only: no other padding variant, no natural leg
+    proofs, public = np.load(tmp_path / "out" / "proofs.npy"), np.load(tmp_path / "out" / "public_inputs.npy")
+    assert proofs.dtype == np.float32 and proofs.shape == (2, 256) and public.shape == (2, 6, 32)
+    vkb = groth16.vk_to_bytes(setups[0].vk)
+    for i in range(2):
+        assert groth16.verify(vkb, public[i].astype(np.uint8), proofs[i].astype(np.uint8).tobytes())
+
+
+def test_dump_outputs_keeps_a_seeded_sample_within_the_budget(tmp_path, monkeypatch):
+    import argparse
+    bench = _load_bench("bench_dump")
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 2 * 10 * 4 * 4)          # two arrays: 10 rows of 4 float32 each
+    args = argparse.Namespace(dump_outputs=str(tmp_path))
+    big = np.arange(100 * 4, dtype=np.uint16).reshape(100, 4)
+    small = np.arange(6, dtype=np.uint8)
+    bench.dump_outputs(args, _OneRank(), big=big, small=small)
+    got, rows = np.load(tmp_path / "big.npy"), np.load(tmp_path / "big_rows.npy")
+    assert got.dtype == np.float32 and got.shape == (10, 4) and (got == big[rows.astype(int)]).all()
+    assert (np.load(tmp_path / "small.npy") == small).all() and not (tmp_path / "small_rows.npy").exists()
+    bench.dump_outputs(args, _OneRank(), big=big, small=small)
+    assert (np.load(tmp_path / "big_rows.npy") == rows).all()                # the same sample every run
+    bench.dump_outputs(argparse.Namespace(dump_outputs=None), _OneRank(), big=big)   # no --dump-outputs: nothing written

@@ -4,7 +4,7 @@
 set -u
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 mkdir -p gpurun_out
-ARGS="${AB_ARGS:---steps 2 --warmup 1 --no-cpu --no-dense}"
+ARGS="${AB_ARGS:---full --steps 2 --warmup 1 --no-cpu --no-dense}"
 cp owshen_amd/libowshen_gpu.so /tmp/new.so
 for t in new base new2; do
   case $t in base) cp owshen_amd/libowshen_gpu_ab.so owshen_amd/libowshen_gpu.so ;; *) cp /tmp/new.so owshen_amd/libowshen_gpu.so ;; esac

@@ -12,6 +12,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 REPO=$PWD
 mode=${1:-}; shift || true
 ARGS="${AB_ARGS:---gpus 1 --steps 5 --warmup 2 --no-cpu --no-legs --dense}"
+BASE_ARGS=$ARGS
 case $mode in
   prepare)
     for spec in "$@"; do
@@ -32,6 +33,7 @@ case $mode in
     for r in $(seq 1 $rounds); do
       for tag in "${tags[@]}"; do
         dir=$REPO; [ "$tag" != HEAD ] && dir=$REPO/build_ab/$tag
+        ARGS=$BASE_ARGS; [ "$tag" = HEAD ] && ARGS="$BASE_ARGS --full"   # (earlier trees' bench.py ran every leg without asking)
         ( cd $dir && timeout -s KILL 400 python bench.py $ARGS > $REPO/gpurun_out/ab_rounds/${tag}_$r.json 2> $REPO/gpurun_out/ab_rounds/${tag}_$r.err )
         python - "$tag" "$r" gpurun_out/ab_rounds/${tag}_$r.json <<'PY' | tee -a $out
 import json, sys

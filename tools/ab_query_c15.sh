@@ -3,7 +3,7 @@
 # 15 bits everywhere (OG_QUERY_C=15), the default by size (B 13, A / L / H 15); throughput at batch 4096 and the latency of 1 / 8 / 64 requests.
 cd "${GRAFT_REPO_ROOT:-/root/repo}"; mkdir -p gpurun_out; OUT=$PWD/gpurun_out; H=$PWD/owshen_amd/libowshen_gpu_hooks.so
 run() { local name=$1; shift
-  env OWSHEN_GPU_LIB=$H "$@" timeout -s KILL 400 python bench.py --natural --batch 4096 --steps 3 --warmup 1 --no-cpu --no-legs > $OUT/c15_$name.json 2> $OUT/c15_$name.err
+  env OWSHEN_GPU_LIB=$H "$@" timeout -s KILL 400 python bench.py --full --natural --batch 4096 --steps 3 --warmup 1 --no-cpu --no-legs > $OUT/c15_$name.json 2> $OUT/c15_$name.err
   python - $OUT/c15_$name.json "$name $*" <<'PY'
 import json,sys
 try:

@@ -6,10 +6,10 @@ export OWSHEN_GPU_LIB=${OWSHEN_GPU_LIB:-${GRAFT_REPO_ROOT:-/root/repo}/owshen_am
 cd "$(dirname "$0")/.." && mkdir -p gpurun_out
 run() {  # name, env...
   local name=$1; shift
-  env "$@" timeout 300 python bench.py --steps 6 --warmup 2 --no-other --no-legs --no-cpu 2>/dev/null | tail -1 > gpurun_out/abr_$name.json
-  python - "$name" <<'P'
+  local line=$(env "$@" timeout 300 python bench.py --full --steps 6 --warmup 2 --no-other --no-legs --no-cpu 2>/dev/null | tail -1)
+  python - "$name" "$line" <<'P'
 import json, sys
-d = json.loads(open(f"gpurun_out/abr_{sys.argv[1]}.json").read())
+d = json.loads(sys.argv[2])
 s = d.get("stage_ms_per_step_isolated", {})
 print(f"{sys.argv[1]:>14} {d['value']:8.2f} proofs/s  {d['ms_per_step']:8.1f} ms   isolated acc {s.get('accumulate_g1',0)+s.get('accumulate_g2',0):7.1f}  reduce {s.get('reduce_g1',0):5.1f} + {s.get('reduce_g2',0):5.1f}")
 P

@@ -3,7 +3,7 @@
 # check that the 2^18-wire headline keeps its plan.
 cd "${GRAFT_REPO_ROOT:-/root/repo}"; mkdir -p gpurun_out; OUT=$PWD/gpurun_out; H=$PWD/owshen_amd/libowshen_gpu_hooks.so
 run() { local name=$1 args=$2; shift 2
-  env OWSHEN_GPU_LIB=$H "$@" timeout -s KILL 400 python bench.py $args --steps 3 --warmup 1 --no-cpu --no-legs --no-other > $OUT/cap_$name.json 2> $OUT/cap_$name.err
+  env OWSHEN_GPU_LIB=$H "$@" timeout -s KILL 400 python bench.py --full $args --steps 3 --warmup 1 --no-cpu --no-legs --no-other > $OUT/cap_$name.json 2> $OUT/cap_$name.err
   python - $OUT/cap_$name.json "$name [$args] $*" <<'PY'
 import json,sys
 try:

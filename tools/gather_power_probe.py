@@ -29,7 +29,7 @@ def run_arm(name, mask, steps, extra):
     env.pop("OG_GATHER_MASK", None)
     if mask is not None:
         env["OG_GATHER_MASK"] = str(mask)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", "1", "--no-cpu", "--no-legs", "--dense",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", str(steps), "--warmup", "1", "--no-cpu", "--no-legs", "--dense",
            "--no-verify"] + extra
     t0 = time.time()
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)

@@ -41,19 +41,19 @@ for s in $stages; do
             echo "   cgroup cpu.max: $(cat /sys/fs/cgroup/cpu.max 2>/dev/null || cat /sys/fs/cgroup/cpu/cpu.cfs_quota_us 2>/dev/null) nproc: $(nproc) loadavg: $(cut -d' ' -f1-3 /proc/loadavg)" ;;
     tests) TAILN=25 run tests ${TESTS_TO:-1000} python -m pytest tests -x -q -m gpu --timeout=400 --durations=10 ;;
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench 900 python bench.py --steps ${BENCH_STEPS:-5} --warmup 2; tail -n 1 $OUT/bench.log > $OUT/${TAG}_bench.json; summ $OUT/${TAG}_bench.json ;;
-    bench_driver) run bench_driver 900 python bench.py --gpus 1 --steps 20 --warmup 5; tail -n 1 $OUT/bench_driver.log > $OUT/${TAG}_bench_driver.json; summ $OUT/${TAG}_bench_driver.json ;;
+    bench) run bench 900 python bench.py --full --steps ${BENCH_STEPS:-5} --warmup 2; tail -n 1 $OUT/bench.log > $OUT/${TAG}_bench.json; summ $OUT/${TAG}_bench.json ;;
+    bench_driver) run bench_driver 900 python bench.py --full --gpus 1 --steps 20 --warmup 5; tail -n 1 $OUT/bench_driver.log > $OUT/${TAG}_bench_driver.json; summ $OUT/${TAG}_bench_driver.json ;;
     variants)  # (OG_* switches exist only in the hooks build of the library: every variant, the empty one too, runs on it)
       i=0
       while IFS= read -r v; do
         [ -z "$v" ] && continue
         i=$((i+1))
-        env OWSHEN_GPU_LIB=$REPO/owshen_amd/libowshen_gpu_hooks.so $v timeout -s KILL 300 python bench.py --steps ${VSTEPS:-3} --warmup 1 --no-cpu --no-legs ${VARGS:---dense} > $OUT/var_$i.log 2>&1
+        env OWSHEN_GPU_LIB=$REPO/owshen_amd/libowshen_gpu_hooks.so $v timeout -s KILL 300 python bench.py --full --steps ${VSTEPS:-3} --warmup 1 --no-cpu --no-legs ${VARGS:---dense} > $OUT/var_$i.log 2>&1
         echo "--- [$i] $v"; tail -n 1 $OUT/var_$i.log > $OUT/var_$i.json; summ $OUT/var_$i.json
       done <<< "$VARIANTS" ;;
-    prof) ( cd /tmp; run prof 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o $TAG -- python $REPO/bench.py --steps 1 --warmup 1 --no-cpu --dense --no-legs --no-verify )
+    prof) ( cd "$TMPDIR"; run prof 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o $TAG -- python $REPO/bench.py --full --steps 1 --warmup 1 --no-cpu --dense --no-legs --no-verify )
           find $OUT/prof -name "*kernel_stats*" | head -3 ;;
-    prof_sparse) ( cd /tmp; run prof_sparse 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_sparse -o $TAG -- python $REPO/bench.py --steps 1 --warmup 1 --no-cpu --sparse --no-legs ) ;;
+    prof_sparse) ( cd "$TMPDIR"; run prof_sparse 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_sparse -o $TAG -- python $REPO/bench.py --full --steps 1 --warmup 1 --no-cpu --sparse --no-legs ) ;;
     pmc) # dense padding; ONE step of the batch-1024 headline under the prover's own sub-batch plan (round 4: the traffic bench.py
          # quotes is a reading of the very launches it times, not a per-point rescale)
          export PMC_ARGS="--batch 1024 --steps 1 --warmup 0 --no-cpu --dense --no-legs --no-isolated --no-verify"
@@ -78,9 +78,9 @@ for s in $stages; do
     msm26) run msm26 600 python bench.py --workload msm26 --steps 2 --warmup 1; tail -n 1 $OUT/msm26.log > $OUT/${TAG}_msm26.json; summ $OUT/${TAG}_msm26.json ;;
     tree20) run tree20 300 python bench.py --workload tree20 --steps 5 --warmup 1; tail -n 1 $OUT/tree20.log > $OUT/${TAG}_tree20.json ;;
     latency) run latency 300 python tools/latency.py; cp $OUT/latency.json $OUT/${TAG}_latency.json ;;
-    bench_nat) run bench_nat 600 python bench.py --natural --batch 4096 --steps 2 --warmup 1; tail -n 1 $OUT/bench_nat.log > $OUT/${TAG}_bench_natural.json ;;
+    bench_nat) run bench_nat 600 python bench.py --full --natural --batch 4096 --steps 2 --warmup 1; tail -n 1 $OUT/bench_nat.log > $OUT/${TAG}_bench_natural.json ;;
     multi_dry)
-      OG_BENCH_OVERSUBSCRIBE=1 run multi_dry_prove 300 python bench.py --gpus 2 --batch 64 --steps 1 --warmup 1 --no-cpu --no-other --no-legs
+      OG_BENCH_OVERSUBSCRIBE=1 run multi_dry_prove 300 python bench.py --full --gpus 2 --batch 64 --steps 1 --warmup 1 --no-cpu --no-other --no-legs
       OG_BENCH_OVERSUBSCRIBE=1 run multi_dry_msm 300 python bench.py --gpus 2 --workload msm26 --log-n 20 --steps 1 --warmup 1 --no-cpu
       OG_BENCH_OVERSUBSCRIBE=1 run multi_dry_tree 300 python bench.py --gpus 2 --workload tree20 --log-n 16 --steps 1 --warmup 1 --no-cpu ;;
     multi_dry6)  # round 6: the window-sharded prove mode with 2 ranks on this one GPU (gloo fallback: RCCL cannot start two ranks on
