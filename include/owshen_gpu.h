@@ -283,6 +283,30 @@ int og_multi_msm(og_multi* m, og_bases* const* bases, const uint8_t* scalars, si
 int og_verify(const uint8_t* vk, size_t vk_len, const uint8_t* public_inputs, size_t n_pub,
               const uint8_t proof[256], int* ok_out);
 
+/* ---- N6 on the GPU: batched Groth16 verification behind a key handle ----------------------------------------------------
+ * og_vk_load decodes and subgroup-checks an "OWVK0001" key ONCE and keeps on the device everything that depends on the key
+ * alone: the Miller value of (alpha, beta), the whole twist walk of gamma and of delta (slope and intercept of each of the 102
+ * steps of the optimal-ate loop) and 4-bit fixed-base window tables of the IC points (60 KB per public input).  A key that
+ * makes og_verify answer OG_ERR_INVALID (magic, length, n_pub, an invalid alpha / beta / gamma / delta / IC point) makes
+ * og_vk_load answer OG_ERR_INVALID.  og_vk_info: info = { n_pub, steps of the stored walks, bytes of IC tables, device bytes }.
+ * The handle belongs to the DEVICE it was loaded on and may be freed before or after og_shutdown of the loading context.
+ *
+ * og_verify_batch_d checks n proofs in one call, one proof per GPU lane: public_inputs_d is n x n_pub x 32 B and proofs_d
+ * n x 256 B, both DEVICE pointers (16-byte aligned, as og_malloc returns); ok_out is a HOST array of n u32, 1 accept / 0 reject.
+ * The number of public inputs is the key's -- a count that differs from the key's cannot be expressed.  ok_out[i] is what
+ * og_verify(vk, public_inputs[i], n_pub, proofs[i]) answers, for every input: a non-canonical coordinate, a point off the
+ * curve, B outside the r-torsion, A, B or C at infinity, or a public input >= r (tested before the infinite-IC shortcut) is a
+ * REJECT (ok = 0, OG_OK); when vk_x is the point at infinity its pairing is skipped.  n = 0 is OG_OK.  Null handles are
+ * OG_ERR_INVALID before the device is touched.  No randomness is drawn: every proof gets its own pairing check (the final
+ * exponentiation is a structured chain that raises og_verify's value to a fixed power prime to r -- the same decision).
+ * og_verify itself, and libowshen_verify.so, are unchanged: the host-only verifier is what a sequencer without a GPU uses. */
+typedef struct og_vk og_vk; /* device-resident verifying key + everything that depends on the key alone */
+int og_vk_load(og_ctx* ctx, const uint8_t* vk, size_t vk_len, og_vk** out);
+void og_vk_free(og_vk* vk);
+int og_vk_info(const og_vk* vk, uint64_t info[4]);
+int og_verify_batch_d(og_ctx* ctx, const og_vk* vk, const uint8_t* public_inputs_d, const uint8_t* proofs_d, size_t n,
+                      uint32_t* ok_out);
+
 /* ---- withdraw circuit: batched witness generation (N5 feeding N6) ----------------------------
  * The statement (public: root, nullifier_hash, recipient, amount, token, chain_id; private: nullifier, secret and a
  * depth-`depth` MiMC7 Merkle path; leaf = H(H(nullifier, secret), H(amount, token))) and its wire order are specified in

@@ -68,6 +68,10 @@ bool job_is_waited_for(og_job*);
 bool ctx_has_waiters(og_ctx*);
 int spmv_canonical(og_ctx*, const uint32_t*, const uint32_t*, const uint8_t*, size_t, const uint8_t*, uint8_t*);
 int eddsa_verify(og_ctx*, const uint8_t*, size_t, uint32_t*);
+int vk_load(og_ctx*, const uint8_t*, size_t, og_vk**);
+void vk_destroy(og_vk*);
+void vk_info(const og_vk*, uint64_t*);
+int verify_batch(og_ctx*, const og_vk*, const uint8_t*, const uint8_t*, size_t, uint32_t*);
 
 }  // namespace og
 
@@ -892,6 +896,40 @@ int og_eddsa_verify_batch_d(og_ctx* ctx, const uint8_t* records_d, size_t n, uin
     OG_HIP(hipMemcpyAsync(ok_out, ok_d, n * 4, hipMemcpyDeviceToHost, ctx->stream));
     OG_HIP(hipStreamSynchronize(ctx->stream));
     return OG_OK;
+  });
+}
+
+int og_vk_load(og_ctx* ctx, const uint8_t* vk, size_t vk_len, og_vk** out) {
+  return guarded([&]() -> int {
+    CTX_OK(ctx);
+    OG_REQUIRE(vk != nullptr && out != nullptr, "og_vk_load: null argument");
+    *out = nullptr;
+    LOCKED(ctx);
+    return vk_load(ctx, vk, vk_len, out);
+  });
+}
+
+void og_vk_free(og_vk* vk) { vk_destroy(vk); }
+
+int og_vk_info(const og_vk* vk, uint64_t info[4]) {
+  return guarded([&]() -> int {
+    OG_REQUIRE(vk != nullptr && info != nullptr, "og_vk_info: null argument");
+    vk_info(vk, info);
+    return OG_OK;
+  });
+}
+
+int og_verify_batch_d(og_ctx* ctx, const og_vk* vk, const uint8_t* public_inputs_d, const uint8_t* proofs_d, size_t n, uint32_t* ok_out) {
+  return guarded([&]() -> int {
+    CTX_OK(ctx);
+    OG_REQUIRE(vk != nullptr, "og_verify_batch_d: null key");
+    if (n == 0) return OG_OK;
+    uint64_t info[4];
+    vk_info(vk, info);
+    OG_REQUIRE(proofs_d && ok_out && (info[0] == 0 || public_inputs_d), "og_verify_batch_d: null argument");
+    LOCKED(ctx);
+    OG_REQUIRE(ctx->jobs[0] == nullptr && ctx->jobs[1] == nullptr, "og_verify_batch_d: a submitted prove call has not been waited for (og_job_wait)");
+    return verify_batch(ctx, vk, public_inputs_d, proofs_d, n, ok_out);
   });
 }
 

@@ -317,4 +317,56 @@ def verify(vk_blob, public_inputs, proof, lib=None):
     return bool(ok.value)
 
 
+class VerifyingKey:
+    """A verifying key on the device (og_vk_load): the "OWVK0001" blob is decoded and subgroup-checked once, and everything that
+    depends on the key alone -- the (alpha, beta) Miller value, gamma's and delta's twist walks, window tables of the IC points --
+    stays in HBM.  A malformed key raises OwshenGpuError (code -1), as `verify` does for the same bytes."""
+
+    def __init__(self, ctx, vk_blob):
+        self.ctx = ctx
+        self._h = None
+        blob = bytes(vk_blob)
+        buf = (C.c_uint8 * max(len(blob), 1)).from_buffer_copy(blob or b"\0")
+        h = C.c_void_p()
+        ctx._check(ctx._lib.og_vk_load(ctx._h, buf, len(blob), C.byref(h)))
+        self._h = h
+        info = (C.c_uint64 * 4)()
+        ctx._check(ctx._lib.og_vk_info(self._h, info))
+        self.n_pub, self.walk_steps, self.table_bytes, self.device_bytes = (int(x) for x in info)
+
+    def verify_batch(self, public_inputs, proofs):
+        """public_inputs: uint8 [n, n_pub, 32], proofs: uint8 [n, 256] -- host arrays or device buffers -> np.ndarray[bool] of n
+        decisions, each what `verify(vk_blob, public_inputs[i], proofs[i])` answers (og_verify_batch_d)."""
+        ctx = self.ctx
+        if isinstance(proofs, np.ndarray):
+            proofs = ctx.to_device(np.ascontiguousarray(proofs, dtype=np.uint8).reshape(-1, 256))
+        n = int(proofs.shape[0]) if len(proofs.shape) > 1 else int(proofs.shape[0]) // 256
+        if isinstance(public_inputs, np.ndarray):
+            public_inputs = ctx.to_device(np.ascontiguousarray(public_inputs, dtype=np.uint8).reshape(n, self.n_pub, 32)) if self.n_pub and n else None
+        if public_inputs is not None:
+            assert int(np.prod(public_inputs.shape)) == n * self.n_pub * 32, "public_inputs must be [n, n_pub, 32]"
+        ok = np.zeros(n, dtype=np.uint32)
+        ctx._pre()
+        ctx._check(ctx._lib.og_verify_batch_d(ctx._h, self._h, ctx.ptr(public_inputs) if n and self.n_pub else None, ctx.ptr(proofs) if n else None, n,
+                                              ok.ctypes.data_as(C.c_void_p)))
+        return ok.astype(bool)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.ctx._lib.og_vk_free(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 from .evm import proof_to_evm_calldata  # noqa: E402,F401  (256-byte proof -> the verifier contract's 8 words; owshen_amd/evm.py)
