@@ -40,7 +40,8 @@ OG_HD Fq2 f_neg(const Fq2& a) { return {fe_neg(a.c0), fe_neg(a.c1)}; }
 OG_HD Fq2 f_mul(const Fq2& a, const Fq2& b) {
   return {fe_mul_add(a.c0, b.c0, fe_neg_lazy(a.c1), b.c1), fe_mul_add(a.c0, b.c1, a.c1, b.c0)};
 }
-// re = a0^2 + (8N - a1) a1 (45 + 81 products, one reduction), im = (2 a0) a1; operands may be weak (< 8N)
+// re = a0^2 + (8N - a1) a1 (45 + 81 products, one reduction), im = (2 a0) a1; operands may be weak (a0 < 8N, a1 < 8N - 2^232:
+// fe_neg_lazy's bound; the group law squares P < 6N)
 OG_HD Fq2 f_sqr(const Fq2& a) {
   return {fe_sqr_add(a.c0, fe_neg_lazy(a.c1), a.c1), fe_mul(fe_dbl_lazy(a.c0), a.c1)};
 }

@@ -41,7 +41,8 @@ struct FqParams {
                                      0x02c0169fu, 0x169bfd53u, 0x11869d4cu, 0x002a11a6u};  // 2^522 mod N
   static constexpr uint32_t INV = 0x04866389u;  // -N^-1 mod 2^29
   // k N with every limb below the top inflated by 2^29 (borrowed from the next limb): C[i] - a[i] lies in (0, 2^30)
-  // for any normalized a < k N, so k N - a needs no borrow propagation (fe_neg_lazy*, fe_sub_weak)
+  // for any normalized a whose TOP limb does not exceed C[8] (a < k N - 2^232 is enough: the top limb has lent one unit and
+  // borrows nothing), so k N - a needs no borrow propagation (fe_neg_lazy*; fe_sub_weak adds before it looks at a limb)
   static constexpr uint32_t NEG4[9] = {0x21f3f51cu, 0x241182dau, 0x31ca8d3bu, 0x2b548b42u, 0x361765dfu, 0x2b6d0301u, 0x229b8503u, 0x397098cfu, 0x00c19138u};
   static constexpr uint32_t NEG8[9] = {0x23e7ea38u, 0x282305b5u, 0x23951a77u, 0x36a91686u, 0x2c2ecbbfu, 0x36da0604u, 0x25370a07u, 0x32e1319fu, 0x01832272u};
   static constexpr uint32_t N3[9] = {0x0976f7d5u, 0x030d2224u, 0x1557e9edu, 0x087f6872u, 0x00918c68u, 0x0891c242u, 0x01f4a3c3u, 0x0b14729cu, 0x00912cebu};
@@ -60,7 +61,8 @@ struct FrParams {
                                      0x1cf855e3u, 0x1c15e103u, 0x07d09161u, 0x000a054au};
   static constexpr uint32_t INV = 0x0fffffffu;
   // k N with every limb below the top inflated by 2^29 (borrowed from the next limb): C[i] - a[i] lies in (0, 2^30)
-  // for any normalized a < k N, so k N - a needs no borrow propagation (fe_neg_lazy*, fe_sub_weak)
+  // for any normalized a whose TOP limb does not exceed C[8] (a < k N - 2^232 is enough: the top limb has lent one unit and
+  // borrows nothing), so k N - a needs no borrow propagation (fe_neg_lazy*; fe_sub_weak adds before it looks at a limb)
   static constexpr uint32_t NEG4[9] = {0x20000004u, 0x3c3eb27du, 0x39709142u, 0x3f4243ccu, 0x36174a0bu, 0x2b6d0301u, 0x229b8503u, 0x397098cfu, 0x00c19138u};
   static constexpr uint32_t NEG8[9] = {0x20000008u, 0x387d64fbu, 0x32e12286u, 0x3e84879au, 0x2c2e9418u, 0x36da0604u, 0x25370a07u, 0x32e1319fu, 0x01832272u};
   static constexpr uint32_t N3[9] = {0x10000003u, 0x1d2f05deu, 0x0b146cf2u, 0x1771b2dau, 0x00917789u, 0x0891c242u, 0x01f4a3c3u, 0x0b14729cu, 0x00912cebu};
@@ -367,8 +369,10 @@ OG_HD Fe<M> fe_add_lazy(const Fe<M>& a, const Fe<M>& b) {
 }
 
 // ---- lazy operands and fused products ----------------------------------------------
-// 8N - a for a normalized a < 8N: limbs in (0, 2^30), value in (0, 8N].  NOT a normalized Fe: valid only
-// as an operand of the multiplication routines (which accept limbs < 2^30).
+// 8N - a for a normalized a < 8N - 2^232: limbs in (0, 2^30), value in (0, 8N].  NOT a normalized Fe: valid only
+// as an operand of the multiplication routines (which accept limbs < 2^30).  The bound is on the TOP LIMB: a.l[8] <= NEG8[8],
+// the top limb of 8N less the unit it lent -- at a = 8N - 1 the top limb would wrap to 2^32 - 1 (tests/field_raw_cases.py
+// found the earlier "a < 8N" to be 2^232 too generous).  Callers pass values below 6N (ec.hip.h).
 template <class M>
 OG_HD Fe<M> fe_neg_lazy(const Fe<M>& a) {
   Fe<M> r;
@@ -376,7 +380,8 @@ OG_HD Fe<M> fe_neg_lazy(const Fe<M>& a) {
   for (int i = 0; i < 9; i++) r.l[i] = M::NEG8[i] - a.l[i];
   return r;
 }
-// 4N - a for a normalized a < 4N (tighter value bound than fe_neg_lazy, for sums of many products)
+// 4N - a for a normalized a < 4N - 2^232, i.e. a.l[8] <= NEG4[8] (tighter value bound than fe_neg_lazy, for sums of many
+// products).  Callers pass values below 2N.
 template <class M>
 OG_HD Fe<M> fe_neg_lazy4(const Fe<M>& a) {
   Fe<M> r;

@@ -126,3 +126,158 @@ int field_mulchain_lat(og_ctx* ctx, int field, int form, uint8_t* x, const uint8
 }
 
 }  // namespace og
+
+#ifdef OG_AB_HOOKS
+// ---- raw-limb seam of the hooks build (never in the shipped library, never in the header) ------------------------------------
+// og_hook_fe_raw_d hands ONE routine of field.hip.h / ec.hip.h its operands AS LIMBS -- no fe_load, no fe_to_mont -- so that the
+// lazy and weak operand bounds the routines document (limbs up to 2^30 / 2^31, values up to 42 N) reach the asm statements of
+// mont_gfx950.inc on the hardware, and returns the routine's limbs untouched (tests/field_raw_cases.py holds the cases and the
+// big-integer reference).  One kernel instantiation per (field, op): every asm statement gets a register allocation of its
+// own.  Op numbers 0..8, 12, 13 are those of emu_fe_op and 64 + k those of emu_fq2_op (tests/hipemu/stubs.cpp).
+#include "ec.hip.h"
+#include <mutex>
+
+namespace og {
+
+constexpr int RAW_SLOTS = 8, RAW_OUT = 2, RAW_NOPS = 80;
+
+// Fe slots an op reads (0 = no such op).  Fq2 operands take two slots each (c0, c1).
+constexpr int raw_arity(int op) {
+  switch (op) {
+    case 0: case 1: case 2: case 8: case 12: case 13: case 28: return 2;   // add sub mul eq sub_weak add2_weak add_lazy
+    case 3: case 4: case 5: case 6: case 7: return 1;                        // sqr from_mont neg inv words
+    case 20: return 3;                                                      // sqr_add(a, c, d)
+    case 21: return 4;                                                      // mul_add(a, b, c, d)
+    case 22: return 3;                                                      // mul_plus(a, b, c)
+    case 23: return 5;                                                      // mul_add_plus(a, b, d, e, c)
+    case 24: return 6;                                                      // mul_add3
+    case 25: return 8;                                                      // mul_add4
+    case 26: return 7;                                                      // sqr_add3
+    case 27: case 29: case 30: case 31: case 33: case 34: case 35: case 36: return 1;  // dbl neg_lazy neg_lazy4 dbl_lazy weak_diff_is_zero canon lt_modulus to_mont
+    case 32: return 3;                                                      // add3_weak
+    case 64: return 4;                                                      // Fq2 f_mul(a, b)
+    case 65: return 2;                                                      // Fq2 f_sqr(a)
+    case 66: return 8;                                                      // Fq2 f_mul_sub(a, b, c, d)
+    case 67: case 68: case 69: case 70: return 6;                           // Fq2 f_sqr_sub(a, c, d)  f_mul_minus(a, b, x)  f_mul_minus_y(y, neg = 0 | 1, z, x)
+    default: return 0;
+  }
+}
+
+template <class M>
+constexpr bool raw_valid(int op) {
+  return raw_arity(op) != 0 && (op < 64 || std::is_same<M, FqParams>::value);
+}
+
+template <class M>
+OG_HD Fe<M> raw_flag(bool v) {
+  Fe<M> r = Fe<M>::zero();
+  r.l[0] = v ? 1u : 0u;
+  return r;
+}
+
+template <class M, int OP>
+OG_HD void fe_raw_apply(const Fe<M>* x, Fe<M>* o) {
+  if constexpr (OP == 0) o[0] = fe_add(x[0], x[1]);
+  else if constexpr (OP == 1) o[0] = fe_sub(x[0], x[1]);
+  else if constexpr (OP == 2) o[0] = fe_mul(x[0], x[1]);
+  else if constexpr (OP == 3) o[0] = fe_sqr(x[0]);
+  else if constexpr (OP == 4) o[0] = fe_from_mont(x[0]);
+  else if constexpr (OP == 5) o[0] = fe_neg(x[0]);
+  else if constexpr (OP == 6) o[0] = fe_inv(x[0]);
+  else if constexpr (OP == 7) {
+    uint32_t w[8];
+    fe_to_words(w, x[0]);
+    o[0] = fe_from_words<M>(w);
+  } else if constexpr (OP == 8) {
+    o[0] = raw_flag<M>(x[0] == x[1]);
+    o[0].l[1] = x[0].is_zero() ? 1u : 0u;
+  } else if constexpr (OP == 12) o[0] = fe_sub_weak(x[0], x[1]);
+  else if constexpr (OP == 13) o[0] = fe_add2_weak(x[0], x[1]);
+  else if constexpr (OP == 20) o[0] = fe_sqr_add(x[0], x[1], x[2]);
+  else if constexpr (OP == 21) o[0] = fe_mul_add(x[0], x[1], x[2], x[3]);
+  else if constexpr (OP == 22) o[0] = fe_mul_plus(x[0], x[1], x[2]);
+  else if constexpr (OP == 23) o[0] = fe_mul_add_plus(x[0], x[1], x[2], x[3], x[4]);
+  else if constexpr (OP == 24) o[0] = fe_mul_add3(x[0], x[1], x[2], x[3], x[4], x[5]);
+  else if constexpr (OP == 25) o[0] = fe_mul_add4(x[0], x[1], x[2], x[3], x[4], x[5], x[6], x[7]);
+  else if constexpr (OP == 26) o[0] = fe_sqr_add3(x[0], x[1], x[2], x[3], x[4], x[5], x[6]);
+  else if constexpr (OP == 27) o[0] = fe_dbl(x[0]);
+  else if constexpr (OP == 28) o[0] = fe_add_lazy(x[0], x[1]);
+  else if constexpr (OP == 29) o[0] = fe_neg_lazy(x[0]);
+  else if constexpr (OP == 30) o[0] = fe_neg_lazy4(x[0]);
+  else if constexpr (OP == 31) o[0] = fe_dbl_lazy(x[0]);
+  else if constexpr (OP == 32) o[0] = fe_add3_weak(x[0], x[1], x[2]);
+  else if constexpr (OP == 33) o[0] = raw_flag<M>(fe_weak_diff_is_zero(x[0]));
+  else if constexpr (OP == 34) o[0] = fe_canon(x[0]);
+  else if constexpr (OP == 35) o[0] = raw_flag<M>(fe_lt_modulus(x[0]));
+  else if constexpr (OP == 36) o[0] = fe_to_mont(x[0]);
+  else if constexpr (OP >= 64 && std::is_same<M, FqParams>::value) {
+    const Fq2 a = {x[0], x[1]};
+    Fq2 r;
+    if constexpr (OP == 64) r = f_mul(a, Fq2{x[2], x[3]});
+    else if constexpr (OP == 65) r = f_sqr(a);
+    else if constexpr (OP == 66) r = f_mul_sub(a, Fq2{x[2], x[3]}, Fq2{x[4], x[5]}, Fq2{x[6], x[7]});
+    else if constexpr (OP == 67) r = f_sqr_sub(a, Fq2{x[2], x[3]}, Fq2{x[4], x[5]});
+    else if constexpr (OP == 68) r = f_mul_minus(a, Fq2{x[2], x[3]}, Fq2{x[4], x[5]});
+    else r = f_mul_minus_y(a, OP == 70, Fq2{x[2], x[3]}, Fq2{x[4], x[5]});
+    o[0] = r.c0;
+    o[1] = r.c1;
+  }
+}
+
+// one lane per case: in = n x 8 slots x 9 limbs (the slots the op reads; the rest is ignored), out = n x 2 x 9 limbs
+template <class M, int OP>
+__global__ void __launch_bounds__(64) k_fe_raw(const uint32_t* __restrict__ in, size_t n, uint32_t* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
+  if (i >= n) return;
+  constexpr int NI = raw_arity(OP);
+  Fe<M> x[NI], o[RAW_OUT];
+#pragma unroll
+  for (int s = 0; s < NI; s++)
+#pragma unroll
+    for (int k = 0; k < 9; k++) x[s].l[k] = in[i * (RAW_SLOTS * 9) + s * 9 + k];
+  o[0] = Fe<M>::zero();
+  o[1] = Fe<M>::zero();
+  fe_raw_apply<M, OP>(x, o);
+#pragma unroll
+  for (int s = 0; s < RAW_OUT; s++)
+#pragma unroll
+    for (int k = 0; k < 9; k++) out[i * (RAW_OUT * 9) + s * 9 + k] = o[s].l[k];
+}
+
+typedef void (*RawLaunch)(hipStream_t, const uint32_t*, size_t, uint32_t*);
+
+template <class M, int OP>
+void raw_launch(hipStream_t st, const uint32_t* in, size_t n, uint32_t* out) {
+  hipLaunchKernelGGL((k_fe_raw<M, OP>), dim3(grid_for(n, 64)), dim3(64), 0, st, in, n, out);
+}
+
+template <class M, int OP>
+constexpr RawLaunch raw_pick() {
+  if constexpr (raw_valid<M>(OP)) return &raw_launch<M, OP>;
+  else return nullptr;
+}
+
+template <class M, int... OPS>
+RawLaunch raw_lookup(int op, std::integer_sequence<int, OPS...>) {
+  static const RawLaunch table[RAW_NOPS] = {raw_pick<M, OPS>()...};
+  return op >= 0 && op < RAW_NOPS ? table[op] : nullptr;
+}
+
+}  // namespace og
+
+extern "C" int og_hook_fe_raw_d(og_ctx* ctx, int field, int op, const uint32_t* operands_d, size_t n, uint32_t* out_d) {
+  using namespace og;
+  return guarded([&]() -> int {
+    OG_REQUIRE(ctx && operands_d && out_d && n >= 1 && n <= ((size_t)1 << 24) && (field == 0 || field == 1), "og_hook_fe_raw_d: bad argument");
+    const RawLaunch f = field == 0 ? raw_lookup<FrParams>(op, std::make_integer_sequence<int, RAW_NOPS>{})
+                                   : raw_lookup<FqParams>(op, std::make_integer_sequence<int, RAW_NOPS>{});
+    OG_REQUIRE(f != nullptr, "og_hook_fe_raw_d: no such op in this field");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    OG_HIP(hipSetDevice(ctx->device));
+    f(ctx->stream, operands_d, n, out_d);
+    OG_HIP(hipGetLastError());
+    OG_HIP(hipStreamSynchronize(ctx->stream));
+    return OG_OK;
+  });
+}
+#endif  // OG_AB_HOOKS

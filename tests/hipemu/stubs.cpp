@@ -7,6 +7,8 @@ int ubench_coresidency(og_ctx*, int, int, int, int, int, int, int, int, int, flo
 
 // raw-limb entry points so the 9 x 29-bit field layer can be driven with adversarial operands
 // (values up to the documented bounds, not just canonical inputs)
+// (og_hook_fe_raw_d of csrc/field_ops.hip -- this build carries it, tests/test_emu_field_raw.py -- keeps the numbers 0..8, 12, 13
+// of emu_fe_op and 64 + k of emu_fq2_op below for the same plain ops, and reaches every routine directly)
 #include "field.hip.h"
 namespace {
 template <class M> void fe_op_raw(int op, const uint32_t* a9, const uint32_t* b9, uint32_t* out9) {

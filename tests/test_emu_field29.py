@@ -7,6 +7,7 @@ import random
 import pytest
 
 from oracle.py import fields
+from tests.field_raw_cases import samples as _samples, worst_lazy31
 
 MASK = (1 << 29) - 1
 RR = 1 << 261
@@ -26,13 +27,6 @@ def fe():
         limbs = list(out)
         return limbs, sum(v << (29 * i) for i, v in enumerate(limbs))
     return call
-
-
-def _samples(N, rnd, bound_mult=2):
-    top = bound_mult * N - 1
-    vals = [0, 1, N - 1, N, N + 1, top, top - 1, (1 << 253) - 1, sum(MASK << (29 * i) for i in range(8)) % (bound_mult * N)]
-    vals += [rnd.randrange(bound_mult * N) for _ in range(40)]
-    return vals
 
 
 @pytest.mark.parametrize("field", [0, 1])
@@ -211,7 +205,6 @@ def test_mul_with_one_operand_of_limbs_up_to_2_31(field):
     same operands in tests/test_mont_asm.py) with all limbs at the bound against the largest normalized partners: exact
     Montgomery products, normalized, < 2N"""
     from tests import emu
-    from tests.test_mont_asm import worst_lazy31
     f = emu.lib.emu_fe_op
     f.restype = None
     A9 = C.c_uint32 * 9

@@ -57,12 +57,8 @@ def test_emu_quotient_radix4_equals_radix2_on_extreme_inputs(ectx, log_d, monkey
     the radix-2 kernel (OG_NTT_RADIX4=0: every butterfly reduced) and the C restatement, through the quotient pipeline (the only
     user of the stage-block kernels), on the inputs that maximise every intermediate sum: all r - 1, alternating 0 / r - 1, all 1"""
     from oracle.c import binding as oc
-    d = 1 << log_d
-    rm1 = np.frombuffer((fields.R - 1).to_bytes(32, "little"), dtype=np.uint8)
-    full, alt, ones = np.tile(rm1, (d, 1)), np.tile(rm1, (d, 1)), np.zeros((d, 32), np.uint8)
-    alt[::2] = 0
-    ones[:, 0] = 1
-    for a, b, c in ((full, full, full), (alt, full, ones), (ones, alt, full), (full, alt[::-1].copy(), alt)):
+    from tests.quotient_cases import extreme_triples
+    for a, b, c in extreme_triples(1 << log_d):
         monkeypatch.delenv("OG_NTT_RADIX4", raising=False)
         r4 = ectx.h_poly(a, b, c).tobytes()
         monkeypatch.setenv("OG_NTT_RADIX4", "0")
@@ -83,20 +79,8 @@ def test_emu_h_poly_block_shapes(ectx, log_d):
     stages (even / odd: the leftover radix-2 stage, the twiddle-free global stage 0 alone and inside a double stage), and a
     second block of 1, 2, 3 and 7 stages (2^17: the prover's domain) -- against the C restatement; extreme inputs (0, 1, r - 1) ride along"""
     from oracle.c import binding as oc
-    d = 1 << log_d
-    rng = np.random.default_rng(40 + log_d)
-    a, b, c = (_rand_fr_np(rng, d) for _ in range(3))
-    rm1 = np.frombuffer((fields.R - 1).to_bytes(32, "little"), dtype=np.uint8)
-    a[0] = rm1
-    b[-1] = rm1
-    c[d // 2] = rm1
-    if d >= 4:
-        a[1] = 0
-        b[2] = 0
-        b[2, 0] = 1
-        c[3] = rm1
-        a[3] = rm1
-        b[3] = rm1
+    from tests.quotient_cases import block_shape_inputs
+    a, b, c = block_shape_inputs(log_d)
     assert ectx.h_poly(a, b, c).tobytes() == oc.h_poly(a, b, c).tobytes()
 
 

@@ -37,6 +37,11 @@ def test_hooks_library_has_the_switches_and_the_same_abi():
     for s in _header_symbols():
         assert hasattr(lib, s), f"{s} missing from the hooks build"
     assert set(_lib.SIGNATURES) == set(_header_symbols())
+    # the test seams exist in the hooks build only: the shipped library's exported set is the header's and nothing else
+    shipped = C.CDLL(os.path.join(PKG, "libowshen_gpu.so"))
+    for seam in ("og_hook_verify_miller_d", "og_hook_final_exp_d", "og_hook_fe_raw_d"):
+        assert hasattr(lib, seam), f"{seam} missing from the hooks build"
+        assert not hasattr(shipped, seam), f"{seam} is in the shipped library"
 
 
 def test_sources_read_the_environment_only_through_the_hook_macros():

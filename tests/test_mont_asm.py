@@ -11,6 +11,9 @@ import re
 
 import pytest
 
+from tests import field_raw_cases as frc
+from tests.field_raw_cases import operand_sets, worst_lazy31
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 spec = importlib.util.spec_from_file_location("gen_mont_asm", os.path.join(ROOT, "tools", "gen_mont_asm.py"))
 gen = importlib.util.module_from_spec(spec)
@@ -81,22 +84,6 @@ def test_generated_file_is_current():
         assert body, name
         got = [re.match(r'"(.*?)(?:\\n\\t)?"', l.strip()).group(1) for l in body.group(1).splitlines()]
         assert got == gen.routine(terms, plus), f"{name}: mont_gfx950.inc is stale -- run python tools/gen_mont_asm.py"
-
-
-def operand_sets(rng, n_mod, kind):
-    """values for one Fe operand: normalized < 2N, or lazy (limbs < 2^30, e.g. 8N - x limb-wise)"""
-    if kind == "norm":
-        return limbs(rng.randrange(0, 2 * n_mod))
-    if kind == "max":
-        return limbs(2 * n_mod - 1)
-    if kind == "allones":
-        return [MASK] * 8 + [limbs(2 * n_mod - 1)[8]]
-    if kind == "zero":
-        return [0] * 9
-    if kind == "lazy":  # 8N - x limb-wise with borrowed 2^29s (fe_neg_lazy): limbs in (0, 2^30), value <= 8N
-        x, n8 = limbs(rng.randrange(0, 2 * n_mod)), limbs(8 * n_mod)
-        return [n8[j] + ((1 << 29) if j < 8 else 0) - (1 if j > 0 else 0) - x[j] for j in range(9)]
-    raise AssertionError(kind)
 
 
 @pytest.mark.parametrize("mod_name", ["Fq", "Fr"])
@@ -186,16 +173,6 @@ def test_instruction_counts_quoted_in_the_roofline_tooling():
     assert _mads("MUL") == 162 and len(gen.routine(*gen.ROUTINES["MUL"])) == 205
 
 
-def worst_lazy31(n_mod):
-    """the laziest operand the radix-4 NTT hands fe_mul (field.hip.h's contract; ntt.hip k_ntt_block4): eight limbs at 2^31 - 1 and a
-    top limb that takes the value to just under 42 N"""
-    low = [(1 << 31) - 1] * 8
-    top = (42 * n_mod - 1 - value(low + [0])) >> 232
-    l = low + [top]
-    assert 41 * n_mod < value(l) < 42 * n_mod and top < (1 << 31)
-    return l
-
-
 @pytest.mark.parametrize("mod_name", ["Fq", "Fr"])
 def test_mul_takes_one_operand_with_limbs_up_to_2_31(mod_name):
     """the lazy butterflies of k_ntt_block4 multiply a sum whose limbs reach 2^31 (value < 42 N) by a normalized
@@ -225,3 +202,33 @@ def test_mul_takes_one_operand_with_limbs_up_to_2_31(mod_name):
                 assert total < 169 * n_mod * n_mod
                 m = (-total * pow(n_mod, -1, big_r)) % big_r
                 assert all(0 <= v <= MASK for v in out[:8]) and value(out) == (total + m * n_mod) // big_r and value(out) < 2 * n_mod
+
+
+ASM_OPS = {op.asm: op for op in frc.OPS.values() if op.asm}
+
+
+@pytest.mark.parametrize("mod_name", ["Fq", "Fr"])
+@pytest.mark.parametrize("name", list(gen.ROUTINES))
+def test_routine_on_the_shared_raw_case_table(name, mod_name):
+    """the asm text on the case table the host column walk (tests/test_emu_field_raw.py) and the hardware
+    (tests/test_gpu_field_raw.py) answer to: tests/field_raw_cases.py, same cases, same big-integer reference, limb for limb.
+    The interpreter asserts that no write of the 64-bit column accumulator overflows."""
+    op, field = ASM_OPS[name], 1 if mod_name == "Fq" else 0
+    n_mod = frc.MODS[field]
+    assert n_mod == (Q if field else R)
+    terms, plus = gen.ROUTINES[name]
+    names = sorted({t for term in terms for t in term[1:]}) + (["p"] if plus else [])   # operand order of the C++ routine
+    assert len(names) == op.arity and [t[0] for t in terms] == [t[0] for t in op.terms]
+    ins = gen.routine(terms, plus)
+    base = {"v30": 0xDEADBEEF, "v31": 0xDEADBEEF, "inv": (-pow(n_mod, -1, 1 << 29)) % (1 << 29)}
+    for j in range(9):
+        base[f"n{j}"], base[f"r{j}"] = limbs(n_mod)[j], 0xDEADBEEF
+    for k, case in enumerate(frc.table(op.name, field)):
+        regs = dict(base)
+        for nm, l in zip(names, case.limbs):
+            for j in range(9):
+                regs[f"{nm}{j}"] = l[j]
+            for j in range(8):
+                regs[f"{nm}d{j}"] = (l[j] << 1) & M32      # fe_doubled (only the squared operand's are read)
+        run(ins, regs)
+        assert [regs[f"r{j}"] for j in range(9)] == frc.expected(op.name, field, case)[:9], (name, mod_name, k, case.classes)
