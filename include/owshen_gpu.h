@@ -465,6 +465,40 @@ int og_r1cs_write(const og_r1cs* r1cs, uint8_t** file_out, size_t* file_len);
 int og_wtns_read(const uint8_t* wtns, size_t len, uint8_t* values_out, size_t capacity, uint64_t* n_out);
 int og_wtns_write(const uint8_t* values, uint64_t n, uint8_t** wtns_out, size_t* wtns_len);
 
+/* ---- a key from a ceremony: `snarkjs groth16 setup` on the GPU, and the delta step (owshen_amd/csrc/ptau.hip) ----------------
+ * og_setup takes the toxic waste as plain scalars; these calls never see a secret scalar.  With og_zkey_export the file loop
+ * closes: .r1cs + .ptau -> OWPK0001 / OWVK0001 -> .zkey.  No reference interface to replace.
+ *   og_ptau_info      host only, no og_ctx: info[0..3] = power, ceremony power, tauG1 points present (section 2's bytes / 64), 1 if
+ *                     the prepared Lagrange sections 12..15 are all present (they are never read).
+ *   og_setup_ptau     an R1CS + a BN254 .ptau -> malloc'd OWPK0001 / OWVK0001 blobs (og_blob_free) with gamma = delta = 1 --
+ *                     snarkjs' initial zkey; byte for byte og_setup(r1cs, tau, alpha, beta, 1, 1) for the file's (tau, alpha,
+ *                     beta).  The file: iden3 binfile "ptau", version <= 1; section 1 = u32 n8 (32) | q | u32 power | u32
+ *                     ceremonyPower; 2 = tauG1, 2^(power+1) - 1 points; 3 = tauG2, 2^power; 4 = alphaTauG1; 5 = betaTauG1; 6 =
+ *                     betaG2 (one point); any other section (7: contributions, 12..15: Lagrange forms) is skipped.  Points are
+ *                     uncompressed affine, little-endian Montgomery numbers with R = 2^256, G2 as x.c0 | x.c1 | y.c0 | y.c1, all
+ *                     zeros = infinity (the .zkey encoding).  With d = 2^log_d the key's domain (constraints + n_pub + 1 rows),
+ *                     the call needs power >= log_d and reads the first d entries of sections 3..5 and 2 d - 1 of section 2.
+ *                     On the GPU: four inverse DFTs of size d over POINTS (three in G1, one in G2: the Lagrange bases at this
+ *                     library's root 7^((r-1)/d)), the transposed sparse products of A, B, C with those bases (a lane per
+ *                     non-zero, then a segmented sum), one subtraction per H entry.  Header flag 0: the C matrix rides in the key.
+ *                     Refused with OG_ERR_INVALID, the reason naming the section: another base field, a missing or mis-sized
+ *                     section, power < log_d, a coordinate >= q, a point off its curve, tauG1[0] / tauG2[0] not the generators,
+ *                     a used G2 point (tauG2, betaG2) outside the order-r subgroup.  NOT checked: that the file is a valid
+ *                     ceremony (the pairing checks between consecutive powers) -- that is `snarkjs powersoftau verify`'s job.
+ *   og_pk_contribute  the delta step of phase 2: delta <- delta * d, L and H queries <- (1 / d) *; everything else is copied (the
+ *                     header flag too).  d: 32 B canonical, non-zero, < r.  Any OWPK0001 / OWVK0001 pair: og_setup's,
+ *                     og_setup_ptau's, an imported one.  After og_setup_ptau the result is og_setup(.., gamma = 1, delta = d) byte
+ *                     for byte.  The library draws no randomness: d is the caller's, and so is forgetting it.  No contribution
+ *                     transcript is written (snarkjs' challenge hashes are out of scope): og_zkey_export still says "no
+ *                     contributions".
+ * The .ptau format is written down from the published sources of snarkjs 0.7; no file made by snarkjs itself was available to
+ * test against: the tests build their files from a known (tau, alpha, beta). */
+int og_ptau_info(const uint8_t* ptau, size_t len, uint64_t info[4]);
+int og_setup_ptau(og_ctx* ctx, const og_r1cs* r1cs, const uint8_t* ptau, size_t len, uint8_t** pk_out, size_t* pk_len,
+                  uint8_t** vk_out, size_t* vk_len);
+int og_pk_contribute(og_ctx* ctx, const uint8_t* pk, size_t pk_len, const uint8_t* vk, size_t vk_len, const uint8_t d[32],
+                     uint8_t** pk_out, size_t* pk_out_len, uint8_t** vk_out, size_t* vk_out_len);
+
 /* ---- key-generation helpers (trusted setup from explicit toxic waste; tests and bench) --------
  * out[i] = k_i * base.  base: host, canonical affine; scalars_d / out_d: device, canonical. */
 int og_scalar_mul_d(og_ctx* ctx, int group, const uint8_t* base, const uint8_t* scalars_d, size_t n,

@@ -15,6 +15,7 @@
 #include "ctx.h"
 #include "msm.hip.h"
 #include "field.hip.h"
+#include "keygen.h"
 #include <string.h>
 #include <stdlib.h>
 #include <algorithm>
@@ -248,10 +249,10 @@ __global__ void __launch_bounds__(256) k_setup_h(const uint8_t* __restrict__ tox
   fe_store(out + j * 32, fe_from_mont(acc));
 }
 
-static const uint8_t G1_GEN_BYTES[64] = {1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0,
+extern const uint8_t G1_GEN_BYTES[64] = {1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0,
                                          2, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 // the EIP-197 G2 generator: x.c0 | x.c1 | y.c0 | y.c1, 32-byte little-endian each
-static const uint8_t G2_GEN_BYTES[128] = {
+extern const uint8_t G2_GEN_BYTES[128] = {
     0xed, 0xf6, 0x92, 0xd9, 0x5c, 0xbd, 0xde, 0x46, 0xdd, 0xda, 0x5e, 0xf7, 0xd4, 0x22, 0x43, 0x67, 0x79, 0x44, 0x5c, 0x5e, 0x66, 0x00,
     0x6a, 0x42, 0x76, 0x1e, 0x1f, 0x12, 0xef, 0xde, 0x00, 0x18, 0xc2, 0x12, 0xf3, 0xae, 0xb7, 0x85, 0xe4, 0x97, 0x12, 0xe7, 0xa9, 0x35,
     0x33, 0x49, 0xaa, 0xf1, 0x25, 0x5d, 0xfb, 0x31, 0xb7, 0xbf, 0x60, 0x72, 0x3a, 0x48, 0x0d, 0x92, 0x93, 0x93, 0x8e, 0x19, 0xaa, 0x7d,
@@ -280,9 +281,85 @@ struct DevBuf {  // hipMalloc'd scratch released on every exit path
   }
 };
 
+// the QAP rows of a circuit: its constraints, then the input-consistency rows A = wire i for i <= n_pub (B = C = 0)
+int r1cs_qap_rows(const og_r1cs* r, const std::string& who, QapRows* out) {
+  const size_t m = r->n_wires, l = r->n_pub, nc = r->n_constraints;
+  OG_REQUIRE(m >= 1 && l < m && m < (1ull << 31), who + ": bad wire counts");
+  for (int k = 0; k < 3; k++) {
+    OG_REQUIRE(r->ptr[k].size() == nc + 1 && r->ptr[k][0] == 0 && r->ptr[k][nc] == r->col[k].size() && r->val[k].size() == r->col[k].size() * 32,
+               who + ": malformed R1CS");
+    for (uint32_t c : r->col[k]) OG_REQUIRE(c < m, who + ": R1CS column out of range");
+  }
+  const uint8_t one32[32] = {1};
+  for (int k = 0; k < 3; k++) {
+    out->ptr[k] = r->ptr[k];
+    out->col[k] = r->col[k];
+    out->val[k] = r->val[k];
+    for (size_t i = 0; i <= l; i++) {
+      if (k == 0) {
+        out->col[k].push_back((uint32_t)i);
+        out->val[k].insert(out->val[k].end(), one32, one32 + 32);
+      }
+      out->ptr[k].push_back((uint32_t)out->col[k].size());
+    }
+    OG_REQUIRE(out->col[k].size() < (1ull << 32), who + ": nnz too large");
+  }
+  return OG_OK;
+}
+
+// CSR over n_rows rows -> CSR of the transpose over m columns (tcol holds ROWS; entries of a column keep their row order)
+void csr_transpose(const std::vector<uint32_t>& ptr, const std::vector<uint32_t>& col, const std::vector<uint8_t>& val, size_t n_rows, size_t m,
+                   std::vector<uint32_t>& tptr, std::vector<uint32_t>& tcol, std::vector<uint8_t>& tval) {
+  const size_t nnz = col.size();
+  tptr.assign(m + 1, 0);
+  tcol.resize(nnz);
+  tval.resize(nnz * 32);
+  for (uint32_t c : col) tptr[c + 1]++;
+  for (size_t i = 0; i < m; i++) tptr[i + 1] += tptr[i];
+  std::vector<uint32_t> cursor(tptr.begin(), tptr.end() - 1);
+  for (size_t row = 0; row < n_rows; row++)
+    for (uint32_t e = ptr[row]; e < ptr[row + 1]; e++) {
+      const uint32_t pos = cursor[col[e]]++;
+      tcol[pos] = (uint32_t)row;
+      memcpy(&tval[(size_t)pos * 32], &val[(size_t)e * 32], 32);
+    }
+}
+
+// "OWPK0001" and "OWVK0001" (include/owshen_gpu.h) from canonical group elements
+void key_blobs(const KeyParts& k, const QapRows& rows, std::vector<uint8_t>& pk, std::vector<uint8_t>& vk) {
+  pk.clear();
+  const uint64_t head[10] = {0x313030304b50574full, k.m, k.l, (uint64_t)k.log_d, k.n_rows, rows.col[0].size(), rows.col[1].size(), rows.col[2].size(), 0, 0};
+  pk.insert(pk.end(), (const uint8_t*)head, (const uint8_t*)head + 80);  // the 80-byte header is not padded
+  put_padded(pk, k.alpha1, 64);
+  put_padded(pk, k.beta1, 64);
+  put_padded(pk, k.delta1, 64);
+  pk.resize(pk.size() + 64, 0);
+  put_padded(pk, k.beta2, 128);
+  put_padded(pk, k.delta2, 128);
+  for (int q = 0; q < 3; q++) {
+    put_padded(pk, rows.ptr[q].data(), rows.ptr[q].size() * 4);
+    put_padded(pk, rows.col[q].data(), rows.col[q].size() * 4);
+    put_padded(pk, rows.val[q].data(), rows.val[q].size());
+  }
+  const size_t nl = k.m - k.l - 1, nh = ((size_t)1 << k.log_d) - 1;
+  const size_t q_bytes[5] = {k.m * 64, k.m * 64, k.m * 128, nl * 64, nh * 64};
+  for (int q = 0; q < 5; q++) put_padded(pk, k.query[q], q_bytes[q]);
+  // ---- "OWVK0001" | n_pub | alpha_g1 | beta_g2 | gamma_g2 | delta_g2 | IC
+  vk.clear();
+  vk.insert(vk.end(), (const uint8_t*)"OWVK0001", (const uint8_t*)"OWVK0001" + 8);
+  const uint64_t npub = k.l;
+  vk.insert(vk.end(), (const uint8_t*)&npub, (const uint8_t*)&npub + 8);
+  vk.insert(vk.end(), k.alpha1, k.alpha1 + 64);
+  vk.insert(vk.end(), k.beta2, k.beta2 + 128);
+  vk.insert(vk.end(), k.gamma2, k.gamma2 + 128);
+  vk.insert(vk.end(), k.delta2, k.delta2 + 128);
+  vk.insert(vk.end(), k.ic, k.ic + (k.l + 1) * 64);
+}
+
 int keygen_setup(og_ctx* ctx, const og_r1cs* r, const uint8_t toxic[160], std::vector<uint8_t>& pk, std::vector<uint8_t>& vk) {
   const size_t m = r->n_wires, l = r->n_pub, nc = r->n_constraints, n_rows = nc + l + 1;
-  OG_REQUIRE(m >= 1 && l < m && m < (1ull << 31), "og_setup: bad wire counts");
+  QapRows rows;
+  OG_TRY(r1cs_qap_rows(r, "og_setup", &rows));
   int log_d = 1;
   while (((size_t)1 << log_d) < n_rows) log_d++;
   OG_REQUIRE(log_d <= 28, "og_setup: too many constraints for the 2^28 domain");
@@ -290,11 +367,6 @@ int keygen_setup(og_ctx* ctx, const og_r1cs* r, const uint8_t toxic[160], std::v
   for (int k = 0; k < 5; k++) {
     const HFr t = hfr_from_bytes(toxic + 32 * k);
     OG_REQUIRE(!hfr_is_zero(t) && !hfr_ge_mod(t), "og_setup: toxic values must be canonical and non-zero");
-  }
-  for (int k = 0; k < 3; k++) {
-    OG_REQUIRE(r->ptr[k].size() == nc + 1 && r->ptr[k][0] == 0 && r->ptr[k][nc] == r->col[k].size() && r->val[k].size() == r->col[k].size() * 32,
-               "og_setup: malformed R1CS");
-    for (uint32_t c : r->col[k]) OG_REQUIRE(c < m, "og_setup: R1CS column out of range");
   }
   DevBuf dev;
   uint8_t *toxic_d, *derived_d, *lag_d, *at_d[3], *ic_s, *l_s, *h_s;
@@ -315,34 +387,11 @@ int keygen_setup(og_ctx* ctx, const og_r1cs* r, const uint8_t toxic[160], std::v
   OG_TRY(lagrange_evals(ctx, log_d, toxic, lag_d));
   // a_i(tau) = sum_rows M[row][i] L_row(tau): the transposed sparse product (QAP rows = constraints, then the
   // input-consistency rows A = wire i for i <= n_pub)
-  std::vector<uint32_t> full_ptr[3];
-  std::vector<uint32_t> full_col[3];
-  std::vector<uint8_t> full_val[3];
-  uint8_t one32[32] = {1};
   for (int k = 0; k < 3; k++) {
-    full_ptr[k] = r->ptr[k];
-    full_col[k] = r->col[k];
-    full_val[k] = r->val[k];
-    for (size_t i = 0; i <= l; i++) {
-      if (k == 0) {
-        full_col[k].push_back((uint32_t)i);
-        full_val[k].insert(full_val[k].end(), one32, one32 + 32);
-      }
-      full_ptr[k].push_back((uint32_t)full_col[k].size());
-    }
-    const size_t nnz = full_col[k].size();
-    OG_REQUIRE(nnz < (1ull << 32), "og_setup: nnz too large");
-    std::vector<uint32_t> tptr(m + 1, 0), tcol(nnz);
-    std::vector<uint8_t> tval(nnz * 32);
-    for (uint32_t c : full_col[k]) tptr[c + 1]++;
-    for (size_t i = 0; i < m; i++) tptr[i + 1] += tptr[i];
-    std::vector<uint32_t> cursor(tptr.begin(), tptr.end() - 1);
-    for (size_t row = 0; row < n_rows; row++)
-      for (uint32_t e = full_ptr[k][row]; e < full_ptr[k][row + 1]; e++) {
-        const uint32_t pos = cursor[full_col[k][e]]++;
-        tcol[pos] = (uint32_t)row;
-        memcpy(&tval[(size_t)pos * 32], &full_val[k][(size_t)e * 32], 32);
-      }
+    const size_t nnz = rows.col[k].size();
+    std::vector<uint32_t> tptr, tcol;
+    std::vector<uint8_t> tval;
+    csr_transpose(rows.ptr[k], rows.col[k], rows.val[k], n_rows, m, tptr, tcol, tval);
     uint8_t *p_d, *c_d, *v_d;
     OG_TRY(dev.get((m + 1) * 4, &p_d));
     OG_TRY(dev.get(nnz * 4, &c_d));
@@ -372,32 +421,13 @@ int keygen_setup(og_ctx* ctx, const og_r1cs* r, const uint8_t toxic[160], std::v
     OG_HIP(hipStreamSynchronize(ctx->stream));
   }
   const std::vector<uint8_t>&c1 = jobs[6].out, &c2 = jobs[7].out;  // index 0 alpha, 1 beta, 2 gamma, 3 delta
-  // ---- "OWPK0001"
-  pk.clear();
-  const uint64_t head[10] = {0x313030304b50574full, m, l, (uint64_t)log_d, n_rows, full_col[0].size(), full_col[1].size(), full_col[2].size(), 0, 0};
-  pk.insert(pk.end(), (const uint8_t*)head, (const uint8_t*)head + 80);  // the 80-byte header is not padded
-  put_padded(pk, &c1[0], 64);        // alpha_g1
-  put_padded(pk, &c1[64], 64);       // beta_g1
-  put_padded(pk, &c1[192], 64);      // delta_g1
-  pk.resize(pk.size() + 64, 0);
-  put_padded(pk, &c2[128], 128);     // beta_g2
-  put_padded(pk, &c2[384], 128);     // delta_g2
-  for (int k = 0; k < 3; k++) {
-    put_padded(pk, full_ptr[k].data(), full_ptr[k].size() * 4);
-    put_padded(pk, full_col[k].data(), full_col[k].size() * 4);
-    put_padded(pk, full_val[k].data(), full_val[k].size());
-  }
-  for (int q = 0; q < 5; q++) put_padded(pk, jobs[q].out.data(), jobs[q].out.size());
-  // ---- "OWVK0001" | n_pub | alpha_g1 | beta_g2 | gamma_g2 | delta_g2 | IC
-  vk.clear();
-  vk.insert(vk.end(), (const uint8_t*)"OWVK0001", (const uint8_t*)"OWVK0001" + 8);
-  const uint64_t npub = l;
-  vk.insert(vk.end(), (const uint8_t*)&npub, (const uint8_t*)&npub + 8);
-  vk.insert(vk.end(), &c1[0], &c1[0] + 64);
-  vk.insert(vk.end(), &c2[128], &c2[128] + 128);
-  vk.insert(vk.end(), &c2[256], &c2[256] + 128);
-  vk.insert(vk.end(), &c2[384], &c2[384] + 128);
-  vk.insert(vk.end(), jobs[5].out.begin(), jobs[5].out.end());
+  KeyParts parts;
+  parts.m = m; parts.l = l; parts.log_d = log_d; parts.n_rows = n_rows;
+  parts.alpha1 = &c1[0]; parts.beta1 = &c1[64]; parts.delta1 = &c1[192];
+  parts.beta2 = &c2[128]; parts.gamma2 = &c2[256]; parts.delta2 = &c2[384];
+  for (int q = 0; q < 5; q++) parts.query[q] = jobs[q].out.data();
+  parts.ic = jobs[5].out.data();
+  key_blobs(parts, rows, pk, vk);
   return OG_OK;
 }
 

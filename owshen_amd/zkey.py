@@ -158,7 +158,7 @@ def prove_files(ctx, zkey_bytes, wtns_bytes, rs=None, r1cs_bytes=None):
         pk.close()
 
 
-def main(argv=None):
+def main(argv=None, ctx=None):
     import argparse
     import os
     ap = argparse.ArgumentParser(description="snarkjs' .zkey / .wtns files and this library's keys (include/owshen_gpu.h: og_zkey_*, og_wtns_*)")
@@ -171,6 +171,9 @@ def main(argv=None):
     p = sub.add_parser("prove", help="`snarkjs groth16 prove` on the GPU: .zkey + .wtns -> proof.json, public.json, verification_key.json")
     p.add_argument("zkey"), p.add_argument("wtns"), p.add_argument("outdir")
     p.add_argument("--r1cs", help="the circuit's .r1cs (a witness that violates a constraint is then refused instead of proved)")
+    p = sub.add_parser("setup", help="`snarkjs groth16 setup` on the GPU: .r1cs + .ptau -> .zkey (gamma = delta = 1, or delta = --delta)")
+    p.add_argument("r1cs"), p.add_argument("ptau"), p.add_argument("zkey_out")
+    p.add_argument("--delta", metavar="HEX", help="one contribution: the scalar delta (hex, 0 < delta < r); yours to draw and to forget")
     p = sub.add_parser("wtns2bin", help=".wtns -> n x 32 B little-endian values")
     p.add_argument("wtns"), p.add_argument("out")
     p = sub.add_parser("bin2wtns", help="n x 32 B little-endian values -> .wtns")
@@ -188,21 +191,30 @@ def main(argv=None):
         return wr(a.out, read_wtns(rd(a.wtns)).tobytes())
     if a.cmd == "bin2wtns":
         return wr(a.out, write_wtns(np.frombuffer(rd(a.values), dtype=np.uint8).reshape(-1, 32)))
-    from .api import Context
-    ctx = Context(0)
+    own = ctx is None
+    if own:
+        from .api import Context
+        ctx = Context(0)
     try:
         if a.cmd == "import":
             pk, vk = import_zkey(ctx, rd(a.zkey), rd(a.r1cs) if a.r1cs else None)
             wr(a.pk_out, pk), wr(a.vk_out, vk)
         elif a.cmd == "export":
             wr(a.zkey_out, export_zkey(ctx, rd(a.pk), rd(a.vk)))
+        elif a.cmd == "setup":
+            from . import ptau
+            pk, vk = ptau.setup(ctx, read_r1cs(rd(a.r1cs), lib=ctx._lib), rd(a.ptau))
+            if a.delta is not None:
+                pk, vk = ptau.contribute(ctx, pk, vk, int(a.delta, 16))
+            wr(a.zkey_out, export_zkey(ctx, pk, vk))
         else:
             from . import snarkjs_json
             proof, pub, vk = prove_files(ctx, rd(a.zkey), rd(a.wtns), r1cs_bytes=rd(a.r1cs) if a.r1cs else None)
             for path in snarkjs_json.write(a.outdir, vk, proof, [bytes(x) for x in pub]).values():
                 print(os.path.abspath(path))
     finally:
-        ctx.close()
+        if own:
+            ctx.close()
 
 
 if __name__ == "__main__":
