@@ -15,6 +15,18 @@ def test_emu_eddsa_batch(ectx):
     eddsa_cases.case_eddsa_batch(ectx, n_valid=2)
 
 
+def test_emu_eddsa_edges(ectx):
+    """the full edge list of the GPU test (nothing cut: the interpreter takes about 10 ms a record)"""
+    from tests import eddsa_cases
+    eddsa_cases.case_eddsa_edges(ectx)
+
+
+def test_emu_eddsa_shapes(ectx):
+    """up to three workgroups, tiled from the pool's first 59 records (the edge records: the host decides nothing new)"""
+    from tests import eddsa_cases
+    eddsa_cases.case_eddsa_shapes(ectx, (0, 1, 64, 65, 129), reuse=(129, 65, 129), m=59)
+
+
 def test_oracle_mimc7_eddsa_self_consistency():
     """the three reference tests' structure (babyjubjub/tests.rs:3-51) on the MiMC7 variant of sign / verify"""
     from oracle.py import babyjubjub as bj
