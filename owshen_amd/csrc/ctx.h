@@ -10,12 +10,29 @@
 #include <map>
 #include "../../include/owshen_gpu.h"
 
+// Events of the batched prover's stage pipeline (groth16.hip issue_pipeline), a set per scratch slot: og_ctx::pipe_ev[slot][...]
+enum PipeEvent {
+  EV_ROWS,       // prep: A z, B z, C z exist                         -> math (quotient)
+  EV_SORT_A,     // prep: the digit sort of the A query | B | L       -> math (that query's accumulation)
+  EV_SORT_B,
+  EV_SORT_L,
+  EV_QUOT,       // math: h exists                                    -> aux (the H query's sort)
+  EV_SORT_H,     // aux: the digit sort of the H query                -> math (H)
+  EV_ASSEMBLED,  // tail: proofs assembled; the slot's bucket sets and reduction levels are free -> math of the slot's NEXT user
+  EV_PREP_FREE,  // behind the last heavy-bucket kernels (msm_run, after_heavy_ev): its witnesses, rows and sorts are free -> prep of the NEXT user
+  EV_COUNT
+};
+// a call that fans its queries out (issue_fan_out) runs only while the pipeline is idle and borrows slot 0's events under its own names
+enum FanEvent { FAN_B_SORTED = EV_SORT_A, FAN_B1_DONE = EV_SORT_B, FAN_A_DONE = EV_SORT_L, FAN_L_DONE = EV_QUOT,
+                FAN_PRODUCTS = EV_SORT_H };  // (the four products of the two-part assembly: assemble_g1_early records it)
+
 struct og_ctx {
   int device = 0;
   hipStream_t stream = nullptr;   // the stream work is currently issued on (= lanes[lane])
-  // Two streams + two scratch namespaces ("lanes"): the batched prover runs the VALU-bound stages of sub-batch k on
-  // lanes[0] and the memory-bound preparation of sub-batch k + 1 on lanes[1]; `lane` selects the scratch namespace
-  // (= sub-batch parity) the next arena_get uses.  A single small request splits one proof across the two streams instead.
+  // Five streams, all created by og_init: lanes[0..1], tail_lane, aux_lane, copy_lane.  The batched prover's stage pipeline runs
+  // the VALU-bound stages of sub-batch k on lanes[0] and the memory-bound preparation of sub-batch k + 1 on lanes[1]; symmetric
+  // lanes run whole sub-batches side by side on the two; a call that fits one sub-batch fans its queries out over all five
+  // (groth16.hip).  `lane` selects the scratch namespace (= scratch slot) the next arena_get uses.
   hipStream_t lanes[2] = {nullptr, nullptr};
   int lane = 0;
   int n_lanes = 2;               // og_set_lanes: 1 = strictly serial sub-batches (isolated kernel timings)
@@ -33,12 +50,12 @@ struct og_ctx {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   // msm_run: optional side stream for an MSM's tail (heavy buckets, reduction, window combine), see msm_impl.hip.h
   hipStream_t tail_stream = nullptr;   // set by the batched prover around its MSMs, null otherwise
-  hipStream_t tail_lane = nullptr;     // the stream object (created at og_init)
+  hipStream_t tail_lane = nullptr;     // the stream object
   hipStream_t aux_lane = nullptr;      // prove_batch pipeline: the H query's digit sort (needs the quotient of the SAME sub-batch)
   hipEvent_t tail_ev[8] = {};
   unsigned tail_ev_next = 0;
   int msm_tag = 0;                     // which of the caller's MSMs this is (names the buffers a tail still reads)
-  // prove_batch jobs (groth16.hip): a call is enqueued completely (every kernel of every sub-batch, on the four streams) and
+  // prove_batch jobs (groth16.hip): a call is enqueued completely (every kernel of every sub-batch, on its streams) and
   // finished separately (wait for its last kernels, copy the proofs out).  The blocking entry points do both at once;
   // og_withdraw_prove_batch_submit_d / og_job_wait let a caller keep ONE call ahead, so that the next call's cold start
   // (first witnesses, first sorts) runs under the current call's last accumulations.  Call-level buffers come in two sets.
@@ -49,14 +66,12 @@ struct og_ctx {
   std::vector<struct og_job*> done_jobs;        // jobs that completed inside the submit call (small circuits): live handles
                                                 // og_job_wait / og_job_abandon still have to see
   bool last_call_piped = false;        // the previous call went through the stage pipeline (its scratch is guarded by slot events)
-  uint64_t pipe_counter = 0;           // sub-batches ever issued through the stage pipeline (scratch slot = counter mod 3)
+  uint64_t pipe_counter = 0;           // sub-batches ever issued through the stage pipeline (scratch slot = counter mod PIPE_SLOTS)
   hipStream_t copy_lane = nullptr;     // (r, s) in, proofs / flags / public inputs out: never queues behind compute
   bool sort_beside_acc = false;        // set by the pipelined prover: digit sorts run BESIDE bucket accumulation (msm.hip picks the
                                        // small-footprint sort kernels, which fit the registers / LDS the accumulation leaves free)
-  static constexpr int PIPE_SLOTS = 3;  // scratch slots the prove_batch pipeline can rotate over (events exist for three; TWO are used
-                                        // since round 6 -- sub-batch k uses slot k mod 2 --, hooks builds: OG_PIPE_SLOTS=3)
-  static constexpr int PIPE_EVENTS = 12;  // [0..6] stage hand-offs; [7..10] "the math stream is about to launch accumulation A | B1 | L | H";
-                                          // [11] "the slot's PREPARATION-side scratch is free" (groth16.hip: two slots, released early)
+  static constexpr int PIPE_SLOTS = 2;  // scratch slots the prove_batch pipeline rotates over, each released in two steps (groth16.hip)
+  static constexpr int PIPE_EVENTS = EV_COUNT;
   hipEvent_t after_heavy_ev = nullptr;  // set by the pipelined prover around a sub-batch's LAST MSM: msm_run records it behind that MSM's
                                         // heavy-bucket kernels, the last readers of the sub-batch's sorted digit entries
   size_t scratch_budget = 0;            // og_set_scratch_budget: bytes the prover may reserve for sub-batch scratch (0 = the default rule)

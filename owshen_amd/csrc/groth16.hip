@@ -4,9 +4,11 @@
 // withdraw seam: `withdraw_handler` (/root/reference/src/services/api_services/withdraw.rs:27-71)
 // would call og_prove between the ECDSA recover (:34) and the sequencer re-sign (:56).
 //
-// Sub-batches of up to 256 proofs go through a two-stage pipeline on the ctx's two streams (prep: witness, sparse
-// products, digit sorts; math: quotient, bucket accumulation / reduction, assembly -- see prove_batch_impl), with scratch
-// per sub-batch parity, so the memory-bound stages of sub-batch k + 1 run under the VALU-bound ones of k; per sub-batch, in HBM:
+// A call is cut into sub-batches (make_plan) and every sub-batch is issued by ONE of three schedules (prove_enqueue and the
+// issue_* functions in front of it): the stage pipeline -- prep: witness, sparse products, digit sorts; math: quotient, bucket
+// accumulation; tail: reduction, assembly; scratch per slot, so the memory-bound stages of sub-batch k + 1 run under the
+// VALU-bound ones of k --, a call that fits one sub-batch with its queries fanned out over the streams, or sub-batches one
+// after the other on a stream.  Per sub-batch, in HBM:
 //   k_withdraw_*     (og_withdraw_prove_batch_d only) the sub-batch's witnesses
 //   k_spmv x3        a = A z, b = B z, c = C z over the QAP rows              (CSR, one lane per row)
 //   h_poly_device    3 iNTT + 3 coset NTT + pointwise + coset iNTT            (ntt.hip)
@@ -16,8 +18,6 @@
 //   msm_run x4       bucket accumulate + reduce over the compacted, precomputed window tables
 //   msm_digit_sort + msm_run   the H query over the quotient coefficients
 //   k_assemble_*     r/s blinding (s delta2 from a fixed-base table), final sums, affine conversion, 256 B proofs
-// A call that is a single small sub-batch (one withdraw request) instead splits ONE proof across the lanes: the B
-// query on lane 1, everything else on lane 0.
 // (r, s) are explicit inputs: proofs are reproducible and bit-comparable with the oracle.
 #include "ctx.h"
 #include "msm.hip.h"
@@ -507,26 +507,14 @@ bool glv_pair_ok() {
   return ok;
 }
 
-// Scratch slots of the stage pipeline.  Round 3 went from two to three because the preparation of sub-batch k waited for the
-// ASSEMBLY of the slot's previous user -- the very end of the tail stream's chain, and the tail kernels are the ones that find
-// room last.  But what the preparation overwrites (witnesses, A z / B z / C z, the sorted digit entries) is last read by the
-// previous user's heavy-bucket kernels; the bucket sets and reduction levels the late tail kernels work on are not touched
-// before the MATH stage.  So since round 6 a slot is released in two steps -- event [11] behind the last heavy-bucket kernels
-// gates the preparation, event [6] (assembly done) gates the first accumulation -- and TWO slots do what three did:
-// same box, interleaved (profiles/r06b_ab_pipe_slots.txt).  One slot less is ~35 GB of HBM at batch 1024.
-static int pipe_slots() {
-  static const int n = std::max(2, std::min((int)og_ctx::PIPE_SLOTS, (int)OG_HOOK_INT("OG_PIPE_SLOTS", 2)));
-  return n;
-}
-
 static int choose_sub_batch(og_ctx* ctx, const og_pk* pk, size_t n) {
   // Large sub-batches amortise the latency-bound tails (reduction levels, scans: a few hundred microseconds each
   // whatever the batch).  Scratch per proof and per scratch slot: the digit entries of the sorts (4 B x nwin x the compacted
   // query sizes -- a shared wire list counted once -- twice: partition + final order), five d x 32 B polynomial buffers, the
-  // witness, bucket sets and reduction levels; bounded to ~64 GiB per scratch slot (three slots in the stage pipeline) of
+  // witness, bucket sets and reduction levels; bounded to ~64 GiB per scratch slot (two slots in the stage pipeline) of
   // the 288 GB -- the 2^18-wire circuit with 17-bit windows (2^16 buckets per set) is ~230 MB per proof, and 256 proofs per
   // sub-batch still fit -- and to what the device has left: (free memory + what this context's arena already holds) x 0.85
-  // over the three slots, so a GPU shared with other work gets smaller sub-batches instead of a failed allocation.
+  // over the slots, so a GPU shared with other work gets smaller sub-batches instead of a failed allocation.
   size_t pts = pk->d;
   for (int q = 0; q < 3; q++)
     if (pk->sort_src[q] == q) pts += pk->n_dense[q];
@@ -535,13 +523,13 @@ static int choose_sub_batch(og_ctx* ctx, const og_pk* pk, size_t n) {
   if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && total_b) {
     size_t mine = 0;
     for (const auto& kv : ctx->arena) mine += kv.second.second;
-    budget = std::min(budget, std::max<size_t>((size_t)1 << 30, (size_t)((double)(free_b + mine) * 0.85) / pipe_slots()));
+    budget = std::min(budget, std::max<size_t>((size_t)1 << 30, (size_t)((double)(free_b + mine) * 0.85) / og_ctx::PIPE_SLOTS));
   }
   // og_set_scratch_budget: the operator's bound on what the sub-batch slots may reserve together (a GPU shared with other work)
-  if (ctx->scratch_budget) budget = std::min(budget, std::max<size_t>(per, ctx->scratch_budget / pipe_slots()));
+  if (ctx->scratch_budget) budget = std::min(budget, std::max<size_t>(per, ctx->scratch_budget / og_ctx::PIPE_SLOTS));
   size_t sb = budget / (per ? per : 1);
   if (const char* e = getenv("OG_SUB_BATCH")) sb = (size_t)atoi(e);
-  // At most 256 proofs per sub-batch for the 2^18-wire circuit (~230 MB of scratch per proof: three slots of 256 are 177 GB),
+  // At most 256 proofs per sub-batch for the 2^18-wire circuit (~230 MB of scratch per proof: two slots of 256 are 118 GB),
   // more for smaller statements -- up to 1024 where a proof needs <= 40 MB: the natural depth-32 statement (26 k wires, 38 MB per
   // proof) in sub-batches of 252 launches kernels too short to fill the chip and pays 17 latency-bound tails per 4096 proofs.
   // Same box, batch 4096 (hooks builds: OG_SUB_CAP): cap 256 -> 4 297 / 4 280 proofs/s, 512 -> 4 642 / 4 641, 1024 -> 4 817,
@@ -583,8 +571,7 @@ struct ProvePlan {
 };
 
 static int make_plan(og_ctx* ctx, const og_pk* pk, size_t n, ProvePlan* out) {
-  static const bool env_one_lane = OG_HOOK_INT("OG_ONE_LANE", 0) != 0;
-  const bool two_lanes = !env_one_lane && ctx->n_lanes >= 2;
+  const bool two_lanes = ctx->n_lanes >= 2;
   int sb_max = choose_sub_batch(ctx, pk, n);
   const size_t split_max = (size_t)OG_HOOK_INT("OG_SPLIT_MAX", 1024);  // the largest call that fans its queries out (below) instead of halving (hooks builds: OG_SPLIT_MAX=1 restores round 5)
   if (two_lanes && (size_t)sb_max * 2 > n && n >= 2 && n > split_max) sb_max = (int)((n + 1) / 2);
@@ -788,50 +775,468 @@ static void glv_halves(const uint8_t* rs, size_t n, std::vector<uint8_t>& out) {
   }
 }
 
-// witnesses_d: n x m x 32 B canonical, device (or null with `gen`).  rs: n x 64 B host.  proofs: n x 256 B host.
+// ---- the batched prover: one call, enqueued ----------------------------------------------------------------------------------
+// prove_enqueue issues ALL the work of a call and returns an og_job; prove_finish waits for it and copies the results out.
+//   call_begin      call-level buffers, (r, s) / GLV halves up on the copy stream, the drain rule between two calls
+//   sub_front       what every sub-batch starts with, on the stream the schedule chose: witnesses, canonical check, public wires
+//   sub_rows        the three sparse products and the satisfiability check;  sub_quotient: h = (A z . B z - C z) / Z
+//   issue_fan_out | issue_pipeline | issue_serial     ONE of the three schedules (make_plan) takes the sub-batch from there
+//                   to "its results exist", assembly included; each owns its streams and events
+//   job_publish     the og_job and one completion event per stream
+// The MSMs learn their stream through the context (ctx->stream, ctx->lane, tail_stream, msm_tag, after_heavy_ev,
+// sort_beside_acc): every function here that sets one of them puts it back (LaneGuard on the error paths).
 //
-// Scheduling (n_lanes = 2): a two-stage software pipeline over sub-batches, on two streams with per-parity scratch:
+// witnesses (z_d): n x m x 32 B canonical, device (or null with `gen` / `z_host`).  rs: n x 64 B host.  proofs: n x 256 B host.
+// pub_out (optional, host): n x n_pub x 32 B, the public wires 1..n_pub of every witness -- what the caller hands the verifier
+// with the proof (withdraw: root, nullifier_hash, ...), so that it does not have to generate the witness a second time.
+static int prove_finish(og_job* job, size_t* first_bad);
+
+struct ProveCall {
+  og_ctx* ctx;
+  const og_pk* pk;
+  size_t n;
+  ProvePlan plan;
+  int call_slot;
+  const WithdrawGen* gen;       // the witnesses: generated per sub-batch | host memory | the caller's device buffer (canonical
+  const uint8_t *z_host, *z_d;  // unless trusted_z)
+  bool trusted_z;
+  const WinShard* sh;  // a window-sharded front: the five results are the call's output, nothing is assembled
+  bool host_asm;       // og_set_host_chains: the host assembles (prove_finish)
+  const uint8_t* rs;   // host
+  uint8_t *proofs, *pub_out;
+  uint8_t *res[5], *rs_d, *proofs_d, *asm_tmp, *glv_d, *pub_d;  // device, per call slot; res: A | B1 | B2 | L | H, an XYZZ point per proof
+  size_t asm_lanes;
+  uint32_t *flags, *bad;  // [n] unsatisfied | [n] first non-canonical wire / record field
+  bool assembles() const { return !sh && !host_asm; }
+};
+struct SubBatch {
+  size_t g0;  // first proof
+  int sb, slot;  // proofs; scratch namespace (ctx->lane) and, in the stage pipeline, event set
+  const uint8_t* zs;
+  uint8_t *ev[3], *tmp, *h;  // A z | B z | C z, quotient scratch, h
+  uint8_t* res(const ProveCall& c, int k) const { return c.res[k] + g0 * (k == 2 ? 256 : 128); }
+  uint8_t* asm_tmp(const ProveCall& c) const { return c.asm_tmp + g0 * c.asm_lanes * 128 * 17; }  // (its products and tables: its own region)
+  const uint8_t* glv(const ProveCall& c) const { return c.glv_d ? c.glv_d + g0 * 128 : nullptr; }
+};
+
+// the digit sort of witness query q (0 A | 1 B | 2 L) over its compacted wire list into sort slot `slot`, and of h into sort
+// slot 2; a sharded front sorts only this rank's windows k = rank (mod world)
+static int sub_sort(const ProveCall& c, const SubBatch& s, int slot, int q, DigitSort* out) {
+  const og_pk* pk = c.pk;
+  return msm_digit_sort_windows(c.ctx, slot, s.zs, pk->m * 32, pk->n_dense[q], pk->map[q], s.sb, (q == 0 ? pk->a : q == 1 ? pk->b1 : pk->l)->c,
+                                1, c.sh ? c.sh->rank : 0, c.sh ? c.sh->world : 1, out);
+}
+static int sub_sort_h(const ProveCall& c, const SubBatch& s, DigitSort* out) {
+  return msm_digit_sort_windows(c.ctx, 2, s.h, c.pk->d * 32, c.pk->d - 1, nullptr, s.sb, c.pk->h->c, 1, c.sh ? c.sh->rank : 0,
+                                c.sh ? c.sh->world : 1, out);
+}
+
+static int call_begin(ProveCall& c) {
+  og_ctx* ctx = c.ctx;
+  const og_pk* pk = c.pk;
+  const size_t n = c.n;
+  const std::string cs = "#" + std::to_string(c.call_slot);  // call-level buffers exist once per call slot
+  const char* resn[5] = {"g16.res.a", "g16.res.b1", "g16.res.b2", "g16.res.l", "g16.res.h"};
+  uint8_t** res = c.res;
+  if (c.sh) {  // the queries' results ARE the call's output: this rank's partial sums, array by array
+    res[0] = c.sh->partials_d; res[1] = res[0] + n * 128; res[3] = res[1] + n * 128; res[4] = res[3] + n * 128; res[2] = res[4] + n * 128;
+  } else {
+    for (int k = 0; k < 5; k++) OG_TRY(arena_get(ctx, (resn[k] + cs).c_str(), n * (k == 2 ? 256 : 128), (void**)&res[k]));
+  }
+  OG_TRY(arena_get(ctx, ("g16.rs" + cs).c_str(), n * 64, (void**)&c.rs_d));
+  OG_TRY(arena_get(ctx, ("g16.proofs" + cs).c_str(), n * 256, (void**)&c.proofs_d));
+  // og_set_host_chains: a call of a handful of requests leaves its assembly to the host (assemble_on_host, in prove_finish)
+  c.host_asm = !c.sh && ctx->host_chains_max > 0 && n <= (size_t)ctx->host_chains_max;
+  std::vector<uint8_t> glv_h;
+  if (c.assembles()) glv_halves(c.rs, n, glv_h);
+  c.asm_lanes = glv_h.empty() ? 4 : 8;
+  OG_TRY(arena_get(ctx, ("g16.asm" + cs).c_str(), n * c.asm_lanes * 128 * 17, (void**)&c.asm_tmp));  // results + window tables of 16 points per lane
+  c.glv_d = nullptr;
+  if (!glv_h.empty()) OG_TRY(arena_get(ctx, ("g16.glv" + cs).c_str(), n * 128, (void**)&c.glv_d));
+  OG_TRY(arena_get(ctx, ("g16.flags" + cs).c_str(), n * 8, (void**)&c.flags));
+  c.bad = c.flags + n;
+  c.pub_d = nullptr;
+  if (c.pub_out && pk->n_pub) OG_TRY(arena_get(ctx, ("g16.pub" + cs).c_str(), n * pk->n_pub * 32, (void**)&c.pub_d));
+  // (r, s) go in on the copy stream, which never holds compute: the copy does not queue behind a previous call's kernels,
+  // and every stream of this call may read rs_d once the host has seen it complete
+  if (!c.sh) OG_HIP(hipMemcpyAsync(c.rs_d, c.rs, n * 64, hipMemcpyHostToDevice, ctx->copy_lane));  // (a sharded front assembles nothing: no blinding yet)
+  if (c.glv_d) OG_HIP(hipMemcpyAsync(c.glv_d, glv_h.data(), n * 128, hipMemcpyHostToDevice, ctx->copy_lane));
+  OG_HIP(hipStreamSynchronize(ctx->copy_lane));
+  if (ctx->pipe_ev[0][0] == nullptr)
+    for (int p = 0; p < og_ctx::PIPE_SLOTS; p++)
+      for (int e = 0; e < og_ctx::PIPE_EVENTS; e++) OG_HIP(hipEventCreateWithFlags(&ctx->pipe_ev[p][e], hipEventDisableTiming));
+  ctx->sort_beside_acc = c.plan.pipe;
+  // A call may be enqueued while the previous one is still running (og_withdraw_prove_batch_submit_d).  Between two calls
+  // of the stage pipeline the scratch slots are guarded by their events; any other combination shares scratch without such
+  // guards, so the streams are drained first (a no-op for the blocking entry points, which left them idle).
+  if (!(c.plan.pipe && ctx->last_call_piped)) OG_HIP(drain_streams(ctx));
+  ctx->last_call_piped = c.plan.pipe;
+  return OG_OK;
+}
+
+// on ctx->stream, in scratch namespace ctx->lane (the schedule set both)
+static int sub_front(const ProveCall& c, SubBatch& s) {
+  og_ctx* ctx = c.ctx;
+  const og_pk* pk = c.pk;
+  const size_t m = pk->m, d = pk->d, g0 = s.g0, sb_max = (size_t)c.plan.sb_max;
+  const char* evn[3] = {"g16.eva", "g16.evb", "g16.evc"};
+  for (int k = 0; k < 3; k++) OG_TRY(arena_get(ctx, evn[k], sb_max * d * 32, (void**)&s.ev[k]));
+  OG_TRY(arena_get(ctx, "g16.tmp", 32, (void**)&s.tmp));
+  OG_TRY(arena_get(ctx, "g16.h", sb_max * d * 32, (void**)&s.h));
+  s.zs = c.z_d ? c.z_d + g0 * m * 32 : nullptr;
+  OG_HIP(hipMemsetAsync(c.bad + g0, 0xff, (size_t)s.sb * 4, ctx->stream));
+  if (const WithdrawGen* gen = c.gen) {
+    const uint8_t* records = gen->inputs_d + g0 * (size_t)(8 + gen->depth) * 32;
+    uint8_t* zbuf = nullptr;
+    OG_TRY(withdraw_check_records(ctx, gen->depth, records, (size_t)s.sb, c.bad + g0));
+    OG_TRY(arena_get(ctx, "g16.zgen", sb_max * m * 32, (void**)&zbuf));
+    OG_TRY(withdraw_witness(ctx, gen->depth, gen->n_pad3, gen->n_pad2, records, (size_t)s.sb, zbuf));
+    s.zs = zbuf;
+  } else if (c.z_host) {
+    // witnesses in HOST memory (og_prove_batch): the sub-batch crosses PCIe into its slot's staging buffer -- in the stage
+    // pipeline on the prep stream, under the math stage of the previous sub-batch like everything else that stream does.
+    // (Pageable memory: the call holds the host until the copy is done; the math work of sub-batch k is already enqueued by then.)
+    uint8_t* zbuf = nullptr;
+    OG_TRY(arena_get(ctx, "g16.zgen", sb_max * m * 32, (void**)&zbuf));
+    OG_HIP(hipMemcpyAsync(zbuf, c.z_host + g0 * m * 32, (size_t)s.sb * m * 32, hipMemcpyHostToDevice, ctx->stream));
+    s.zs = zbuf;
+  }
+  if (!c.gen && !c.trusted_z) {  // caller-supplied witnesses: every wire must be canonical (one more read of the witness)
+    hipLaunchKernelGGL(k_check_canonical, dim3(grid_for(m, 256), s.sb), dim3(256), 0, ctx->stream, s.zs, m * 32, m, c.bad + g0);
+    OG_HIP(hipGetLastError());
+  }
+  if (c.pub_d)  // wires 1..n_pub of each witness of the sub-batch (a strided device-to-device copy)
+    OG_HIP(hipMemcpy2DAsync(c.pub_d + g0 * pk->n_pub * 32, pk->n_pub * 32, s.zs + 32, m * 32, pk->n_pub * 32, (size_t)s.sb,
+                            hipMemcpyDeviceToDevice, ctx->stream));
+  return OG_OK;
+}
+
+static int sub_rows(const ProveCall& c, const SubBatch& s) {
+  og_ctx* ctx = c.ctx;
+  const og_pk* pk = c.pk;
+  const size_t m = pk->m, d = pk->d;
+  const int sb = s.sb;
+  for (int k = 0; k < 3; k++) {
+    ProfScope ps(ctx, PROF_SPMV, (double)pk->nnz[k] * sb);
+    if (k == 2 && pk->c_is_ab) {
+      hipLaunchKernelGGL(k_mul_rows, dim3(grid_for(d, 256), sb), dim3(256), 0, ctx->stream, s.ev[0], s.ev[1], s.ev[2], d);
+      OG_HIP(hipGetLastError());
+      continue;
+    }
+    hipLaunchKernelGGL(k_spmv, dim3(grid_for(d, 256), sb), dim3(256), 0, ctx->stream, pk->ptr[k], pk->col[k], pk->val[k],
+                       (size_t)pk->n_rows, d, s.zs, m * 32, s.ev[k], d * 32, 1, 1, SPMV_LONG);
+    OG_HIP(hipGetLastError());
+    if (pk->n_long[k]) {
+      hipLaunchKernelGGL(k_spmv_long, dim3(pk->n_long[k], sb), dim3(256), 0, ctx->stream, pk->long_rows[k], pk->ptr[k], pk->col[k],
+                         pk->val[k], s.zs, m * 32, s.ev[k], d * 32, 1, 1);
+      OG_HIP(hipGetLastError());
+    }
+  }
+  OG_HIP(hipMemsetAsync(c.flags + s.g0, 0, (size_t)sb * 4, ctx->stream));
+  if (pk->n_rows) {
+    hipLaunchKernelGGL(k_check_rows, dim3(grid_for(pk->n_rows, 256), sb), dim3(256), 0, ctx->stream, s.ev[0], s.ev[1], s.ev[2],
+                       (size_t)pk->n_rows, d, s.zs, m * 32, c.flags + s.g0);
+    OG_HIP(hipGetLastError());
+  }
+  OG_STEP(ctx, "g16.spmv");
+  return OG_OK;
+}
+
+static int sub_quotient(const ProveCall& c, const SubBatch& s) {
+  ProfScope ps(c.ctx, PROF_HPOLY, (double)c.pk->d * s.sb);
+  OG_TRY(h_poly_device(c.ctx, s.ev[0], s.ev[1], s.ev[2], s.tmp, s.h, (int)c.pk->log_d, s.sb));
+  OG_STEP(c.ctx, "g16.hpoly");
+  return OG_OK;
+}
+
+// The L and H queries of a sub-batch.  With pk->merge_lh (pk_load) they are ONE multi-scalar multiplication over one bucket
+// set: the L half accumulates and stops -- its result slot is the point at infinity --, the H half adds to the same buckets
+// and is reduced once.
+static int msm_l(const ProveCall& c, const SubBatch& s, const DigitSort& ds_l) {
+  if (!c.pk->merge_lh) return msm_run(c.ctx, c.pk->l, ds_l, s.res(c, 3));
+  OG_HIP(hipMemsetAsync(s.res(c, 3), 0, (size_t)s.sb * 128, c.ctx->stream));
+  return msm_run_phase(c.ctx, c.pk->l, ds_l, nullptr, MSM_FIRST);
+}
+static int msm_h(const ProveCall& c, const SubBatch& s, const DigitSort& dh) {
+  return msm_run_phase(c.ctx, c.pk->h, dh, s.res(c, 4), c.pk->merge_lh ? MSM_SECOND : MSM_FULL);
+}
+
+// the sub-batch's proofs from its five results, in one part on ctx->stream (latency-bound scalar multiplications)
+static int sub_assemble(const ProveCall& c, const SubBatch& s) {
+  if (!c.assembles()) return OG_OK;
+  og_ctx* ctx = c.ctx;
+  const og_pk* pk = c.pk;
+  ProfScope ps_asm(ctx, PROF_ASSEMBLE, (double)s.sb);
+  OG_TRY(assemble_g1(ctx, pk->consts1, c.rs_d + s.g0 * 64, s.res(c, 0), s.res(c, 1), s.res(c, 3), s.res(c, 4), (size_t)s.sb, s.asm_tmp(c),
+                     c.proofs_d + s.g0 * 256, s.glv(c)));
+  OG_TRY(assemble_g2(ctx, pk->consts2, pk->fb_delta2, c.rs_d + s.g0 * 64, s.res(c, 2), (size_t)s.sb, c.proofs_d + s.g0 * 256));
+  OG_STEP(ctx, "g16.assemble");
+  return OG_OK;
+}
+
+// ---- schedule 1: a call that fits one sub-batch fans its queries out --------------------------------------------------------
+// Nothing here fills the chip, and every MSM ends in a chain of ~140 dependent additions (its bucket reduction: 0.9 ms in G1,
+// 2.5 ms in G2).  So the four witness queries fan out -- B's sort and G2 MSM on stream 1, its G1 MSM (same sorted entries) on
+// the copy stream, A on the tail stream, L on the aux stream -- while stream 0 goes on to the sparse products, the quotient and
+// the H query; the assembly joins them.  (Round 2 ran A, L, H one after the other on stream 0.)  The side streams are issued
+// BEFORE stream 0's sparse products: launch latency sits in front of every stream.  L and H stay apart here: side by side.
+// The proofs are assembled in two parts (ecmul_impl.hip.h k_assemble_g1_early / _late; OG_ASM_EARLY=0: A/B, the one-part form):
+// what needs A and B1 only runs on A's stream beside the quotient and the H query, C = L + H + three of the products is left.
+// Events: ctx->ev0 the witness is complete, ctx->ev1 B's half of the proof, the rest ctx.h FanEvent.
+static int issue_fan_out(const ProveCall& c, SubBatch& s) {
+  og_ctx* ctx = c.ctx;
+  const og_pk* pk = c.pk;
+  hipEvent_t* fan = ctx->pipe_ev[0];
+  hipStream_t s0 = ctx->lanes[0], s_b2 = ctx->lanes[1], s_b1 = ctx->copy_lane, s_a = ctx->tail_lane, s_l = ctx->aux_lane;
+  const bool asm_early = c.assembles() && OG_HOOK_INT("OG_ASM_EARLY", 1) != 0;
+  const uint8_t* rs_sub = c.rs_d + s.g0 * 64;
+  uint8_t* proofs_sub = c.proofs_d + s.g0 * 256;
+  auto side = [&](int lane_id, hipStream_t st, hipEvent_t after) -> int {
+    ctx->lane = lane_id;  // scratch namespace
+    ctx->stream = st;
+    OG_HIP(hipStreamWaitEvent(st, after, 0));
+    return OG_OK;
+  };
+  ctx->lane = s.slot;
+  ctx->stream = s0;
+  OG_TRY(sub_front(c, s));
+  OG_HIP(hipEventRecord(ctx->ev0, s0));  // the witness is complete
+  DigitSort dsb, dsa, dsl, dh;
+  OG_TRY(side(1, s_b2, ctx->ev0));
+  OG_TRY(sub_sort(c, s, 1, 1, &dsb));
+  OG_HIP(hipEventRecord(fan[FAN_B_SORTED], s_b2));
+  OG_TRY(msm_run(ctx, pk->b2, dsb, s.res(c, 2)));
+  {  // B's half of the proof is assembled right here, on the stream that produced B2: the G2 query is the longest chain of
+     // a request (its bucket reduction: 2.5 ms), and its 1.2 ms of assembly (s delta2 from the fixed-base table, one
+     // inversion) used to queue behind the G1 half on stream 0 instead of running beside it
+    ProfScope ps_asm(ctx, PROF_ASSEMBLE, 0.0);  // (0 items: the G1 half below counts the sub-batch's proofs, og_profile_read must not see them twice)
+    if (c.assembles())  // (a wave per proof, the sum as a tree: OG_ASM_G2_TREE=0 is the lane per proof it replaced here)
+      OG_TRY(assemble_g2(ctx, pk->consts2, pk->fb_delta2, rs_sub, s.res(c, 2), (size_t)s.sb, proofs_sub, OG_HOOK_INT("OG_ASM_G2_TREE", 1) != 0));
+  }
+  OG_HIP(hipEventRecord(ctx->ev1, s_b2));
+  OG_TRY(side(4, s_b1, fan[FAN_B_SORTED]));
+  OG_TRY(msm_run(ctx, pk->b1, dsb, s.res(c, 1)));
+  OG_HIP(hipEventRecord(fan[FAN_B1_DONE], s_b1));
+  OG_TRY(side(2, s_a, ctx->ev0));
+  OG_TRY(sub_sort(c, s, 1, 0, &dsa));
+  OG_TRY(msm_run(ctx, pk->a, dsa, s.res(c, 0)));
+  if (asm_early) {
+    ProfScope ps_asm(ctx, PROF_ASSEMBLE, 0.0);  // (0 items: as for the G2 half above)
+    OG_HIP(hipStreamWaitEvent(s_a, fan[FAN_B1_DONE], 0));
+    OG_TRY(assemble_g1_early(ctx, pk->consts1, rs_sub, s.res(c, 0), s.res(c, 1), (size_t)s.sb, s.asm_tmp(c), proofs_sub, s.glv(c),
+                             fan[FAN_PRODUCTS]));
+  }
+  OG_HIP(hipEventRecord(fan[FAN_A_DONE], s_a));
+  OG_TRY(side(3, s_l, ctx->ev0));
+  OG_TRY(sub_sort(c, s, 1, 2, &dsl));
+  OG_TRY(msm_run(ctx, pk->l, dsl, s.res(c, 3)));
+  OG_HIP(hipEventRecord(fan[FAN_L_DONE], s_l));
+  ctx->lane = s.slot;
+  ctx->stream = s0;
+  OG_TRY(sub_rows(c, s));
+  OG_TRY(sub_quotient(c, s));
+  OG_TRY(sub_sort_h(c, s, &dh));
+  OG_TRY(msm_run_phase(ctx, pk->h, dh, s.res(c, 4), MSM_FULL));
+  OG_STEP(ctx, "g16.msm");
+  if (asm_early) {  // C's sum waits for L and the four PRODUCTS; A's own sum and inversion join at the end
+    OG_HIP(hipStreamWaitEvent(s0, fan[FAN_L_DONE], 0));
+    OG_HIP(hipStreamWaitEvent(s0, fan[FAN_PRODUCTS], 0));
+    ProfScope ps_asm(ctx, PROF_ASSEMBLE, (double)s.sb);
+    OG_TRY(assemble_g1_late(ctx, s.res(c, 3), s.res(c, 4), (size_t)s.sb, s.asm_tmp(c), proofs_sub, c.glv_d != nullptr));
+    OG_STEP(ctx, "g16.assemble");
+  } else {  // the side streams' G1 results; the G2 half is B's stream's (above)
+    for (int e : {FAN_B1_DONE, FAN_A_DONE, FAN_L_DONE}) OG_HIP(hipStreamWaitEvent(s0, fan[e], 0));
+    if (c.assembles()) {
+      ProfScope ps_asm(ctx, PROF_ASSEMBLE, (double)s.sb);
+      OG_TRY(assemble_g1(ctx, pk->consts1, rs_sub, s.res(c, 0), s.res(c, 1), s.res(c, 3), s.res(c, 4), (size_t)s.sb, s.asm_tmp(c), proofs_sub,
+                         s.glv(c)));
+      OG_STEP(ctx, "g16.assemble");
+    }
+  }
+  if (asm_early) OG_HIP(hipStreamWaitEvent(s0, fan[FAN_A_DONE], 0));  // A's half of the proof
+  OG_HIP(hipStreamWaitEvent(s0, ctx->ev1, 0));  // stream 0 ends after B's half too (scratch reuse by the next call)
+  return OG_OK;
+}
+
+// ---- schedule 2: the stage pipeline --------------------------------------------------------------------------------------------
+// A software pipeline over sub-batches on four streams, two scratch slots:
 //   PREP stream (lanes[1])   witness generation, the three sparse products + the satisfiability check, the digit sorts of
-//                            the A | B | L queries, and -- once the quotient of the same sub-batch exists -- the digit sort
-//                            of h: memory- / latency-bound kernels with small register footprints
-//   MATH stream (lanes[0])   quotient (NTT) and the five bucket accumulations: VALU-bound
-//   TAIL stream              each MSM's heavy buckets / reduction / combine, then the sub-batch's proof assembly
+//                            the A | B | L queries: memory- / latency-bound kernels with small register footprints
+//   MATH stream (lanes[0])   quotient (NTT) and the five bucket accumulations, back to back: VALU-bound
+//   AUX stream               the digit sort of h: it needs THIS sub-batch's quotient and is needed by its last accumulation, and
+//                            here it does not queue behind the next sub-batch's preparation (which the prep stream was given first)
+//   TAIL stream              each MSM's heavy buckets / reduction / combine (msm_run sends them to ctx->tail_stream), where
+//                            they fill the ramp-down of the following accumulation; then the sub-batch's proof assembly
 // prep(k + 1) runs under math(k).  All VALU-heavy kernels sit on ONE stream, in order.  (Round 2's first scheme alternated
 // whole sub-batches between two symmetric lanes; once bucket accumulation moved to one-wave workgroups, a 300-register
 // reduction kernel of one lane could wait for the whole length of the other lane's accumulation kernel -- up to 129 ms in
 // the rocprof trace -- because every slot a finishing wave freed was refilled at once by a smaller-footprint wave.)
-// Events: e[p][0] sparse products ready, [1..3] sort A / B / L ready, [4] quotient ready, [5] sort h ready, [6] math done.
-// pub_out (optional, host): n x n_pub x 32 B, the public wires 1..n_pub of every witness -- what the caller hands the verifier
-// with the proof (withdraw: root, nullifier_hash, ...), so that it does not have to generate the witness a second time.
-//
-// prove_enqueue issues ALL the work of the call and returns an og_job; prove_finish waits for it and copies the results out.
-static int prove_finish(og_job* job, size_t* first_bad);
+// Every query keeps its own sorted entries (sort slots 1, 3, 4; a shared wire list is sorted once: pk->sort_src) so that all
+// three can be ready before the math stage needs them.  The slot (= scratch namespace and event set, ctx.h PipeEvent) is the
+// pipeline's sub-batch counter mod 2, and the counter runs on across calls: the next call's first sub-batch must not take the
+// slot this call's last one is still using, and it waits for what the slot's previous user recorded, whichever call that was.
+// A slot is released in two steps: what the preparation overwrites (witnesses, A z / B z / C z, sorted digits) is last read by
+// its previous user's heavy-bucket kernels (EV_PREP_FREE); the bucket sets and reduction levels that the late tail kernels work
+// on are not touched before the math stage (EV_ASSEMBLED).  So TWO slots do what round 3's three did, same box, interleaved
+// (profiles/r06b_ab_pipe_slots.txt); one slot less is ~35 GB of HBM at batch 1024.
+// The quotient sits on the math stream, in front of the sub-batch's accumulations: beside the previous sub-batch's
+// accumulations it loses (DESIGN.md 4.4 -- its ~37 ms per sub-batch on the math stream are the only windows in which the
+// tails' big-register kernels find room).
+static int issue_pipeline(const ProveCall& c, SubBatch& s) {
+  og_ctx* ctx = c.ctx;
+  const og_pk* pk = c.pk;
+  hipStream_t math = ctx->lanes[0], prep = ctx->lanes[1], aux = ctx->aux_lane, tail = ctx->tail_lane;
+  s.slot = (int)(ctx->pipe_counter++ % og_ctx::PIPE_SLOTS);
+  hipEvent_t* ev = ctx->pipe_ev[s.slot];
+  auto on = [&](hipStream_t st) { ctx->stream = st; };
+  auto rec = [&](int e) -> int { OG_HIP(hipEventRecord(ev[e], ctx->stream)); return OG_OK; };
+  auto wait = [&](int e) -> int { OG_HIP(hipStreamWaitEvent(ctx->stream, ev[e], 0)); return OG_OK; };
+  ctx->lane = s.slot;
+  // ---------------- PREP ----------------
+  on(prep);
+  OG_TRY(wait(EV_PREP_FREE));
+  OG_TRY(sub_front(c, s));
+  OG_TRY(sub_rows(c, s));
+  OG_TRY(rec(EV_ROWS));
+  DigitSort ds_a, ds_b, ds_l, dh;
+  OG_TRY(sub_sort(c, s, 1, 0, &ds_a));
+  OG_TRY(rec(EV_SORT_A));
+  if (pk->sort_src[1] == 0) ds_b = ds_a;  // same wire list (pk_load): the sorted entries serve both
+  else OG_TRY(sub_sort(c, s, 3, 1, &ds_b));
+  OG_TRY(rec(EV_SORT_B));
+  if (pk->sort_src[2] == 0) ds_l = ds_a;
+  else if (pk->sort_src[2] == 1) ds_l = ds_b;
+  else OG_TRY(sub_sort(c, s, 4, 2, &ds_l));
+  OG_TRY(rec(EV_SORT_L));
+  // ---------------- QUOTIENT ----------------
+  on(math);
+  OG_TRY(wait(EV_ROWS));
+  OG_TRY(sub_quotient(c, s));
+  OG_TRY(rec(EV_QUOT));
+  on(aux);
+  OG_TRY(wait(EV_QUOT));
+  OG_TRY(sub_sort_h(c, s, &dh));
+  OG_TRY(rec(EV_SORT_H));
+  // ---------------- MATH ----------------
+  on(math);
+  {
+    struct TailGuard {
+      og_ctx* c;
+      ~TailGuard() { c->tail_stream = nullptr; c->msm_tag = 0; c->after_heavy_ev = nullptr; }
+    } tail_guard{ctx};
+    ctx->tail_stream = tail;
+    OG_TRY(wait(EV_ASSEMBLED));  // the bucket sets / reduction levels of this slot: free once its previous user is assembled
+    OG_TRY(wait(EV_SORT_A));
+    ctx->msm_tag = 0;
+    OG_TRY(msm_run(ctx, pk->a, ds_a, s.res(c, 0)));
+    OG_TRY(wait(EV_SORT_B));
+    ctx->msm_tag = 1;
+    OG_TRY(msm_run(ctx, pk->b1, ds_b, s.res(c, 1)));
+    ctx->msm_tag = 2;
+    OG_TRY(msm_run(ctx, pk->b2, ds_b, s.res(c, 2)));
+    OG_TRY(wait(EV_SORT_L));
+    ctx->msm_tag = 3;
+    OG_TRY(msm_l(c, s, ds_l));
+    OG_TRY(wait(EV_SORT_H));
+    // the H query is the sub-batch's last MSM: behind its heavy buckets nothing reads the slot's digit sorts (msm_run records it)
+    ctx->after_heavy_ev = ev[EV_PREP_FREE];
+    if (!pk->merge_lh) ctx->msm_tag = 4;  // (merged: the same tag, the same buckets)
+    OG_TRY(msm_h(c, s, dh));
+  }
+  OG_STEP(ctx, "g16.msm");
+  // Assembly needs every tail, and it is latency-bound (a few waves of scalar multiplications): it is queued on the tail
+  // stream behind the last tail, so the math stream goes straight on to the next sub-batch's quotient instead of idling
+  // through the H query's reduction and the assembly.  (Everything the math stream did for this sub-batch precedes one of
+  // the tails, so "assembled" on the tail stream is also "math done".)
+  on(tail);
+  OG_TRY(sub_assemble(c, s));
+  OG_TRY(rec(EV_ASSEMBLED));
+  on(math);
+  return OG_OK;
+}
+
+// ---- schedule 3: sub-batches one after the other on one stream ----------------------------------------------------------------
+// og_set_lanes(1) (isolated kernel timings) runs every sub-batch on lanes[0].  With two lanes, sub-batches too small to fill
+// the chip (a handful of requests each, below the pipeline's threshold) are latency-bound end to end: whole sub-batches then
+// run side by side, sub-batch k on lanes[k & 1] in scratch namespace k & 1, which is worth ~1.5x (batch 8: 46 vs 68 ms).
+// The witness queries share ONE set of sorted entries (sort slot 1: a third of the pipeline's scratch), interleaved with the MSMs.
+static int issue_serial(const ProveCall& c, SubBatch& s, size_t sub_index) {
+  og_ctx* ctx = c.ctx;
+  const og_pk* pk = c.pk;
+  s.slot = c.plan.sym ? (int)(sub_index & 1) : 0;
+  ctx->lane = s.slot;
+  ctx->stream = ctx->lanes[s.slot];
+  OG_TRY(sub_front(c, s));
+  OG_TRY(sub_rows(c, s));
+  OG_TRY(sub_quotient(c, s));
+  // A, then the queries that share A's wire list (their sort is A's: pk_load), then the rest; `held` = whose list the sorted
+  // entries currently hold
+  DigitSort ds, dh;
+  int order[3] = {0, 1, 2}, held = -1;
+  if (pk->sort_src[1] != 0 && pk->sort_src[2] == 0) std::swap(order[1], order[2]);
+  for (int q : order) {
+    if (pk->sort_src[q] != held) {
+      OG_TRY(sub_sort(c, s, 1, q, &ds));
+      held = pk->sort_src[q];
+    }
+    if (q == 0) OG_TRY(msm_run(ctx, pk->a, ds, s.res(c, 0)));
+    if (q == 1) {
+      OG_TRY(msm_run(ctx, pk->b1, ds, s.res(c, 1)));
+      OG_TRY(msm_run(ctx, pk->b2, ds, s.res(c, 2)));
+    }
+    if (q == 2) OG_TRY(msm_l(c, s, ds));
+  }
+  OG_TRY(sub_sort_h(c, s, &dh));
+  OG_TRY(msm_h(c, s, dh));
+  OG_STEP(ctx, "g16.msm");
+  return sub_assemble(c, s);
+}
+
+// everything is enqueued: the og_job, and one event per stream that marks the end of this call's work there
+static int job_publish(const ProveCall& c, og_job** job_out) {
+  og_ctx* ctx = c.ctx;
+  og_job* job = new og_job();
+  job->id = next_job_id();
+  job->ctx = ctx; job->call_slot = c.call_slot; job->n = c.n; job->n_pub = c.pub_d ? c.pk->n_pub : 0;
+  job->proofs = c.proofs; job->pub_out = c.pub_out; job->proofs_d = c.proofs_d; job->pub_d = c.pub_d; job->flags_d = c.flags;
+  job->bad_kind = c.gen ? 2 : (c.trusted_z ? 0 : 1);
+  if (c.host_asm) {
+    job->host_asm_pk = c.pk;
+    for (int k = 0; k < 5; k++) job->res_d[k] = c.res[k];
+    job->rs_h.assign(c.rs, c.rs + c.n * 64);
+  }
+  for (hipStream_t st : {ctx->lanes[0], ctx->lanes[1], ctx->tail_lane, ctx->aux_lane}) {
+    hipEvent_t e = nullptr;
+    if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess || hipEventRecord(e, st) != hipSuccess) {
+      for (int k = 0; k < job->n_done; k++) (void)hipEventDestroy(job->done[k]);
+      if (e) (void)hipEventDestroy(e);
+      delete job;
+      set_error("og_prove: could not record the completion events");
+      return OG_ERR_HIP;  // (the caller's guard drains the streams)
+    }
+    job->done[job->n_done++] = e;
+  }
+  ctx->jobs[c.call_slot] = job;
+  *job_out = job;
+  return OG_OK;
+}
 
 static int prove_enqueue(og_ctx* ctx, const og_pk* pk, const uint8_t* z_d, size_t n, const uint8_t* rs, uint8_t* proofs,
                          const WithdrawGen* gen, uint8_t* pub_out, og_job** job_out, const uint8_t* z_host = nullptr,
                          bool trusted_z = false, const WinShard* sh = nullptr) {
   *job_out = nullptr;
-  const int wr = sh ? sh->rank : 0, ww = sh ? sh->world : 1;  // this rank's windows: k = wr (mod ww)
-  auto dsort = [&](int slot, const uint8_t* sc, size_t stride, size_t cnt, const uint32_t* map, int batch, int c, DigitSort* out) -> int {
-    return msm_digit_sort_windows(ctx, slot, sc, stride, cnt, map, batch, c, 1, wr, ww, out);
-  };
+  ProveCall c{};
+  c.ctx = ctx; c.pk = pk; c.n = n;
+  c.gen = gen; c.z_host = z_host; c.z_d = z_d; c.trusted_z = trusted_z; c.sh = sh;
+  c.rs = rs; c.proofs = proofs; c.pub_out = pub_out;
   // the first FREE call slot (not a toggle: a blocking call between a submit and its wait would flip a toggle back onto the
   // slot that is still occupied, and the next submit would be refused although only one call is in flight)
-  const int call_slot = ctx->jobs[0] == nullptr ? 0 : 1;
-  OG_REQUIRE(ctx->jobs[call_slot] == nullptr, "og_prove: two calls are already in flight on this context (og_job_wait or og_job_abandon one of them first)");
-  const std::string cs = "#" + std::to_string(call_slot);  // call-level buffers exist once per call slot
-  const size_t m = pk->m, d = pk->d;
-  ProvePlan pp;
-  OG_TRY(make_plan(ctx, pk, n, &pp));
-  const int sb_max = pp.sb_max;
-  const bool split = pp.split, sym = pp.sym, pipe = pp.pipe;
-  const std::vector<int>& plan = pp.plan;
-  uint8_t *res[5], *rs_d, *proofs_d, *asm_tmp;
-  uint32_t* flags;
-  const char* evn[3] = {"g16.eva", "g16.evb", "g16.evc"};
-  struct LaneGuard {  // an error return in the middle of the pipeline leaves no work of this call in flight (the next call
-    og_ctx* c;        // reuses the scratch); on every path the ctx is back on lane 0
-    bool ok = false;  // set once everything is enqueued: then the streams are left running
+  c.call_slot = ctx->jobs[0] == nullptr ? 0 : 1;
+  OG_REQUIRE(ctx->jobs[c.call_slot] == nullptr, "og_prove: two calls are already in flight on this context (og_job_wait or og_job_abandon one of them first)");
+  OG_TRY(make_plan(ctx, pk, n, &c.plan));
+  struct LaneGuard {  // an error return in the middle of the call leaves no work of it in flight (the next call reuses the
+    og_ctx* c;        // scratch); on every path the ctx is back on lane 0
+    bool ok = false;  // (everything is enqueued: the streams are left running)
     ~LaneGuard() {
       if (!ok) (void)drain_streams(c);
       c->lane = 0;
@@ -847,361 +1252,20 @@ static int prove_enqueue(og_ctx* ctx, const og_pk* pk, const uint8_t* z_d, size_
   ctx->call_requests = n;
   ctx->lane = 0;
   ctx->stream = ctx->lanes[0];
-  const char* resn[5] = {"g16.res.a", "g16.res.b1", "g16.res.b2", "g16.res.l", "g16.res.h"};
-  if (sh) {  // the queries' results ARE the call's output: this rank's partial sums, array by array
-    res[0] = sh->partials_d; res[1] = res[0] + n * 128; res[3] = res[1] + n * 128; res[4] = res[3] + n * 128; res[2] = res[4] + n * 128;
-  } else {
-    for (int k = 0; k < 5; k++) OG_TRY(arena_get(ctx, (resn[k] + cs).c_str(), n * (k == 2 ? 256 : 128), (void**)&res[k]));
-  }
-  OG_TRY(arena_get(ctx, ("g16.rs" + cs).c_str(), n * 64, (void**)&rs_d));
-  OG_TRY(arena_get(ctx, ("g16.proofs" + cs).c_str(), n * 256, (void**)&proofs_d));
-  // og_set_host_chains: a call of a handful of requests leaves its assembly to the host (assemble_on_host, in prove_finish)
-  const bool host_asm = !sh && ctx->host_chains_max > 0 && n <= (size_t)ctx->host_chains_max;
-  std::vector<uint8_t> glv_h;
-  if (!sh && !host_asm) glv_halves(rs, n, glv_h);
-  const size_t asm_lanes = glv_h.empty() ? 4 : 8;
-  OG_TRY(arena_get(ctx, ("g16.asm" + cs).c_str(), n * asm_lanes * 128 * 17, (void**)&asm_tmp));  // results + window tables of 16 points per lane
-  uint8_t* glv_d = nullptr;
-  if (!glv_h.empty()) OG_TRY(arena_get(ctx, ("g16.glv" + cs).c_str(), n * 128, (void**)&glv_d));
-  OG_TRY(arena_get(ctx, ("g16.flags" + cs).c_str(), n * 8, (void**)&flags));  // [n] unsatisfied flags | [n] first non-canonical wire / field
-  uint32_t* bad = flags + n;
-  uint8_t* pub_d = nullptr;
-  if (pub_out && pk->n_pub) OG_TRY(arena_get(ctx, ("g16.pub" + cs).c_str(), n * pk->n_pub * 32, (void**)&pub_d));
-  // (r, s) go in on the copy stream, which never holds compute: the copy does not queue behind a previous call's kernels,
-  // and every stream of this call may read rs_d once the host has seen it complete
-  if (!sh) OG_HIP(hipMemcpyAsync(rs_d, rs, n * 64, hipMemcpyHostToDevice, ctx->copy_lane));  // (a sharded front assembles nothing: no blinding yet)
-  if (glv_d) OG_HIP(hipMemcpyAsync(glv_d, glv_h.data(), n * 128, hipMemcpyHostToDevice, ctx->copy_lane));
-  OG_HIP(hipStreamSynchronize(ctx->copy_lane));
-  if (ctx->pipe_ev[0][0] == nullptr)
-    for (int p = 0; p < og_ctx::PIPE_SLOTS; p++)
-      for (int e = 0; e < og_ctx::PIPE_EVENTS; e++) OG_HIP(hipEventCreateWithFlags(&ctx->pipe_ev[p][e], hipEventDisableTiming));
-  ctx->sort_beside_acc = pipe;
-  // A call may be enqueued while the previous one is still running (og_withdraw_prove_batch_submit_d).  Between two calls
-  // of the stage pipeline the scratch slots are guarded by their events; any other combination shares scratch without such
-  // guards, so the streams are drained first (a no-op for the blocking entry points, which left them idle).
-  if (!(pipe && ctx->last_call_piped)) OG_HIP(drain_streams(ctx));
-  ctx->last_call_piped = pipe;
-  hipStream_t math = ctx->lanes[0], prep = pipe ? ctx->lanes[1] : ctx->lanes[0];
-  auto on = [&](hipStream_t st) { ctx->stream = st; };
-  auto rec = [&](hipEvent_t e) -> int {
-    if (pipe) OG_HIP(hipEventRecord(e, ctx->stream));
-    return OG_OK;
-  };
-  auto wait = [&](hipEvent_t e) -> int {
-    if (pipe) OG_HIP(hipStreamWaitEvent(ctx->stream, e, 0));
-    return OG_OK;
-  };
-  hipEvent_t* prev_ev = nullptr;  // the events of the previous sub-batch of THIS call (stage pipeline): gates of the next quotient
+  OG_TRY(call_begin(c));
+  const std::vector<int>& sizes = c.plan.plan;
   size_t g0 = 0;
-  for (size_t sub_index = 0; sub_index < plan.size(); g0 += plan[sub_index], sub_index++) {
-    const int sb = plan[sub_index];
-    // Scratch slot of this sub-batch.  The stage pipeline uses THREE slots: the preparation of sub-batch k + 1 must not wait
-    // for the assembly of k - 1 -- the end of the tail stream's chain, and the tail kernels (92..152 registers) are the ones
-    // that find room last beside the accumulation and the sorts (round 3 trace: every sub-batch boundary cost the math stream
-    // ~65 ms waiting for exactly that) -- but only for k - 2, which is long done.  Symmetric lanes keep two.
-    const int n_slots = pipe_slots();
-    static const bool early_release = OG_HOOK_INT("OG_PIPE_EARLY_RELEASE", 1) != 0;  // (A/B hook: 0 = the preparation waits for the assembly, as before round 6)
-    // (the pipeline's slot index runs on across calls: the next call's first sub-batch must not take the slot this call's
-    // last one is still using, and the slot's "free" event is the one its previous user recorded, whichever call that was)
-    const int par = pipe ? (int)(ctx->pipe_counter++ % n_slots) : (sym ? (int)(sub_index & 1) : 0);
-    if (sym) math = prep = ctx->lanes[par];
-    hipEvent_t* ev_ = ctx->pipe_ev[par];
-    ctx->lane = par;  // scratch namespace of this sub-batch (both stages)
-    uint8_t *ev[3], *tmp, *h;
-    bool asm_on_tail = false;
-    // a call whose queries fan out assembles in two parts (ecmul_impl.hip.h k_assemble_g1_early / _late; OG_ASM_EARLY=0: A/B, the one-part form)
-    const bool asm_early = split && !sh && !host_asm && OG_HOOK_INT("OG_ASM_EARLY", 1) != 0;
-    // ---------------- PREP ----------------
-    on(prep);
-    // the preparation-side scratch of this slot is free once its previous user's last heavy-bucket kernels have run ([11]; the
-    // stage pipeline); symmetric lanes and OG_PIPE_EARLY_RELEASE=0 wait for the previous user's assembly ([6])
-    OG_TRY(wait(pipe && early_release ? ev_[11] : ev_[6]));
-    for (int k = 0; k < 3; k++) OG_TRY(arena_get(ctx, evn[k], (size_t)sb_max * d * 32, (void**)&ev[k]));
-    OG_TRY(arena_get(ctx, "g16.tmp", 32, (void**)&tmp));
-    OG_TRY(arena_get(ctx, "g16.h", (size_t)sb_max * d * 32, (void**)&h));
-    const uint8_t* zs = z_d ? z_d + g0 * m * 32 : nullptr;
-    OG_HIP(hipMemsetAsync(bad + g0, 0xff, (size_t)sb * 4, ctx->stream));
-    if (gen) {
-      OG_TRY(withdraw_check_records(ctx, gen->depth, gen->inputs_d + g0 * (size_t)(8 + gen->depth) * 32, (size_t)sb, bad + g0));
-      uint8_t* zbuf = nullptr;
-      OG_TRY(arena_get(ctx, "g16.zgen", (size_t)sb_max * m * 32, (void**)&zbuf));
-      OG_TRY(withdraw_witness(ctx, gen->depth, gen->n_pad3, gen->n_pad2, gen->inputs_d + g0 * (size_t)(8 + gen->depth) * 32, (size_t)sb,
-                              zbuf));
-      zs = zbuf;
-    } else if (z_host) {
-      // witnesses in HOST memory (og_prove_batch): the sub-batch crosses PCIe into its slot's staging buffer on the prep
-      // stream -- under the math stage of the previous sub-batch, like everything else the prep stream does.  (Pageable
-      // memory: the call holds the host until the copy is done; the math work of sub-batch k is already enqueued by then.)
-      uint8_t* zbuf = nullptr;
-      OG_TRY(arena_get(ctx, "g16.zgen", (size_t)sb_max * m * 32, (void**)&zbuf));
-      OG_HIP(hipMemcpyAsync(zbuf, z_host + g0 * m * 32, (size_t)sb * m * 32, hipMemcpyHostToDevice, ctx->stream));
-      zs = zbuf;
-    }
-    if (!gen && !trusted_z) {  // caller-supplied witnesses: every wire must be canonical (one more read of the witness)
-      hipLaunchKernelGGL(k_check_canonical, dim3(grid_for(m, 256), sb), dim3(256), 0, ctx->stream, zs, m * 32, m, bad + g0);
-      OG_HIP(hipGetLastError());
-    }
-    if (pub_d)  // wires 1..n_pub of each witness of the sub-batch (a strided device-to-device copy)
-      OG_HIP(hipMemcpy2DAsync(pub_d + g0 * pk->n_pub * 32, pk->n_pub * 32, zs + 32, m * 32, pk->n_pub * 32, (size_t)sb,
-                              hipMemcpyDeviceToDevice, ctx->stream));
-    if (split) {
-      // One request: nothing here fills the chip, and every MSM ends in a chain of ~140 dependent additions (its bucket
-      // reduction: 0.9 ms in G1, 2.5 ms in G2).  So the four witness queries fan out -- B's sort and G2 MSM on stream 1, its G1
-      // MSM (same sorted entries) on the copy stream, A on the tail stream, L on the aux stream -- while stream 0 goes on to
-      // the quotient and the H query; the assembly joins them.  (Round 2 ran A, L, H one after the other on stream 0.)
-      OG_HIP(hipEventRecord(ctx->ev0, ctx->lanes[0]));  // the witness is complete
-      hipEvent_t* sev = ctx->pipe_ev[0];                // (the stage pipeline's events are idle in this mode)
-      auto side = [&](int lane_id, hipStream_t st, hipEvent_t after) -> int {
-        ctx->lane = lane_id;  // scratch namespace
-        ctx->stream = st;
-        OG_HIP(hipStreamWaitEvent(st, after, 0));
-        return OG_OK;
-      };
-      DigitSort dsb, dsa, dsl;
-      OG_TRY(side(1, ctx->lanes[1], ctx->ev0));
-      OG_TRY(dsort(1, zs, m * 32, pk->n_dense[1], pk->map[1], sb, pk->b1->c, &dsb));
-      OG_HIP(hipEventRecord(sev[1], ctx->lanes[1]));
-      OG_TRY(msm_run(ctx, pk->b2, dsb, res[2] + g0 * 256));
-      {  // B's half of the proof is assembled right here, on the stream that produced B2: the G2 query is the longest chain of
-         // a request (its bucket reduction: 2.5 ms), and its 1.2 ms of assembly (s delta2 from the fixed-base table, one
-         // inversion) used to queue behind the G1 half on stream 0 instead of running beside it
-        ProfScope ps_asm(ctx, PROF_ASSEMBLE, 0.0);  // (0 items: the G1 half below counts the sub-batch's proofs, og_profile_read must not see them twice)
-        if (!sh && !host_asm)  // (a wave per proof, the sum as a tree: OG_ASM_G2_TREE=0 is the lane per proof it replaced here)
-          OG_TRY(assemble_g2(ctx, pk->consts2, pk->fb_delta2, rs_d + g0 * 64, res[2] + g0 * 256, (size_t)sb, proofs_d + g0 * 256,
-                             OG_HOOK_INT("OG_ASM_G2_TREE", 1) != 0));
-      }
-      OG_HIP(hipEventRecord(ctx->ev1, ctx->lanes[1]));
-      hipStream_t s_b1 = ctx->copy_lane ? ctx->copy_lane : ctx->lanes[1];
-      OG_TRY(side(4, s_b1, sev[1]));
-      OG_TRY(msm_run(ctx, pk->b1, dsb, res[1] + g0 * 128));
-      OG_HIP(hipEventRecord(sev[2], s_b1));
-      hipStream_t s_a = ctx->tail_lane ? ctx->tail_lane : ctx->lanes[1];
-      OG_TRY(side(2, s_a, ctx->ev0));
-      OG_TRY(dsort(1, zs, m * 32, pk->n_dense[0], pk->map[0], sb, pk->a->c, &dsa));
-      OG_TRY(msm_run(ctx, pk->a, dsa, res[0] + g0 * 128));
-      if (asm_early) {  // the part of the G1 assembly that needs A and B1 only: here, beside the quotient and the H query on stream 0
-        ProfScope ps_asm(ctx, PROF_ASSEMBLE, 0.0);  // (0 items: as for the G2 half above)
-        OG_HIP(hipStreamWaitEvent(s_a, sev[2], 0));  // B1
-        OG_TRY(assemble_g1_early(ctx, pk->consts1, rs_d + g0 * 64, res[0] + g0 * 128, res[1] + g0 * 128, (size_t)sb,
-                                 asm_tmp + g0 * asm_lanes * 128 * 17, proofs_d + g0 * 256, glv_d ? glv_d + g0 * 128 : nullptr, sev[5]));
-      }
-      OG_HIP(hipEventRecord(sev[3], s_a));
-      hipStream_t s_l = ctx->aux_lane ? ctx->aux_lane : ctx->lanes[1];
-      OG_TRY(side(3, s_l, ctx->ev0));
-      OG_TRY(dsort(1, zs, m * 32, pk->n_dense[2], pk->map[2], sb, pk->l->c, &dsl));
-      OG_TRY(msm_run(ctx, pk->l, dsl, res[3] + g0 * 128));
-      OG_HIP(hipEventRecord(sev[4], s_l));
-      ctx->lane = 0;
-      ctx->stream = ctx->lanes[0];
-    }
-    for (int k = 0; k < 3; k++) {
-      ProfScope ps(ctx, PROF_SPMV, (double)pk->nnz[k] * sb);
-      if (k == 2 && pk->c_is_ab) {
-        hipLaunchKernelGGL(k_mul_rows, dim3(grid_for(d, 256), sb), dim3(256), 0, ctx->stream, ev[0], ev[1], ev[2], d);
-        OG_HIP(hipGetLastError());
-        continue;
-      }
-      hipLaunchKernelGGL(k_spmv, dim3(grid_for(d, 256), sb), dim3(256), 0, ctx->stream, pk->ptr[k], pk->col[k], pk->val[k],
-                         (size_t)pk->n_rows, d, zs, m * 32, ev[k], d * 32, 1, 1, SPMV_LONG);
-      OG_HIP(hipGetLastError());
-      if (pk->n_long[k]) {
-        hipLaunchKernelGGL(k_spmv_long, dim3(pk->n_long[k], sb), dim3(256), 0, ctx->stream, pk->long_rows[k], pk->ptr[k], pk->col[k],
-                           pk->val[k], zs, m * 32, ev[k], d * 32, 1, 1);
-        OG_HIP(hipGetLastError());
-      }
-    }
-    OG_HIP(hipMemsetAsync(flags + g0, 0, (size_t)sb * 4, ctx->stream));
-    if (pk->n_rows) {
-      hipLaunchKernelGGL(k_check_rows, dim3(grid_for(pk->n_rows, 256), sb), dim3(256), 0, ctx->stream, ev[0], ev[1], ev[2],
-                         (size_t)pk->n_rows, d, zs, m * 32, flags + g0);
-      OG_HIP(hipGetLastError());
-    }
-    OG_STEP(ctx, "g16.spmv");
-    OG_TRY(rec(ev_[0]));
-    // one digit sort per density map: A | B (G1 and G2 copies) | L, each over its compacted wire list.  Pipelined, every
-    // query keeps its own sorted entries (slots 1..3) so that all three can be ready before the math stage needs them;
-    // serial, they share slot 1 and are interleaved with the MSMs as before (a third of the scratch).
-    DigitSort ds_a, ds_b, ds_l, dh;
-    if (pipe) {
-      OG_TRY(dsort(1, zs, m * 32, pk->n_dense[0], pk->map[0], sb, pk->a->c, &ds_a));
-      OG_TRY(rec(ev_[1]));
-      if (pk->sort_src[1] == 0) ds_b = ds_a;  // same wire list (pk_load): the sorted entries serve both
-      else OG_TRY(dsort(3, zs, m * 32, pk->n_dense[1], pk->map[1], sb, pk->b1->c, &ds_b));
-      OG_TRY(rec(ev_[2]));
-      if (pk->sort_src[2] == 0) ds_l = ds_a;
-      else if (pk->sort_src[2] == 1) ds_l = ds_b;
-      else OG_TRY(dsort(4, zs, m * 32, pk->n_dense[2], pk->map[2], sb, pk->l->c, &ds_l));
-      OG_TRY(rec(ev_[3]));
-    }
-    // ---------------- QUOTIENT ----------------
-    // On the math stream, in front of the sub-batch's accumulations.  Round 4 measured the alternative -- the quotient of
-    // sub-batch k + 1 on the aux stream BESIDE the accumulations of sub-batch k (OG_HPOLY_ASIDE=1), its 11 passes gated so
-    // that they start beside a G1 accumulation and not in front of the G2 one, whose accumulators fill the LDS
-    // (OG_HPOLY_GATED) -- and it loses, same box, interleaved: 583.2 / 584.1 (here) against 573.8 / 575.3 (aside, ungated),
-    // 591.0 / 591.5 against 580.4 / 580.6 (aside, gated).  The NTT passes are not the half-idle kernels their 0.43 of an
-    // idealised butterfly count suggested: beside the accumulation they take from it what they cost alone (accumulate
-    // 1490 -> 1571 ms per 1024 proofs for 95 ms of quotient), and the ~37 ms per sub-batch in which the math stream runs the
-    // quotient are the only windows where the tails' big-register kernels (reduction: 184 / 308 registers) find room;
-    // without them every tail kernel waits for an accumulation-kernel boundary, the assembly of sub-batch k - 3 is late, the
-    // preparation of k stalls on its scratch slot, and the math stream idles 170 - 190 ms instead of 35 - 60.
-    static const bool hpoly_aside = OG_HOOK_INT("OG_HPOLY_ASIDE", 0) != 0;
-    const bool quot_aside = pipe && hpoly_aside && ctx->aux_lane != nullptr;
-    static const bool hpoly_gated = OG_HOOK_INT("OG_HPOLY_GATED", 1) != 0;
-    on(quot_aside ? ctx->aux_lane : math);
-    OG_TRY(wait(ev_[0]));
-    {
-      ProfScope ps(ctx, PROF_HPOLY, (double)d * sb);
-      OG_TRY(h_poly_device(ctx, ev[0], ev[1], ev[2], tmp, h, (int)pk->log_d, sb, quot_aside && hpoly_gated && prev_ev ? prev_ev + 7 : nullptr));
-    }
-    OG_STEP(ctx, "g16.hpoly");
-    OG_TRY(rec(ev_[4]));
-    // ---------------- MATH ----------------
-    if (pipe) {
-      // the H query's sort needs THIS sub-batch's quotient and is needed by its last accumulation: on a stream of its own it
-      // does not queue behind the next sub-batch's preparation (which the prep stream was given first)
-      on(ctx->aux_lane ? ctx->aux_lane : prep);
-      OG_TRY(wait(ev_[4]));
-      OG_TRY(dsort(2, h, d * 32, d - 1, nullptr, sb, pk->h->c, &dh));
-      OG_TRY(rec(ev_[5]));
-      on(math);
-      // the five accumulation kernels run back to back on the math stream; each MSM's tail (heavy buckets, reduction,
-      // combine) goes to the tail stream, where it fills the ramp-down of the following accumulation
-      static const bool no_tail = OG_HOOK_INT("OG_NO_TAIL", 0) != 0;
-      struct TailGuard {
-        og_ctx* c;
-        ~TailGuard() { c->tail_stream = nullptr; c->msm_tag = 0; }
-      } tail_guard{ctx};
-      ctx->tail_stream = no_tail ? nullptr : ctx->tail_lane;
-      if (early_release) OG_TRY(wait(ev_[6]));  // the bucket sets / reduction levels of this slot: free once its previous user is assembled
-      OG_TRY(wait(ev_[1]));
-      OG_TRY(rec(ev_[7]));  // "about to launch accumulation A": the gates of the next sub-batch's quotient passes
-      ctx->msm_tag = 0;
-      OG_TRY(msm_run(ctx, pk->a, ds_a, res[0] + g0 * 128));
-      OG_TRY(wait(ev_[2]));
-      OG_TRY(rec(ev_[8]));
-      ctx->msm_tag = 1;
-      OG_TRY(msm_run(ctx, pk->b1, ds_b, res[1] + g0 * 128));
-      ctx->msm_tag = 2;
-      OG_TRY(msm_run(ctx, pk->b2, ds_b, res[2] + g0 * 256));
-      OG_TRY(wait(ev_[3]));
-      OG_TRY(rec(ev_[9]));
-      ctx->msm_tag = 3;
-      if (pk->merge_lh) {  // L and H into ONE bucket set (pk_load): the L half accumulates and stops, its result slot is the point at infinity
-        OG_HIP(hipMemsetAsync(res[3] + g0 * 128, 0, (size_t)sb * 128, ctx->stream));
-        OG_TRY(msm_run_phase(ctx, pk->l, ds_l, nullptr, MSM_FIRST));
-      } else {
-        OG_TRY(msm_run(ctx, pk->l, ds_l, res[3] + g0 * 128));
-      }
-      OG_TRY(wait(ev_[5]));
-      OG_TRY(rec(ev_[10]));
-      {
-        struct AfterHeavy {  // the H query is the sub-batch's last MSM: behind its heavy buckets nothing reads the slot's digit sorts
-          og_ctx* c;
-          ~AfterHeavy() { c->after_heavy_ev = nullptr; }
-        } after_heavy{ctx};
-        ctx->after_heavy_ev = ev_[11];
-        if (pk->merge_lh) {
-          OG_TRY(msm_run_phase(ctx, pk->h, dh, res[4] + g0 * 128, MSM_SECOND));  // (same msm_tag: the same buckets)
-        } else {
-          ctx->msm_tag = 4;
-          OG_TRY(msm_run(ctx, pk->h, dh, res[4] + g0 * 128));
-        }
-      }
-      prev_ev = ev_;
-      // Assembly needs every tail, and it is latency-bound (a few waves of scalar multiplications): it is queued on the
-      // tail stream behind the last tail, so the math stream goes straight on to the next sub-batch's quotient instead of
-      // idling through the H query's reduction and the assembly.  (Everything the math stream did for this sub-batch
-      // precedes one of the tails, so "assembly done" on the tail stream is also "math done".)
-      static const bool asm_on_math = OG_HOOK_INT("OG_ASM_ON_MATH", 0) != 0;  // A/B hook: the old order
-      if (ctx->tail_stream && asm_on_math) {
-        OG_HIP(hipEventRecord(ctx->ev1, ctx->tail_stream));
-        OG_HIP(hipStreamWaitEvent(math, ctx->ev1, 0));
-      }
-      asm_on_tail = ctx->tail_stream != nullptr && !asm_on_math;
-      ctx->tail_stream = nullptr;
-    } else {
-      DigitSort ds;
-      if (!split) {  // (one request: the A, B and L queries are already under way on their own streams)
-        // A, then the queries that share A's wire list (their sort is A's: pk_load), then the rest; `held` = whose list the
-        // one set of sorted entries (slot 1) currently holds
-        int order[3] = {0, 1, 2}, held = -1;
-        if (pk->sort_src[1] != 0 && pk->sort_src[2] == 0) std::swap(order[1], order[2]);
-        for (int q : order) {
-          if (pk->sort_src[q] != held) {
-            OG_TRY(dsort(1, zs, m * 32, pk->n_dense[q], pk->map[q], sb, (q == 0 ? pk->a : q == 1 ? pk->b1 : pk->l)->c, &ds));
-            held = pk->sort_src[q];
-          }
-          if (q == 0) OG_TRY(msm_run(ctx, pk->a, ds, res[0] + g0 * 128));
-          if (q == 1) {
-            OG_TRY(msm_run(ctx, pk->b1, ds, res[1] + g0 * 128));
-            OG_TRY(msm_run(ctx, pk->b2, ds, res[2] + g0 * 256));
-          }
-          if (q == 2) {
-            if (pk->merge_lh) {
-              OG_HIP(hipMemsetAsync(res[3] + g0 * 128, 0, (size_t)sb * 128, ctx->stream));
-              OG_TRY(msm_run_phase(ctx, pk->l, ds, nullptr, MSM_FIRST));
-            } else {
-              OG_TRY(msm_run(ctx, pk->l, ds, res[3] + g0 * 128));
-            }
-          }
-        }
-      }
-      OG_TRY(dsort(2, h, d * 32, d - 1, nullptr, sb, pk->h->c, &dh));
-      // (one request fanned out over the streams keeps L and H apart: there the two run SIDE BY SIDE, which is worth more)
-      OG_TRY(msm_run_phase(ctx, pk->h, dh, res[4] + g0 * 128, pk->merge_lh && !split ? MSM_SECOND : MSM_FULL));
-    }
-    OG_STEP(ctx, "g16.msm");
-    if (split) {  // the side streams' G1 results (A, B1, L); the G2 half joins after the G1 assembly below
-      // (two-part assembly: C's sum waits for the four PRODUCTS [5] and L [4]; A's own sum and inversion [3] join at the end)
-      for (int k = asm_early ? 4 : 2; k <= (asm_early ? 5 : 4); k++) OG_HIP(hipStreamWaitEvent(ctx->lanes[0], ctx->pipe_ev[0][k], 0));
-    }
-    if (asm_on_tail) on(ctx->tail_lane);
-    if (asm_early) {  // the products and A are the side stream's (above): C = L + H + three of the products is left
-      ProfScope ps_asm(ctx, PROF_ASSEMBLE, (double)sb);
-      OG_TRY(assemble_g1_late(ctx, res[3] + g0 * 128, res[4] + g0 * 128, (size_t)sb, asm_tmp + g0 * asm_lanes * 128 * 17, proofs_d + g0 * 256,
-                              glv_d != nullptr));
-      OG_STEP(ctx, "g16.assemble");
-    } else if (!sh && !host_asm) {  // assemble this sub-batch's proofs (latency-bound scalar multiplications)
-      ProfScope ps_asm(ctx, PROF_ASSEMBLE, (double)sb);
-      OG_TRY(assemble_g1(ctx, pk->consts1, rs_d + g0 * 64, res[0] + g0 * 128, res[1] + g0 * 128, res[3] + g0 * 128, res[4] + g0 * 128,
-                         (size_t)sb, asm_tmp + g0 * asm_lanes * 128 * 17, proofs_d + g0 * 256,  // (a sub-batch's products and tables: its own region)
-                         glv_d ? glv_d + g0 * 128 : nullptr));
-      if (!split) OG_TRY(assemble_g2(ctx, pk->consts2, pk->fb_delta2, rs_d + g0 * 64, res[2] + g0 * 256, (size_t)sb, proofs_d + g0 * 256));
-      OG_STEP(ctx, "g16.assemble");
-    }
-    if (asm_early) OG_HIP(hipStreamWaitEvent(ctx->lanes[0], ctx->pipe_ev[0][3], 0));  // A's half of the proof
-    if (split) OG_HIP(hipStreamWaitEvent(ctx->lanes[0], ctx->ev1, 0));  // stream 0 ends after B's half too (scratch reuse by the next call)
-    OG_TRY(rec(ev_[6]));
-    if (asm_on_tail) on(math);
+  for (size_t k = 0; k < sizes.size(); g0 += sizes[k], k++) {
+    SubBatch s{};
+    s.g0 = g0;
+    s.sb = sizes[k];
+    if (c.plan.split) OG_TRY(issue_fan_out(c, s));
+    else if (c.plan.pipe) OG_TRY(issue_pipeline(c, s));
+    else OG_TRY(issue_serial(c, s, k));
   }
-  // everything is enqueued: one event per stream marks the end of this call's work there
-  og_job* job = new og_job();
-  job->id = next_job_id();
-  job->ctx = ctx; job->call_slot = call_slot; job->n = n; job->n_pub = pub_d ? pk->n_pub : 0;
-  job->proofs = proofs; job->pub_out = pub_out; job->proofs_d = proofs_d; job->pub_d = pub_d; job->flags_d = flags;
-  job->bad_kind = gen ? 2 : (trusted_z ? 0 : 1);
-  if (host_asm) {
-    job->host_asm_pk = pk;
-    for (int k = 0; k < 5; k++) job->res_d[k] = res[k];
-    job->rs_h.assign(rs, rs + n * 64);
-  }
-  hipStream_t all[4] = {ctx->lanes[0], ctx->lanes[1], ctx->tail_lane, ctx->aux_lane};
-  for (hipStream_t st : all) {
-    if (!st) continue;
-    hipEvent_t e = nullptr;
-    if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess || hipEventRecord(e, st) != hipSuccess) {
-      for (int k = 0; k < job->n_done; k++) (void)hipEventDestroy(job->done[k]);
-      if (e) (void)hipEventDestroy(e);
-      delete job;
-      set_error("og_prove: could not record the completion events");
-      return OG_ERR_HIP;  // (the guard drains the streams)
-    }
-    job->done[job->n_done++] = e;
-  }
+  OG_TRY(job_publish(c, job_out));
   lane_guard.ok = true;
-  ctx->jobs[call_slot] = job;
-  *job_out = job;
-  if (host_asm) assemble_fixed_on_host(pk, job->rs_h.data(), n, job->host_fixed);  // (the GPU is busy with the call's MSMs meanwhile)
+  if (c.host_asm) assemble_fixed_on_host(pk, (*job_out)->rs_h.data(), n, (*job_out)->host_fixed);  // (the GPU is busy with the call's MSMs meanwhile)
   return OG_OK;
 }
 

@@ -177,18 +177,13 @@ def case_pk_load_rejects_malformed_blobs(ctx):
         assert e.value.code == -1
 
 
-def case_medium_circuit_vs_c_oracle(ctx, n_constraints, n_proofs, sub_batch=None):
-    """Key generated by the product's own setup, handed byte-for-byte to the C oracle prover: proofs for
-    injected (r, s) must be identical.  Sizes pick the 12- and 16-bit window paths and sub-batching."""
-    import os
+def medium_case(ctx, n_constraints, n_proofs):
+    """(key blob, witnesses [n, wires, 32], [(r, s)]) of the random circuit with n_constraints rows, key by the product's own setup"""
     from owshen_amd import groth16 as g16
-    from tests.r1cs_util import oracle_c_key_from_blob
     n_pub = 4
     n_wires, cons, z0 = random_r1cs(n_constraints, n_pub, seed=n_constraints, n_free=8, bool_every=5)
     r1 = g16.R1CS.from_constraints(n_wires, n_pub, cons)
     blob, _vk = g16.setup(ctx, r1, 1234567, 7654321, 1111111, 2222222, 3333333)
-    pk = g16.ProvingKey(ctx, blob)
-    ck = oracle_c_key_from_blob(blob)
     zs = []
     for t in range(n_proofs):
         z = list(z0)
@@ -202,12 +197,23 @@ def case_medium_circuit_vs_c_oracle(ctx, n_constraints, n_proofs, sub_batch=None
                 z[n_wires - len(cons) + k] = av * bv % fields.R
         zs.append(_wit(z))
     rnd = random.Random(77)
-    rs = [(rnd.randrange(fields.R), rnd.randrange(fields.R)) for _ in zs]
+    return blob, np.stack(zs), [(rnd.randrange(fields.R), rnd.randrange(fields.R)) for _ in zs]
+
+
+def case_medium_circuit_vs_c_oracle(ctx, n_constraints, n_proofs, sub_batch=None):
+    """Key generated by the product's own setup, handed byte-for-byte to the C oracle prover: proofs for
+    injected (r, s) must be identical.  Sizes pick the 12- and 16-bit window paths and sub-batching."""
+    import os
+    from owshen_amd import groth16 as g16
+    from tests.r1cs_util import oracle_c_key_from_blob
+    blob, zs, rs = medium_case(ctx, n_constraints, n_proofs)
+    pk = g16.ProvingKey(ctx, blob)
+    ck = oracle_c_key_from_blob(blob)
     old = os.environ.get("OG_SUB_BATCH")
     if sub_batch:
         os.environ["OG_SUB_BATCH"] = str(sub_batch)
     try:
-        got = pk.prove_batch(np.stack(zs), rs)
+        got = pk.prove_batch(zs, rs)
     finally:
         if sub_batch:
             if old is None:
@@ -216,6 +222,29 @@ def case_medium_circuit_vs_c_oracle(ctx, n_constraints, n_proofs, sub_batch=None
                 os.environ["OG_SUB_BATCH"] = old
     for w, (r, s), p in zip(zs, rs, got):
         assert p.tobytes() == ck.prove(w, r, s)
+
+
+def case_stage_pipeline_at_toy_size_equals_one_stream(ctx, monkeypatch):
+    """The stage pipeline on real streams at a size where a sub-batch is a few launches long -- 9 proofs of the 60-constraint
+    circuit in sub-batches 1, 2, 2, 2, 2 (hooks build: OG_PIPE_MIN=1), so both scratch slots are reused twice and every hand-off
+    between the four streams is close in time: the bytes of the same call on ONE stream, where nothing can overtake anything"""
+    from owshen_amd import groth16 as g16
+    blob, zs, rs = medium_case(ctx, 60, 9)
+    pk = g16.ProvingKey(ctx, blob)
+    zs_d = ctx.to_device(zs)
+    monkeypatch.setenv("OG_SUB_BATCH", "2")
+    try:
+        ctx.set_lanes(1)
+        assert pk.plan(9) == ("serial", [2, 2, 2, 2, 1])
+        want = pk.prove_batch_device(zs_d, rs).tobytes()
+        ctx.set_lanes(2)
+        monkeypatch.setenv("OG_PIPE_MIN", "1")
+        assert pk.plan(9) == ("stage pipeline", [1, 2, 2, 2, 2])
+        assert pk.prove_batch_device(zs_d, rs).tobytes() == want
+        assert pk.prove_batch(zs, rs).tobytes() == want   # (witnesses from host memory: copied per sub-batch on the prep stream)
+    finally:
+        ctx.set_lanes(2)
+        pk.close()
 
 
 def case_degenerate_circuits(ctx):

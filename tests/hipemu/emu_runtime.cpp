@@ -92,8 +92,43 @@ struct Prof {
 } prof;
 }  // namespace
 
+namespace {
+// HIPEMU_ISSUE_LOG (hip_runtime.h): read at every operation, so that a test can point one process at a file per case
+struct IssueLog {
+  std::string path;
+  FILE* f = nullptr;
+  std::map<const void*, int> events;  // numbered by first appearance in the current file
+  FILE* file() {
+    const char* p = getenv("HIPEMU_ISSUE_LOG");
+    if (path != (p ? p : "")) {
+      if (f) fclose(f);
+      path = p ? p : "";
+      f = path.empty() ? nullptr : fopen(p, "a");
+      events.clear();
+    }
+    return f;
+  }
+} issue_log;
+}  // namespace
+
+void log_op(char op, void* stream, const void* event, const char* what, size_t bytes) {
+  FILE* f = issue_log.file();
+  if (!f) return;
+  fprintf(f, "%c %d", op, (int)(intptr_t)stream);
+  if (event) fprintf(f, " %d", issue_log.events.emplace(event, (int)issue_log.events.size()).first->second);
+  if (what) fprintf(f, op == 'C' ? " %s %zu" : " %s", what, bytes);
+  fputc('\n', f);
+  fflush(f);
+}
+void log_event_gone(const void* event) { issue_log.events.erase(event); }  // (its address may come back as another event)
+
 static void launch_impl(dim3 grid, dim3 block, size_t shmem, const std::function<void()>& body);
-void launch(dim3 grid, dim3 block, size_t shmem, const std::function<void()>& body, const char* name) {
+void launch(dim3 grid, dim3 block, size_t shmem, const std::function<void()>& body, const char* name, void* stream) {
+  if (issue_log.file()) {
+    char shape[96];
+    snprintf(shape, sizeof shape, "%s %u,%u,%u %u", name ? name : "?", grid.x, grid.y, grid.z, block.x);
+    log_op('L', stream, nullptr, shape);
+  }
   if (!prof.on) return launch_impl(grid, block, shmem, body);
   const auto t0 = std::chrono::steady_clock::now();
   launch_impl(grid, block, shmem, body);

@@ -41,8 +41,13 @@ struct Idx { unsigned x, y, z; };
 extern Idx threadIdx_, blockIdx_;
 extern dim3 blockDim_, gridDim_;
 extern void* dyn_shared;
-void launch(dim3 grid, dim3 block, size_t shmem, const std::function<void()>& body, const char* name = nullptr);
+void launch(dim3 grid, dim3 block, size_t shmem, const std::function<void()>& body, const char* name = nullptr, void* stream = nullptr);
 void sync_threads();
+// HIPEMU_ISSUE_LOG=<file>: every stream operation appends one line (emu_runtime.cpp) -- the ORDER in which a host function issues its
+// launches, records, waits and copies, and on which stream: the one thing an interpreter that runs every launch to completion cannot
+// otherwise show.  Streams are their creation numbers (0 = the null stream), events are numbered by first appearance in the file.
+void log_op(char op, void* stream, const void* event = nullptr, const char* what = nullptr, size_t bytes = 0);
+void log_event_gone(const void* event);
 }  // namespace hipemu
 #define threadIdx hipemu::threadIdx_
 #define blockIdx hipemu::blockIdx_
@@ -57,7 +62,7 @@ void sync_threads();
 #define OG_SHADER_CYCLES() 0ull  // no shader clock to read
 #define OG_LDS_ATOMIC_INC_AGG(arr, key) atomicAdd(&(arr)[key], 1u)  // wave-aggregated LDS increment (ctx.h): lanes run one after the other here
 #define hipLaunchKernelGGL(kern, grid, block, shmem, stream, ...) \
-  hipemu::launch(dim3(grid), dim3(block), (shmem), [&]() { kern(__VA_ARGS__); }, #kern)
+  hipemu::launch(dim3(grid), dim3(block), (shmem), [&]() { kern(__VA_ARGS__); }, #kern, (void*)(stream))
 
 // ---- device intrinsics ---------------------------------------------------------
 static inline unsigned long long __brevll(unsigned long long v) {
@@ -145,26 +150,33 @@ static inline hipError_t hipFree(void* p) { free(p); return hipSuccess; }
 static inline hipError_t hipMemGetInfo(size_t* free_b, size_t* total_b) { *free_b = *total_b = (size_t)256 << 30; return hipSuccess; }
 static inline hipError_t hipHostMalloc(void** p, size_t n, unsigned = 0) { return hipMalloc(p, n); }
 static inline hipError_t hipHostFree(void* p) { free(p); return hipSuccess; }
-static inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t = nullptr) { if (n) memmove(d, s, n); return hipSuccess; }
+static inline const char* hipemu_kind(hipMemcpyKind k) { return k == hipMemcpyHostToDevice ? "h2d" : k == hipMemcpyDeviceToHost ? "d2h" : k == hipMemcpyDeviceToDevice ? "d2d" : "h2h"; }
+static inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind k, hipStream_t st = nullptr) {
+  hipemu::log_op('C', st, nullptr, hipemu_kind(k), n);
+  if (n) memmove(d, s, n);
+  return hipSuccess;
+}
 static inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { if (n) memmove(d, s, n); return hipSuccess; }
-static inline hipError_t hipMemcpy2DAsync(void* d, size_t dpitch, const void* s, size_t spitch, size_t width, size_t height, hipMemcpyKind, hipStream_t = nullptr) {
+static inline hipError_t hipMemcpy2DAsync(void* d, size_t dpitch, const void* s, size_t spitch, size_t width, size_t height, hipMemcpyKind k, hipStream_t st = nullptr) {
+  hipemu::log_op('C', st, nullptr, hipemu_kind(k), width * height);
   for (size_t r = 0; r < height; r++) memmove((uint8_t*)d + r * dpitch, (const uint8_t*)s + r * spitch, width);
   return hipSuccess;
 }
-static inline hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t = nullptr) { memset(d, v, n); return hipSuccess; }
+static inline hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t st = nullptr) { hipemu::log_op('C', st, nullptr, "set", n); memset(d, v, n); return hipSuccess; }
 static inline hipError_t hipMemset(void* d, int v, size_t n) { memset(d, v, n); return hipSuccess; }
-static inline hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { *s = (void*)0x1; return hipSuccess; }
+inline uintptr_t hipemu_streams_made = 0;  // handles are creation numbers (nothing dereferences a stream)
+static inline hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { *s = (void*)++hipemu_streams_made; return hipSuccess; }
 static inline hipError_t hipStreamDestroy(hipStream_t) { return hipSuccess; }
-static inline hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
+static inline hipError_t hipStreamSynchronize(hipStream_t st) { hipemu::log_op('S', st); return hipSuccess; }
 static inline hipError_t hipDeviceSynchronize() { return hipSuccess; }
 static inline hipError_t hipEventCreate(hipEvent_t* e) { *e = new hipemu_event(); return hipSuccess; }
 enum { hipEventDisableTiming = 2 };
 static inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e = new hipemu_event(); return hipSuccess; }
-static inline hipError_t hipEventDestroy(hipEvent_t e) { delete e; return hipSuccess; }
-static inline hipError_t hipEventRecord(hipEvent_t e, hipStream_t = nullptr) { e->t = std::chrono::steady_clock::now(); return hipSuccess; }
+static inline hipError_t hipEventDestroy(hipEvent_t e) { hipemu::log_event_gone(e); delete e; return hipSuccess; }
+static inline hipError_t hipEventRecord(hipEvent_t e, hipStream_t st = nullptr) { hipemu::log_op('R', st, e); e->t = std::chrono::steady_clock::now(); return hipSuccess; }
 static inline hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }
 static inline hipError_t hipEventQuery(hipEvent_t) { return hipSuccess; }  // (launches run to completion when issued)
 static inline hipError_t hipEventElapsedTime(float* ms, hipEvent_t a, hipEvent_t b) {
   *ms = std::chrono::duration<float, std::milli>(b->t - a->t).count(); return hipSuccess;
 }
-static inline hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned = 0) { return hipSuccess; }
+static inline hipError_t hipStreamWaitEvent(hipStream_t st, hipEvent_t e, unsigned = 0) { hipemu::log_op('W', st, e); return hipSuccess; }

@@ -4,7 +4,7 @@ sub-batch in front of something that is not the pipeline:
 
   * the strictly serial path (og_set_lanes(1): one stream, one slot) must produce the same 1024 x 256 bytes;
   * the C restatement re-proves the first and the last proof of EVERY sub-batch (sub-batch k runs in slot k mod 2, so the
-    sample straddles each slot's reuse -- k and k + 2, released in two steps: groth16.hip pipe_slots) and must produce the same bytes;
+    sample straddles each slot's reuse -- k and k + 2, released in two steps: ctx.h PIPE_SLOTS) and must produce the same bytes;
   * og_verify accepts all 1024 proofs with the public inputs the call returned, and refuses a proof for its neighbour's.
 
 The reference's convention for the seam: a burn is accepted by `verify` or refused

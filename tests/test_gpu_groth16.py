@@ -33,6 +33,10 @@ def test_medium_circuit_vs_c_oracle(ctx, n_constraints, n_proofs, sub_batch):
     cases.case_medium_circuit_vs_c_oracle(ctx, n_constraints, n_proofs, sub_batch)
 
 
+def test_stage_pipeline_at_toy_size_equals_one_stream(ctx_hooks, monkeypatch):
+    cases.case_stage_pipeline_at_toy_size_equals_one_stream(ctx_hooks, monkeypatch)
+
+
 def test_degenerate_circuits(ctx):
     cases.case_degenerate_circuits(ctx)
 
