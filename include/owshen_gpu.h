@@ -443,7 +443,8 @@ void og_blob_free(uint8_t* blob);
  *                   matrix), its proof simply does not verify.  Refused with OG_ERR_INVALID: another curve or protocol, a
  *                   section whose length disagrees with the header, a coordinate >= q, a point off its curve, a coefficient
  *                   >= r or outside the matrix.  Proofs made with the imported key are the ones snarkjs' prover makes for
- *                   the same (r, s).
+ *                   the same (r, s).  Subgroup membership of the key's G2 points is not checked here (it would change what
+ *                   this call refuses): a key that passes og_pk_verify, below, has all of them in the order-r subgroup.
  *                   r1cs (optional, may be NULL): the circuit the key was made for, as og_r1cs_read returns it.  Its A and B must
  *                   be the key's coefficient section row for row (else OG_ERR_INVALID: not this key's circuit); its C matrix
  *                   then rides in the imported key (flag 0) and OG_ERR_UNSATISFIED works as for a key of og_setup.
@@ -451,7 +452,7 @@ void og_blob_free(uint8_t* blob);
  *   og_r1cs_write   the inverse (malloc'd, og_blob_free): what `snarkjs r1cs info` / `snarkjs groth16 setup` read.
  *   og_zkey_export  the way back: an OWPK0001 + OWVK0001 pair as a .zkey that `snarkjs groth16 prove` accepts (C matrix left
  *                   behind, H section by the inverse transform, "no contributions": `snarkjs zkey verify` against a .ptau
- *                   will not pass, proving and verifying do).
+ *                   will not pass, proving and verifying do, and so does og_pk_verify after an import beside the .r1cs).
  *   og_wtns_read    a .wtns -> n x 32 B canonical values (values_out == NULL: only *n_out); host only, no og_ctx.
  *   og_wtns_write   the inverse (malloc'd, og_blob_free).
  * The formats are written down from the published sources of snarkjs 0.7 / ffjavascript; no file made by snarkjs itself was
@@ -484,13 +485,45 @@ int og_wtns_write(const uint8_t* values, uint64_t n, uint8_t** wtns_out, size_t*
  *                     Refused with OG_ERR_INVALID, the reason naming the section: another base field, a missing or mis-sized
  *                     section, power < log_d, a coordinate >= q, a point off its curve, tauG1[0] / tauG2[0] not the generators,
  *                     a used G2 point (tauG2, betaG2) outside the order-r subgroup.  NOT checked: that the file is a valid
- *                     ceremony (the pairing checks between consecutive powers) -- that is `snarkjs powersoftau verify`'s job.
+ *                     ceremony (the pairing checks between consecutive powers) -- that is og_ptau_verify's job, below.
  *   og_pk_contribute  the delta step of phase 2: delta <- delta * d, L and H queries <- (1 / d) *; everything else is copied (the
  *                     header flag too).  d: 32 B canonical, non-zero, < r.  Any OWPK0001 / OWVK0001 pair: og_setup's,
  *                     og_setup_ptau's, an imported one.  After og_setup_ptau the result is og_setup(.., gamma = 1, delta = d) byte
  *                     for byte.  The library draws no randomness: d is the caller's, and so is forgetting it.  No contribution
  *                     transcript is written (snarkjs' challenge hashes are out of scope): og_zkey_export still says "no
  *                     contributions".
+ *   og_ptau_verify    `snarkjs powersoftau verify` without the contribution transcripts (section 7 is not read): is every
+ *                     section a geometric sequence in the ratio tauG2[1] carries?  OG_OK means the verdict is in *failed_out: 0 if
+ *                     everything holds, otherwise one bit per failed check -- every check runs, the mask is complete, and
+ *                     og_last_error() names the failed checks.  With rho_i the challenge scalars below, N the points of a section,
+ *                     S0 = sum_{i<N-1} rho_i P_i and S1 = sum_{i<N-1} rho_i P_{i+1}:
+ *                        1  tauG1:       e(S1, G2) = e(S0, tauG2[1])         4  alphaTauG1: the same
+ *                        2  tauG2:       e(tauG1[1], S0) = e(G1, S1)         8  betaTauG1:  the same
+ *                       16  betaG2:      e(betaTauG1[0], G2) = e(G1, betaG2)
+ *                     A point at infinity anywhere in a section sets that section's bit (no ceremony holds one).  Malformed
+ *                     input is OG_ERR_INVALID with og_setup_ptau's reasons, here for EVERY point of sections 2..6, not a prefix.
+ *                     On the GPU: per section one vector of scalars, one digit sort, two sums over plain bases (from point 0,
+ *                     from point 1); on the host: one two-pairing product per check.
+ *   og_pk_verify      `snarkjs zkey verify`, likewise: is (pk, vk) the key of THIS circuit from THIS file, up to its delta?  The
+ *                     delta = 1 key (pk0, vk0) is rebuilt as og_setup_ptau builds it (same refusals), then, as bits of *failed_out:
+ *                        1  header, domain, matrices, alpha1, beta1, beta2 of pk equal pk0's; alpha, beta, gamma of vk equal
+ *                           vk0's; lengths equal     2  the A, B1, B2 queries are pk0's, byte for byte     4  vk's IC is vk0's
+ *                        8  delta1, delta2 not infinity, canonical, on their curves, delta2 in the order-r subgroup, pk's delta2 =
+ *                           vk's, e(delta1, G2) = e(G1, delta2)
+ *                       16  L: every entry canonical and on the curve, e(sum rho_i L_i, delta2) = e(sum rho_i L0_i, G2)
+ *                       32  H: the same over the H query
+ *                     If delta2 itself is unusable (infinity, off the twist, outside the subgroup) 16 and 32 are set with 8; if the
+ *                     header or a length differs from pk0's no query lies where it should and every bit is set.  A key with
+ *                     header flag 1 (imported without its .r1cs) is OG_ERR_INVALID: import it beside its .r1cs.  A key that
+ *                     passes has every G2 element in the subgroup (bits 1, 2 and 8 cover them).  Accepts og_setup_ptau's key,
+ *                     any number of og_pk_contribute steps on it, og_setup(.., gamma = 1, any delta) for the file's (tau, alpha,
+ *                     beta), and such a key after og_zkey_export / og_zkey_import with its r1cs.
+ *                     Both calls are refused while a submitted prove call is pending (they use the lone MSM's scratch).
+ *                     The challenge scalars: the library draws no randomness, so they are Fiat-Shamir.  seed = keccak256(tag |
+ *                     keccak256(ptau) [| keccak256(pk) | keccak256(vk)]) mod r -- every byte of the inputs, so whoever wrote them
+ *                     could not know the scalars --, rho_i = the low 128 bits of MiMC7 hash2(seed, section * 2^32 + i), computed
+ *                     on the device.  A section that is NOT what it should be passes only if its points satisfy one linear
+ *                     relation in the rho_i: probability about 2^-128.
  * The .ptau format is written down from the published sources of snarkjs 0.7; no file made by snarkjs itself was available to
  * test against: the tests build their files from a known (tau, alpha, beta). */
 int og_ptau_info(const uint8_t* ptau, size_t len, uint64_t info[4]);
@@ -498,6 +531,9 @@ int og_setup_ptau(og_ctx* ctx, const og_r1cs* r1cs, const uint8_t* ptau, size_t 
                   uint8_t** vk_out, size_t* vk_len);
 int og_pk_contribute(og_ctx* ctx, const uint8_t* pk, size_t pk_len, const uint8_t* vk, size_t vk_len, const uint8_t d[32],
                      uint8_t** pk_out, size_t* pk_out_len, uint8_t** vk_out, size_t* vk_out_len);
+int og_ptau_verify(og_ctx* ctx, const uint8_t* ptau, size_t len, uint32_t* failed_out);
+int og_pk_verify(og_ctx* ctx, const og_r1cs* r1cs, const uint8_t* ptau, size_t len, const uint8_t* pk, size_t pk_len,
+                 const uint8_t* vk, size_t vk_len, uint32_t* failed_out);
 
 /* ---- key-generation helpers (trusted setup from explicit toxic waste; tests and bench) --------
  * out[i] = k_i * base.  base: host, canonical affine; scalars_d / out_d: device, canonical. */

@@ -1,5 +1,6 @@
 // Groth16 key generation from a powers-of-tau file: `snarkjs groth16 setup` on the GPU (og_setup_ptau), the one-scalar delta
-// step of phase 2 (og_pk_contribute), and a host-only look at a .ptau's header (og_ptau_info).
+// step of phase 2 (og_pk_contribute), a host-only look at a .ptau's header (og_ptau_info), and the two checks that go with
+// them: is a file a ceremony (og_ptau_verify), is a key this circuit's key from this ceremony (og_pk_verify) -- at the end.
 //
 // No reference counterpart: the snapshot holds no prover and no key.  og_setup (keygen.hip) takes the toxic
 // waste as plain scalars, which is good for tests and benchmarks only; here no secret scalar is ever in the process -- the
@@ -21,13 +22,16 @@
 //
 // The file format is written down from snarkjs' published sources (powersoftau_new.js / binfileutils); no file made by snarkjs
 // itself was available to test against.  Whether the file is a VALID ceremony (the geometric-sequence
-// pairing checks) is `snarkjs powersoftau verify`'s job and is not checked here; what is checked on every point that is used:
-// coordinates < q, on the curve, tauG1[0] / tauG2[0] the generators, G2 points in the order-r subgroup.
+// pairing checks) is not og_setup_ptau's business -- og_ptau_verify below asks that; what og_setup_ptau checks on every point
+// it uses: coordinates < q, on the curve, tauG1[0] / tauG2[0] the generators, G2 points in the order-r subgroup.
 #include "ctx.h"
 #include "field.hip.h"
 #include "ec.hip.h"
 #include "snarkfile.hip.h"
 #include "keygen.h"
+#include "mimc7.hip.h"
+#include "msm.hip.h"
+#include "verify_tower.h"
 #include <string.h>
 #include <stdlib.h>
 #include <algorithm>
@@ -124,6 +128,46 @@ __global__ void __launch_bounds__(64) k_smul_uniform(const uint8_t* __restrict__
   r.store(out + i * Affine<T>::BYTES);
 }
 
+// The challenge scalars of og_ptau_verify / og_pk_verify: out[i] = the low 128 bits of MiMC7 hash2(seed, section 2^32 + i), a
+// lane per scalar, as the 32-byte canonical scalars the digit sort reads.  seed: 32 B canonical, on the device.
+__global__ void __launch_bounds__(128) k_challenge_scalars(const uint32_t* __restrict__ consts, const uint8_t* __restrict__ seed, uint32_t section,
+                                                          size_t n, uint8_t* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t idx[8] = {(uint32_t)i, section, 0, 0, 0, 0, 0, 0};
+  const Fr h = fe_from_mont(mimc7_hash2<false>(consts, fe_to_mont(fe_load<FrParams>(seed)), fe_to_mont(fe_from_words<FrParams>(idx))));
+  uint32_t w[8];
+  fe_to_words(w, h);
+  uint4* q = reinterpret_cast<uint4*>(out + i * 32);
+  q[0] = make_uint4(w[0], w[1], w[2], w[3]);
+  q[1] = make_uint4(0, 0, 0, 0);
+}
+
+// Canonical affine points (a key's bytes) -> affine Montgomery, checked: flags[0] |= 1: a coordinate >= q; |= 2: a point off
+// the curve (such an entry is stored as infinity: nothing after this kernel meets a point outside the curve).  b: the
+// curve's constant in Montgomery form.  All zeros is the point at infinity, on both sides.
+template <class T>
+__global__ void __launch_bounds__(256) k_canon_to_mont(const uint8_t* __restrict__ in, size_t n, const uint8_t* __restrict__ b_mont,
+                                                      uint8_t* __restrict__ out_mont, uint32_t* __restrict__ flags) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const Affine<T> c = Affine<T>::load(in + i * Affine<T>::BYTES);
+  Affine<T> m = Affine<T>::inf();
+  if (lem_or(c.x) | lem_or(c.y)) {
+    if (!lem_lt(c.x) || !lem_lt(c.y)) {
+      atomicOr(flags, 1u);
+    } else {
+      m = {FieldIO<T>::to_mont(c.x), FieldIO<T>::to_mont(c.y)};
+      const T b = FieldIO<T>::load(b_mont);
+      if (!(f_sqr(m.y) == f_add(f_mul(f_sqr(m.x), m.x), b))) {
+        atomicOr(flags, 2u);
+        m = Affine<T>::inf();
+      }
+    }
+  }
+  m.store(out_mont + i * Affine<T>::BYTES);
+}
+
 // ---- the file -----------------------------------------------------------------------------------------------------------------
 static const uint32_t FR_WORDS[8] = {0xf0000001u, 0x43e1f593u, 0x79b97091u, 0x2833e848u, 0x8181585du, 0xb85045b6u, 0xe131a029u, 0x30644e72u};
 static K256 fr_order(uint32_t minus) {
@@ -165,7 +209,8 @@ static int ptau_decode(og_ctx* ctx, ZDev& dev, BinFile& bf, int sec, bool g2, si
   return lem_convert(ctx, dev, g2, false, in.data(), n_dev, canon.data(), *mont_d, who + ": " + PTAU_SEC[sec]);
 }
 
-static int g2_subgroup_check(og_ctx* ctx, ZDev& dev, const uint8_t* mont_d, size_t n, const std::string& who_sec) {
+// *outside = 1 if some point of the n (affine Montgomery, device) is not in the order-r subgroup
+static int g2_subgroup_flags(og_ctx* ctx, ZDev& dev, const uint8_t* mont_d, size_t n, bool* outside) {
   uint8_t* f_d;
   OG_TRY(dev.get(4, &f_d));
   OG_HIP(hipMemsetAsync(f_d, 0, 4, ctx->stream));
@@ -174,7 +219,14 @@ static int g2_subgroup_check(og_ctx* ctx, ZDev& dev, const uint8_t* mont_d, size
   uint32_t flags = 0;
   OG_HIP(hipMemcpyAsync(&flags, f_d, 4, hipMemcpyDeviceToHost, ctx->stream));
   OG_HIP(hipStreamSynchronize(ctx->stream));
-  OG_REQUIRE(flags == 0, who_sec + ": a point is not in the order-r subgroup");
+  *outside = flags != 0;
+  return OG_OK;
+}
+
+static int g2_subgroup_check(og_ctx* ctx, ZDev& dev, const uint8_t* mont_d, size_t n, const std::string& who_sec) {
+  bool outside = false;
+  OG_TRY(g2_subgroup_flags(ctx, dev, mont_d, n, &outside));
+  OG_REQUIRE(!outside, who_sec + ": a point is not in the order-r subgroup");
   return OG_OK;
 }
 
@@ -229,11 +281,8 @@ static int point_spmv(og_ctx* ctx, const uint8_t* lag_d, const std::vector<uint3
   return OG_OK;
 }
 
-int ptau_setup(og_ctx* ctx, const og_r1cs* r, const uint8_t* data, size_t len, std::vector<uint8_t>& pk, std::vector<uint8_t>& vk) {
-  const std::string who = "og_setup_ptau";
-  BinFile bf;
-  PtauHeader hd;
-  OG_TRY(ptau_parse(data, len, who, &bf, &hd));
+// sections 2..6 are present and have the lengths the header's power asks for
+static int ptau_sections(BinFile& bf, const PtauHeader& hd, const std::string& who) {
   const uint64_t np = 1ull << hd.power;
   const uint64_t want[7] = {0, 0, (2 * np - 1) * 64, np * 128, np * 64, np * 64, 128};
   for (uint32_t id = 2; id <= 6; id++) {
@@ -241,6 +290,16 @@ int ptau_setup(og_ctx* ctx, const og_r1cs* r, const uint8_t* data, size_t len, s
     OG_REQUIRE(bf.sec[id].second == want[id], who + ": " + PTAU_SEC[id] + " has " + std::to_string(bf.sec[id].second) + " bytes, power " +
                                                   std::to_string(hd.power) + " asks for " + std::to_string(want[id]));
   }
+  return OG_OK;
+}
+
+// who: the entry point the reasons name (og_setup_ptau, or og_pk_verify rebuilding the delta = 1 key)
+int ptau_setup(og_ctx* ctx, const og_r1cs* r, const uint8_t* data, size_t len, std::vector<uint8_t>& pk, std::vector<uint8_t>& vk,
+               const std::string& who = "og_setup_ptau") {
+  BinFile bf;
+  PtauHeader hd;
+  OG_TRY(ptau_parse(data, len, who, &bf, &hd));
+  OG_TRY(ptau_sections(bf, hd, who));
   QapRows rows;
   OG_TRY(r1cs_qap_rows(r, who, &rows));
   const size_t m = r->n_wires, l = r->n_pub, n_rows = r->n_constraints + l + 1;
@@ -410,6 +469,304 @@ int pk_contribute(og_ctx* ctx, const uint8_t* pkb, size_t pk_len, const uint8_t*
   return OG_OK;
 }
 
+// ---- the two checks ---------------------------------------------------------------------------------------------------------
+// og_ptau_verify: every section of the file is a geometric sequence with the ratio tauG2[1] carries (`snarkjs powersoftau
+// verify` without the contribution transcripts); og_pk_verify: a key is og_setup_ptau's key for this circuit and this file up
+// to its delta (`snarkjs zkey verify`, likewise).  Both are linear in the points: per section one vector of challenge scalars
+// rho, ONE digit sort of it, and an msm_run per sum over plain bases -- the section from point 0 and from point 1, or a key's
+// query and the rebuilt key's -- then one two-pairing product per check on the host.  The library draws no randomness: the
+// scalars are Fiat-Shamir, MiMC7 of a seed that is the Keccak-256 of every input byte and of the (section, index) pair,
+// truncated to 128 bits; a section that is not what it should be satisfies one linear relation in uniformly drawn rho, which
+// happens with probability about 2^-128.  Every check runs; the verdict is a bit mask.
+static const char* const PTAU_CHECK[5] = {"tauG1", "tauG2", "alphaTauG1", "betaTauG1", "betaG2"};
+static const char* const PK_CHECK[6] = {"header", "queries", "ic", "delta", "L", "H"};
+
+static std::string failed_names(uint32_t mask, const char* const* names, int n) {
+  std::string out;
+  for (int k = 0; k < n; k++)
+    if (mask & (1u << k)) out += (out.empty() ? "" : ", ") + std::string(names[k]);
+  return out;
+}
+
+// seed = keccak256(tag | keccak256(part) ...) mod r, canonical
+static void challenge_seed(const char* tag, std::initializer_list<std::pair<const uint8_t*, size_t>> parts, uint8_t seed[32]) {
+  std::vector<uint8_t> pre(tag, tag + strlen(tag));
+  uint8_t h[32];
+  for (const auto& p : parts) {
+    keccak256(p.first, p.second, h);
+    pre.insert(pre.end(), h, h + 32);
+  }
+  keccak256(pre.data(), pre.size(), h);
+  zfr_store(seed, fe_from_mont(fe_to_mont(zfr_load(h))));  // (any 256-bit value goes in, its residue comes out)
+}
+
+static bool all_zero(const uint8_t* p, size_t n) {
+  for (size_t i = 0; i < n; i++)
+    if (p[i]) return false;
+  return true;
+}
+static bool any_infinity(const uint8_t* pts, size_t n, size_t pb) {
+  for (size_t i = 0; i < n; i++)
+    if (all_zero(pts + i * pb, pb)) return true;
+  return false;
+}
+
+// f <- f * (the Miller value of e(+-p, q)); canonical affine bytes of points on their curves, q in the subgroup.  A point at
+// infinity pairs to one.  false: the loop met a vertical line, which points of order r never give.
+static bool miller_factor(const uint8_t* p64, const uint8_t* q128, bool neg, Fq12& f) {
+  if (all_zero(p64, 64) || all_zero(q128, 128)) return true;
+  G1A p = {fe_to_mont(ld_any<FqParams>(p64)), fe_to_mont(ld_any<FqParams>(p64 + 32))};
+  if (neg) p.y = fe_neg(p.y);
+  const G2A q = {fq2_from_bytes(q128), fq2_from_bytes(q128 + 64)};
+  Fq12 m;
+  if (!miller_loop(p, q, m)) return false;
+  f = f12_mul(f, m);
+  return true;
+}
+// e(a1, b1) == e(a2, b2): one product of two Miller values, the second with its G1 side negated, one final exponentiation
+static bool pairing_eq(const uint8_t* a1, const uint8_t* b1, const uint8_t* a2, const uint8_t* b2) {
+  Fq12 f = f12_one();
+  if (!miller_factor(a1, b1, false, f) || !miller_factor(a2, b2, true, f)) return false;
+  return f12_is_one(final_exponentiation(f));
+}
+
+// out[k] = sum over i < n of rho_i . bases_d[k][i], k < nb: canonical affine bytes on the host.  rho = the challenge scalars
+// of (seed, section); every sum takes the SAME vector through the SAME digit sort.  bases_d[k]: n affine Montgomery points of
+// one group on the device, used where they lie -- plain bases, no window tables for sums that run once.
+static int challenge_sums(og_ctx* ctx, const uint8_t* seed_d, uint32_t section, bool g2, size_t n, const uint8_t* const* bases_d, int nb, uint8_t* out) {
+  const size_t pb = g2 ? 128 : 64;
+  memset(out, 0, (size_t)nb * pb);
+  if (n == 0) return OG_OK;
+  ZDev dev;
+  uint8_t *rho_d, *res_d, *aff_d;
+  OG_TRY(dev.get(n * 32, &rho_d));
+  OG_TRY(dev.get((size_t)nb * 2 * pb, &res_d));
+  OG_TRY(dev.get((size_t)nb * pb, &aff_d));
+  hipLaunchKernelGGL(k_challenge_scalars, dim3(grid_for(n, 128)), dim3(128), 0, ctx->stream, (const uint32_t*)ctx->mimc_consts_d, seed_d, section, n, rho_d);
+  OG_HIP(hipGetLastError());
+  const int c = (int)msm_pick_c(n);
+  DigitSort ds;
+  OG_TRY(msm_digit_sort(ctx, 0, rho_d, n * 32, n, nullptr, 1, c, 0, &ds));
+  for (int k = 0; k < nb; k++) {
+    og_bases b;
+    b.is_g2 = g2 ? 1 : 0; b.n = n; b.c = c; b.nwin = msm_nwin(c); b.precomp = 0; b.device = ctx->device;
+    b.tab_d = const_cast<uint8_t*>(bases_d[k]);
+    OG_TRY(msm_run(ctx, &b, ds, res_d + (size_t)k * 2 * pb));
+  }
+  OG_TRY(xyzz_to_affine_bytes(ctx, g2 ? 1 : 0, res_d, aff_d, (size_t)nb));
+  OG_HIP(hipMemcpyAsync(out, aff_d, (size_t)nb * pb, hipMemcpyDeviceToHost, ctx->stream));
+  OG_HIP(hipStreamSynchronize(ctx->stream));
+  return OG_OK;
+}
+
+static int ctx_is_idle(og_ctx* ctx, const std::string& who) {
+  // (the sums' scratch -- the digit sort, the bucket sets -- is also the scratch of a submitted prove call)
+  OG_REQUIRE(ctx->jobs[0] == nullptr && ctx->jobs[1] == nullptr, who + ": a submitted prove call has not been waited for (og_job_wait) -- its scratch is in use");
+  return OG_OK;
+}
+
+int ptau_verify(og_ctx* ctx, const uint8_t* data, size_t len, uint32_t* failed_out) {
+  const std::string who = "og_ptau_verify";
+  BinFile bf;
+  PtauHeader hd;
+  OG_TRY(ptau_parse(data, len, who, &bf, &hd));
+  OG_TRY(ptau_sections(bf, hd, who));
+  uint8_t seed[32];
+  challenge_seed("owshen_gpu og_ptau_verify 1", {{data, len}}, seed);
+
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  OG_TRY(ctx_is_idle(ctx, who));
+  OG_HIP(hipSetDevice(ctx->device));
+  ctx->lane = 0;
+  ctx->stream = ctx->lanes[0];
+  ZDev keep;
+  uint8_t* seed_d;
+  OG_TRY(keep.get(32, &seed_d));
+  OG_HIP(hipMemcpyAsync(seed_d, seed, 32, hipMemcpyHostToDevice, ctx->stream));
+  const size_t np = (size_t)1 << hd.power;
+  // a section at a time (its decoded copies go back before the next one comes): tauG2 first, whose second point is the ratio
+  // three other checks are made against
+  const struct { int id; bool g2; size_t n; } secs[4] = {{3, true, np}, {2, false, 2 * np - 1}, {4, false, np}, {5, false, np}};
+  uint8_t sums[6][2][128] = {}, second[6][128] = {}, beta1_0[64], beta2[128];
+  bool has_inf[7] = {};
+  for (const auto& sc : secs) {
+    const size_t pb = sc.g2 ? 128 : 64;
+    ZDev dev;
+    std::vector<uint8_t> canon;
+    uint8_t* mont_d;
+    OG_TRY(ptau_decode(ctx, dev, bf, sc.id, sc.g2, sc.n, sc.n, canon, &mont_d, who));
+    if (sc.id == 2) OG_REQUIRE(memcmp(canon.data(), G1_GEN_BYTES, 64) == 0, who + ": " + PTAU_SEC[2] + ": the first point is not the G1 generator");
+    if (sc.id == 3) {
+      OG_REQUIRE(memcmp(canon.data(), G2_GEN_BYTES, 128) == 0, who + ": " + PTAU_SEC[3] + ": the first point is not the G2 generator");
+      OG_TRY(g2_subgroup_check(ctx, dev, mont_d, sc.n, who + ": " + PTAU_SEC[3]));
+    }
+    has_inf[sc.id] = any_infinity(canon.data(), sc.n, pb);
+    if (sc.n > 1) memcpy(second[sc.id], canon.data() + pb, pb);
+    if (sc.id == 5) memcpy(beta1_0, canon.data(), 64);
+    const uint8_t* bases[2] = {mont_d, mont_d + pb};  // S0 over points 0 .. n - 2, S1 over points 1 .. n - 1
+    OG_TRY(challenge_sums(ctx, seed_d, (uint32_t)sc.id, sc.g2, sc.n - 1, bases, 2, &sums[sc.id][0][0]));
+    if (!sc.g2) memcpy(sums[sc.id][1], &sums[sc.id][0][64], 64);  // (challenge_sums packs its results: G1 points are 64 B apart)
+  }
+  {
+    ZDev dev;
+    std::vector<uint8_t> canon;
+    uint8_t* mont_d;
+    OG_TRY(ptau_decode(ctx, dev, bf, 6, true, 1, 1, canon, &mont_d, who));
+    OG_TRY(g2_subgroup_check(ctx, dev, mont_d, 1, who + ": " + PTAU_SEC[6]));
+    memcpy(beta2, canon.data(), 128);
+  }
+  uint32_t mask = 0;
+  const uint8_t* tau2_1 = second[3];
+  for (int id : {2, 4, 5})  // e(S1, G2) = e(S0, tau G2)
+    if (has_inf[id] || !pairing_eq(sums[id][1], G2_GEN_BYTES, sums[id][0], tau2_1)) mask |= id == 2 ? 1u : id == 4 ? 4u : 8u;
+  if (has_inf[3] || !pairing_eq(second[2], sums[3][0], G1_GEN_BYTES, sums[3][1])) mask |= 2u;  // e(tau G1, S0) = e(G1, S1)
+  if (all_zero(beta2, 128) || all_zero(beta1_0, 64) || !pairing_eq(beta1_0, G2_GEN_BYTES, G1_GEN_BYTES, beta2)) mask |= 16u;
+  *failed_out = mask;
+  if (mask) set_error(who + ": failed checks: " + failed_names(mask, PTAU_CHECK, 5));
+  return OG_OK;
+}
+
+// n canonical affine points on the host -> affine Montgomery on the device; *flags: 1 a coordinate >= q, 2 a point off the curve
+template <class T>
+static int canon_to_mont(og_ctx* ctx, ZDev& dev, const uint8_t* in, size_t n, uint8_t** mont_d, uint32_t* flags) {
+  constexpr size_t pb = Affine<T>::BYTES;
+  uint8_t *in_d, *c_d, *f_d;
+  OG_TRY(dev.get(n * pb, &in_d));
+  OG_TRY(dev.get(n * pb, mont_d));
+  OG_TRY(dev.get(96, &c_d));
+  OG_TRY(dev.get(4, &f_d));
+  alignas(16) uint8_t consts[96];
+  lem_consts(pb == 128, false, consts);
+  OG_HIP(hipMemcpyAsync(in_d, in, n * pb, hipMemcpyHostToDevice, ctx->stream));
+  OG_HIP(hipMemcpyAsync(c_d, consts, 96, hipMemcpyHostToDevice, ctx->stream));
+  OG_HIP(hipMemsetAsync(f_d, 0, 4, ctx->stream));
+  hipLaunchKernelGGL(k_canon_to_mont<T>, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, in_d, n, c_d + 32, *mont_d, (uint32_t*)f_d);
+  OG_HIP(hipGetLastError());
+  OG_HIP(hipMemcpyAsync(flags, f_d, 4, hipMemcpyDeviceToHost, ctx->stream));
+  OG_HIP(hipStreamSynchronize(ctx->stream));
+  return OG_OK;
+}
+
+// where the parts of an OWPK0001 blob lie, by its own header; false: the header is out of range or disagrees with the length
+struct PkLayout {
+  size_t m, l, power, n_rows, nnz[3];
+  size_t mat[3][3];  // ptr | col | val of A, B, C
+  size_t a_off, l_off, h_off;
+};
+static bool pk_layout(const uint8_t* pk, size_t len, PkLayout* out) {
+  if (len < 80 + 512) return false;
+  uint64_t hd[10];
+  memcpy(hd, pk, 80);
+  if (!(hd[3] >= 1 && hd[3] <= 28 && hd[1] >= 1 && hd[2] < hd[1] && hd[1] < (1ull << 31) && hd[4] <= (1ull << hd[3]))) return false;
+  out->m = hd[1]; out->l = hd[2]; out->power = hd[3]; out->n_rows = hd[4];
+  size_t off = 80 + 512;
+  for (int k = 0; k < 3; k++) {
+    if (hd[5 + k] >= (1ull << 32)) return false;
+    out->nnz[k] = hd[5 + k];
+    out->mat[k][0] = off;
+    out->mat[k][1] = off += zpad32((out->n_rows + 1) * 4);
+    out->mat[k][2] = off += zpad32(out->nnz[k] * 4);
+    off += zpad32(out->nnz[k] * 32);
+    if (off > len) return false;
+  }
+  out->a_off = off;
+  out->l_off = off + 2 * zpad32(out->m * 64) + zpad32(out->m * 128);
+  out->h_off = out->l_off + zpad32((out->m - out->l - 1) * 64);
+  return out->h_off + zpad32((((size_t)1 << out->power) - 1) * 64) == len;
+}
+
+int pk_verify(og_ctx* ctx, const og_r1cs* r, const uint8_t* data, size_t len, const uint8_t* pkb, size_t pk_len, const uint8_t* vkb, size_t vk_len,
+              uint32_t* failed_out) {
+  const std::string who = "og_pk_verify";
+  OG_REQUIRE(pk_len >= 80 + 512 && rd64(pkb) == 0x313030304b50574full, who + ": not an OWPK0001 blob");
+  OG_REQUIRE(vk_len >= 16 + 64 + 3 * 128 && memcmp(vkb, "OWVK0001", 8) == 0, who + ": not an OWVK0001 blob");
+  OG_REQUIRE(rd64(pkb + 64) == 0, who + ": the key carries header flag " + std::to_string(rd64(pkb + 64)) +
+                                      " (imported without its .r1cs: no C matrix) -- import it beside its .r1cs (og_zkey_import with r1cs) and verify that key");
+  {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    OG_TRY(ctx_is_idle(ctx, who));
+  }
+  std::vector<uint8_t> pk0, vk0;  // the delta = 1 key of this circuit and this file
+  OG_TRY(ptau_setup(ctx, r, data, len, pk0, vk0, who));
+  uint8_t seed[32];
+  challenge_seed("owshen_gpu og_pk_verify 1", {{data, len}, {pkb, pk_len}, {vkb, vk_len}}, seed);
+  PkLayout lay, lay0;
+  OG_REQUIRE(pk_layout(pk0.data(), pk0.size(), &lay0), who + ": internal: the rebuilt key does not parse");
+  if (!pk_layout(pkb, pk_len, &lay) || lay.m != lay0.m || lay.l != lay0.l || lay.power != lay0.power || memcmp(lay.nnz, lay0.nnz, sizeof lay.nnz) != 0 ||
+      vk_len != vk0.size()) {
+    *failed_out = 63u;  // another shape: no query of this key is the size of the circuit's, nothing else has anything to be compared with
+    set_error(who + ": failed checks: " + failed_names(63u, PK_CHECK, 6) + " (the key's header or length is not this circuit's: nothing else can be compared)");
+    return OG_OK;
+  }
+  const size_t m = lay0.m, nl = m - lay0.l - 1, nh = ((size_t)1 << lay0.power) - 1;
+  const size_t vk_fixed = 16 + 64 + 2 * 128, ic_off = vk_fixed + 128;  // magic, n_pub, alpha, beta, gamma | delta | IC
+  uint32_t mask = 0;
+  // the matrices row for row; a key that went through a .zkey counts its rows up to the domain: the rows it adds must be empty
+  bool mats = lay.n_rows >= lay0.n_rows;
+  for (int k = 0; k < 3 && mats; k++) {
+    const uint8_t *pt = pkb + lay.mat[k][0], *pt0 = &pk0[lay0.mat[k][0]];
+    mats = memcmp(pt, pt0, (lay0.n_rows + 1) * 4) == 0 && memcmp(pkb + lay.mat[k][1], &pk0[lay0.mat[k][1]], lay0.nnz[k] * 4) == 0 &&
+           memcmp(pkb + lay.mat[k][2], &pk0[lay0.mat[k][2]], lay0.nnz[k] * 32) == 0;
+    for (size_t i = lay0.n_rows + 1; i <= lay.n_rows && mats; i++) mats = rd32(pt + i * 4) == lay0.nnz[k];
+  }
+  if (!mats || rd64(pkb + 72) != 0 || memcmp(pkb + 80, &pk0[80], 128) != 0 || memcmp(pkb + 80 + 256, &pk0[80 + 256], 128) != 0 ||
+      memcmp(vkb, vk0.data(), vk_fixed) != 0)
+    mask |= 1u;
+  if (memcmp(pkb + lay.a_off, &pk0[lay0.a_off], lay0.l_off - lay0.a_off) != 0) mask |= 2u;
+  if (memcmp(vkb + ic_off, &vk0[ic_off], vk_len - ic_off) != 0) mask |= 4u;
+
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  OG_TRY(ctx_is_idle(ctx, who));
+  OG_HIP(hipSetDevice(ctx->device));
+  ctx->lane = 0;
+  ctx->stream = ctx->lanes[0];
+  ZDev keep;
+  uint8_t* seed_d;
+  OG_TRY(keep.get(32, &seed_d));
+  OG_HIP(hipMemcpyAsync(seed_d, seed, 32, hipMemcpyHostToDevice, ctx->stream));
+  // ---- delta
+  const uint8_t *d1 = pkb + 80 + 128, *d2 = pkb + 80 + 384;
+  bool d1_ok = !all_zero(d1, 64), d2_ok = !all_zero(d2, 128);
+  {
+    ZDev dev;
+    uint8_t *d1_m, *d2_m;
+    uint32_t f1 = 0, f2 = 0;
+    OG_TRY(canon_to_mont<Fq>(ctx, dev, d1, 1, &d1_m, &f1));
+    OG_TRY(canon_to_mont<Fq2>(ctx, dev, d2, 1, &d2_m, &f2));
+    d1_ok = d1_ok && f1 == 0;
+    d2_ok = d2_ok && f2 == 0;
+    if (d2_ok) {
+      bool outside = false;
+      OG_TRY(g2_subgroup_flags(ctx, dev, d2_m, 1, &outside));
+      d2_ok = !outside;
+    }
+  }
+  if (!d1_ok || !d2_ok || memcmp(d2, vkb + vk_fixed, 128) != 0 || !pairing_eq(d1, G2_GEN_BYTES, G1_GEN_BYTES, d2)) mask |= 8u;
+  if (!d2_ok) mask |= 16u | 32u;  // nothing to check L and H against
+  // ---- L and H: e(sum rho_i Q_i, delta2) = e(sum rho_i Q0_i, G2), Q0 the delta = 1 key's query
+  const struct { size_t off, off0, n; uint32_t bit; } qs[2] = {{lay.l_off, lay0.l_off, nl, 16u}, {lay.h_off, lay0.h_off, nh, 32u}};
+  for (const auto& q : qs) {
+    if (!d2_ok || q.n == 0) continue;
+    ZDev dev;
+    uint8_t *q_m, *q0_m;
+    uint32_t f = 0, f0 = 0;
+    OG_TRY(canon_to_mont<Fq>(ctx, dev, pkb + q.off, q.n, &q_m, &f));
+    OG_TRY(canon_to_mont<Fq>(ctx, dev, &pk0[q.off0], q.n, &q0_m, &f0));
+    OG_REQUIRE(f0 == 0, who + ": internal: the rebuilt key holds a point off the curve");
+    if (f) {  // an entry that is not canonical or not on the curve
+      mask |= q.bit;
+      continue;
+    }
+    const uint8_t* bases[2] = {q_m, q0_m};
+    uint8_t s[2][64];
+    OG_TRY(challenge_sums(ctx, seed_d, q.bit, false, q.n, bases, 2, &s[0][0]));
+    if (!pairing_eq(s[0], d2, s[1], G2_GEN_BYTES)) mask |= q.bit;
+  }
+  *failed_out = mask;
+  if (mask) set_error(who + ": failed checks: " + failed_names(mask, PK_CHECK, 6));
+  return OG_OK;
+}
+
 }  // namespace og
 
 using namespace og;
@@ -465,6 +822,23 @@ int og_pk_contribute(og_ctx* ctx, const uint8_t* pk, size_t pk_len, const uint8_
     std::vector<uint8_t> npk, nvk;
     OG_TRY(pk_contribute(ctx, pk, pk_len, vk, vk_len, d, npk, nvk));
     return two_blobs_out(npk, nvk, pk_out, pk_out_len, vk_out, vk_out_len, "og_pk_contribute");
+  });
+}
+
+int og_ptau_verify(og_ctx* ctx, const uint8_t* ptau, size_t len, uint32_t* failed_out) {
+  return guarded([&]() -> int {
+    OG_REQUIRE(ctx && ptau && failed_out, "og_ptau_verify: null argument");
+    *failed_out = 0;
+    return ptau_verify(ctx, ptau, len, failed_out);
+  });
+}
+
+int og_pk_verify(og_ctx* ctx, const og_r1cs* r1cs, const uint8_t* ptau, size_t len, const uint8_t* pk, size_t pk_len, const uint8_t* vk, size_t vk_len,
+                 uint32_t* failed_out) {
+  return guarded([&]() -> int {
+    OG_REQUIRE(ctx && r1cs && ptau && pk && vk && failed_out, "og_pk_verify: null argument");
+    *failed_out = 0;
+    return pk_verify(ctx, r1cs, ptau, len, pk, pk_len, vk, vk_len, failed_out);
   });
 }
 

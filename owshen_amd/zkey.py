@@ -174,6 +174,10 @@ def main(argv=None, ctx=None):
     p = sub.add_parser("setup", help="`snarkjs groth16 setup` on the GPU: .r1cs + .ptau -> .zkey (gamma = delta = 1, or delta = --delta)")
     p.add_argument("r1cs"), p.add_argument("ptau"), p.add_argument("zkey_out")
     p.add_argument("--delta", metavar="HEX", help="one contribution: the scalar delta (hex, 0 < delta < r); yours to draw and to forget")
+    p = sub.add_parser("verify", help="`snarkjs zkey verify` on the GPU: is the .zkey this circuit's key from this .ptau, up to its delta? exit status 0 = yes")
+    p.add_argument("r1cs"), p.add_argument("ptau"), p.add_argument("zkey")
+    p = sub.add_parser("ptau-verify", help="`snarkjs powersoftau verify` on the GPU (without the contribution transcripts): exit status 0 = a valid ceremony")
+    p.add_argument("ptau")
     p = sub.add_parser("wtns2bin", help=".wtns -> n x 32 B little-endian values")
     p.add_argument("wtns"), p.add_argument("out")
     p = sub.add_parser("bin2wtns", help="n x 32 B little-endian values -> .wtns")
@@ -207,6 +211,15 @@ def main(argv=None, ctx=None):
             if a.delta is not None:
                 pk, vk = ptau.contribute(ctx, pk, vk, int(a.delta, 16))
             wr(a.zkey_out, export_zkey(ctx, pk, vk))
+        elif a.cmd in ("verify", "ptau-verify"):
+            from . import ptau
+            if a.cmd == "verify":
+                pk, vk = import_zkey(ctx, rd(a.zkey), rd(a.r1cs))
+                failed = ptau.verify_key(ctx, read_r1cs(rd(a.r1cs), lib=ctx._lib), rd(a.ptau), pk, vk)
+            else:
+                failed = ptau.verify(ctx, rd(a.ptau))
+            print("ok" if not failed else "FAILED: " + ", ".join(failed))
+            return 1 if failed else 0
         else:
             from . import snarkjs_json
             proof, pub, vk = prove_files(ctx, rd(a.zkey), rd(a.wtns), r1cs_bytes=rd(a.r1cs) if a.r1cs else None)
@@ -218,4 +231,4 @@ def main(argv=None, ctx=None):
 
 
 if __name__ == "__main__":
-    main()
+    raise SystemExit(main())
