@@ -35,6 +35,7 @@ int h_poly_canonical(og_ctx*, const uint8_t*, const uint8_t*, const uint8_t*, in
 
 int pk_load(og_ctx*, const uint8_t*, size_t, og_pk**);
 void pk_destroy(og_pk*);
+void pk_info(const og_pk*, uint64_t*);
 void pk_density(const og_pk*, uint64_t*);
 void pk_windows(const og_pk*, uint64_t*);
 uint64_t pk_bytes(const og_pk*);
@@ -74,11 +75,6 @@ void vk_info(const og_vk*, uint64_t*);
 int verify_batch(og_ctx*, const og_vk*, const uint8_t*, const uint8_t*, size_t, uint32_t*);
 
 }  // namespace og
-
-// mirrors the head of the definition in groth16.hip (og_pk_info reads only these fields)
-struct og_pk_head {
-  uint64_t m, n_pub, log_d, n_rows;
-};
 
 using namespace og;
 
@@ -510,8 +506,7 @@ void og_pk_free(og_pk* pk) { pk_destroy(pk); }
 int og_pk_info(const og_pk* pk, uint64_t info[4]) {
   return guarded([&]() -> int {
     OG_REQUIRE(pk != nullptr && info != nullptr, "og_pk_info: null argument");
-    const og_pk_head* h = reinterpret_cast<const og_pk_head*>(pk);
-    info[0] = h->m; info[1] = h->n_pub; info[2] = h->log_d; info[3] = h->n_rows;
+    pk_info(pk, info);
     return OG_OK;
   });
 }

@@ -24,6 +24,7 @@
 #include "field.hip.h"
 #include "glv.h"
 #include "ec.hip.h"
+#include "key_blob.h"
 #include <string.h>
 #include <algorithm>
 #include <iterator>
@@ -253,18 +254,7 @@ int scalar_mul_fixed(og_ctx* ctx, int is_g2, const uint8_t* base_host, const uin
 }
 
 // ---- proving key -----------------------------------------------------------------------
-// Serialized key ("OWPK0001"), all little-endian, every section padded to a multiple of 32 B:
-//   u64 x 10 : magic, n_wires, n_pub, log_d, n_rows, nnz_a, nnz_b, nnz_c, flags, 0
-//              flags bit 0: the key carries no C matrix (nnz_c = 0) and the prover takes C z = (A z) o (B z) row by row -- what
-//              snarkjs' prover does, whose .zkey stores A and B only (og_zkey_import); such a key cannot tell a witness that
-//              violates a constraint (the proof simply does not verify), only wire 0 != 1
-//   alpha_g1 (64) beta_g1 (64) delta_g1 (64) pad (64) | beta_g2 (128) delta_g2 (128)
-//   for M in A, B, C: ptr (n_rows+1 u32) | col (nnz u32) | val (nnz x 32 B canonical)
-//   a_query (m x 64) | b_g1_query (m x 64) | b_g2_query (m x 128) | l_query ((m-n_pub-1) x 64) | h_query ((d-1) x 64)
-static const uint64_t PK_MAGIC = 0x313030304b50574full;  // "OWPK0001"
-
-static inline size_t pad32(size_t n) { return (n + 31) / 32 * 32; }
-
+// The serialized key: key_blob.h.
 void pk_destroy(og_pk* pk) {
   if (!pk) return;
   (void)hipSetDevice(pk->device);
@@ -285,59 +275,28 @@ void pk_destroy(og_pk* pk) {
 }
 
 static int pk_load_impl(og_ctx* ctx, const uint8_t* blob, size_t len, og_pk* pk) {
-  OG_REQUIRE(len >= 80 + 256 + 256, "og_pk_load: blob too short");
-  uint64_t hd[10];
-  memcpy(hd, blob, 80);
-  OG_REQUIRE(hd[0] == PK_MAGIC, "og_pk_load: bad magic (want OWPK0001)");
-  pk->m = hd[1]; pk->n_pub = hd[2]; pk->log_d = hd[3]; pk->n_rows = hd[4];
-  pk->nnz[0] = hd[5]; pk->nnz[1] = hd[6]; pk->nnz[2] = hd[7];
-  OG_REQUIRE(hd[8] <= 1 && hd[9] == 0, "og_pk_load: unknown header flags");
-  pk->c_is_ab = (hd[8] & 1) != 0;
-  OG_REQUIRE(!pk->c_is_ab || pk->nnz[2] == 0, "og_pk_load: a key with the C = A o B flag carries no C matrix");
-  OG_REQUIRE(pk->log_d >= 1 && pk->log_d <= 28, "og_pk_load: log_d must be 1..28");
-  pk->d = (size_t)1 << pk->log_d;
-  OG_REQUIRE(pk->m >= 1 && pk->m < (1ull << 31) && pk->n_pub < pk->m, "og_pk_load: bad wire counts");
-  OG_REQUIRE(pk->n_rows <= pk->d, "og_pk_load: more QAP rows than the domain holds");
-  for (int k = 0; k < 3; k++) OG_REQUIRE(pk->nnz[k] < (1ull << 32), "og_pk_load: nnz too large");
-  const size_t m = pk->m, nl = m - pk->n_pub - 1, nh = pk->d - 1;
-  size_t off = 80;
-  const uint8_t* c1 = blob + off; off += 256;
-  const uint8_t* c2 = blob + off; off += 256;
-  const uint8_t *ptr_h[3], *col_h[3], *val_h[3];
-  for (int k = 0; k < 3; k++) {
-    ptr_h[k] = blob + off; off += pad32((pk->n_rows + 1) * 4);
-    col_h[k] = blob + off; off += pad32(pk->nnz[k] * 4);
-    val_h[k] = blob + off; off += pad32(pk->nnz[k] * 32);
-    OG_REQUIRE(off <= len, "og_pk_load: truncated R1CS section");
-  }
-  const uint8_t* q_h[5];
-  const size_t q_n[5] = {m, m, m, nl, nh};
-  const size_t q_pb[5] = {64, 64, 128, 64, 64};
-  for (int k = 0; k < 5; k++) {
-    q_h[k] = blob + off;
-    off += pad32(q_n[k] * q_pb[k]);
-  }
-  OG_REQUIRE(off == len, "og_pk_load: blob length does not match its header");
-  // validate the CSR on the host (cheap, and a malformed key must never index out of bounds on the GPU)
-  for (int k = 0; k < 3; k++) {
-    const uint32_t* p = (const uint32_t*)ptr_h[k];
-    const uint32_t* c = (const uint32_t*)col_h[k];
-    OG_REQUIRE(p[0] == 0 && p[pk->n_rows] == pk->nnz[k], "og_pk_load: CSR row pointers inconsistent");
-    for (size_t r = 0; r < pk->n_rows; r++) OG_REQUIRE(p[r] <= p[r + 1], "og_pk_load: CSR row pointers not monotone");
-    for (size_t i = 0; i < pk->nnz[k]; i++) OG_REQUIRE(c[i] < m, "og_pk_load: CSR column out of range");
-  }
+  const std::string who = "og_pk_load";
+  PkView v;
+  OG_TRY(pk_view(blob, len, who, &v));
+  OG_REQUIRE(v.flags <= 1 && v.word9 == 0, who + ": unknown header flags");
+  OG_REQUIRE(!(v.flags & 1) || v.nnz[2] == 0, who + ": a key with the C = A o B flag carries no C matrix");
+  OG_TRY(pk_csr_check(v, 3, who));  // (cheap, and a malformed key must never index out of bounds on the GPU)
+  pk->m = v.m; pk->n_pub = v.l; pk->log_d = v.log_d; pk->n_rows = v.n_rows; pk->d = v.d;
+  for (int k = 0; k < 3; k++) pk->nnz[k] = v.nnz[k];
+  pk->c_is_ab = (v.flags & 1) != 0;
+  const size_t m = pk->m, nl = v.nl, nh = v.nh;
+  const uint8_t *c1 = blob + PK_CONSTS1, *c2 = blob + PK_CONSTS2;
   for (int k = 0; k < 3; k++) {
     OG_HIP(hipMalloc((void**)&pk->ptr[k], (pk->n_rows + 1) * 4));
     OG_HIP(hipMalloc((void**)&pk->col[k], pk->nnz[k] * 4 + 4));
     OG_HIP(hipMalloc((void**)&pk->val[k], pk->nnz[k] * 32 + 32));
-    OG_HIP(hipMemcpyAsync(pk->ptr[k], ptr_h[k], (pk->n_rows + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-    OG_HIP(hipMemcpyAsync(pk->col[k], col_h[k], pk->nnz[k] * 4, hipMemcpyHostToDevice, ctx->stream));
-    OG_HIP(hipMemcpyAsync(pk->val[k], val_h[k], pk->nnz[k] * 32, hipMemcpyHostToDevice, ctx->stream));
+    OG_HIP(hipMemcpyAsync(pk->ptr[k], v.ptr[k], (pk->n_rows + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+    OG_HIP(hipMemcpyAsync(pk->col[k], v.col[k], pk->nnz[k] * 4, hipMemcpyHostToDevice, ctx->stream));
+    OG_HIP(hipMemcpyAsync(pk->val[k], v.val[k], pk->nnz[k] * 32, hipMemcpyHostToDevice, ctx->stream));
     {
       std::vector<uint32_t> lr;
-      const uint32_t* p = (const uint32_t*)ptr_h[k];
       for (size_t r = 0; r < pk->n_rows; r++)
-        if (p[r + 1] - p[r] > SPMV_LONG) lr.push_back((uint32_t)r);
+        if (rd32(v.ptr[k] + (r + 1) * 4) - rd32(v.ptr[k] + r * 4) > SPMV_LONG) lr.push_back((uint32_t)r);
       pk->n_long[k] = (uint32_t)lr.size();
       if (!lr.empty()) {
         OG_HIP(hipMalloc((void**)&pk->long_rows[k], lr.size() * 4));
@@ -373,18 +332,13 @@ static int pk_load_impl(og_ctx* ctx, const uint8_t* blob, size_t len, og_pk* pk)
   // polynomial is zero at tau: the wire never occurs in that matrix) contributes nothing; drop it from the
   // table and from the digit sort.  B1 / B2 are the same polynomial in two groups, so they share one map.
   int ch = (int)msm_pick_query_c(nh);
-  auto is_inf = [](const uint8_t* p, size_t nb) {
-    for (size_t i = 0; i < nb; i++)
-      if (p[i]) return false;
-    return true;
-  };
   std::vector<uint32_t> wire[3];
   for (size_t i = 0; i < m; i++) {
-    if (!is_inf(q_h[0] + i * 64, 64)) wire[0].push_back((uint32_t)i);
-    if (!is_inf(q_h[1] + i * 64, 64) || !is_inf(q_h[2] + i * 128, 128)) wire[1].push_back((uint32_t)i);
+    if (!all_zero(v.query[0] + i * 64, 64)) wire[0].push_back((uint32_t)i);
+    if (!all_zero(v.query[1] + i * 64, 64) || !all_zero(v.query[2] + i * 128, 128)) wire[1].push_back((uint32_t)i);
   }
   for (size_t i = 0; i < nl; i++)
-    if (!is_inf(q_h[3] + i * 64, 64)) wire[2].push_back((uint32_t)(i + pk->n_pub + 1));
+    if (!all_zero(v.query[3] + i * 64, 64)) wire[2].push_back((uint32_t)(i + pk->n_pub + 1));
   // Queries whose wire lists coincide up to a few wires share ONE list -- the union; a wire a query does not have keeps its
   // zero bytes in that query's table, the point at infinity, which the accumulation skips -- and with it ONE digit sort per
   // sub-batch in the stage pipeline instead of one each.  The benchmark's dense padding: A and B hold every wire, L all but
@@ -419,7 +373,7 @@ static int pk_load_impl(og_ctx* ctx, const uint8_t* blob, size_t len, og_pk* pk)
     const size_t shift = q.src == 3 ? pk->n_pub + 1 : 0;  // l_query is indexed from wire n_pub + 1
     const size_t q_len = q.src == 3 ? nl : m;
     for (size_t k = 0; k < w.size(); k++) {
-      if (w[k] >= shift && w[k] - shift < q_len) memcpy(host.data() + k * pb, q_h[q.src] + (w[k] - shift) * pb, pb);
+      if (w[k] >= shift && w[k] - shift < q_len) memcpy(host.data() + k * pb, v.query[q.src] + (w[k] - shift) * pb, pb);
       else memset(host.data() + k * pb, 0, pb);  // a wire of the shared list this query has no base for: infinity
     }
     OG_HIP(hipMemcpyAsync(stage, host.data(), w.size() * pb, hipMemcpyHostToDevice, ctx->stream));
@@ -430,7 +384,7 @@ static int pk_load_impl(og_ctx* ctx, const uint8_t* blob, size_t len, og_pk* pk)
   for (size_t k = 0; k < nh; k++) {
     size_t r = 0;
     for (uint64_t bit = 0; bit < pk->log_d; bit++) r |= ((k >> bit) & 1) << (pk->log_d - 1 - bit);
-    memcpy(host.data() + k * 64, q_h[4] + r * 64, 64);
+    memcpy(host.data() + k * 64, v.query[4] + r * 64, 64);
   }
   OG_HIP(hipMemcpyAsync(stage, host.data(), nh * 64, hipMemcpyHostToDevice, ctx->stream));
   // C = sum z_i L_i + sum h_j H_j is ONE multi-scalar multiplication: when the H query can take the L query's window size, the
@@ -445,6 +399,11 @@ static int pk_load_impl(og_ctx* ctx, const uint8_t* blob, size_t len, og_pk* pk)
   }
   OG_TRY(bases_create(ctx, 0, stage, nh, ch, 1, &pk->h));
   return OG_OK;
+}
+
+// out[0..3] = n_wires, n_pub, log_d, n_rows: the key's header
+void pk_info(const og_pk* pk, uint64_t out[4]) {
+  out[0] = pk->m; out[1] = pk->n_pub; out[2] = pk->log_d; out[3] = pk->n_rows;
 }
 
 // out[0..3] = window bits of the A, B (G1 and G2 copies), L and H queries' precomputed tables (msm_pick_query_c)

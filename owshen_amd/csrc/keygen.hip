@@ -11,7 +11,7 @@
 //   og_r1cs_from_csr   any R1CS the caller built
 //   og_setup           Groth16 key generation from (tau, alpha, beta, gamma, delta): Lagrange evaluations, the three
 //                      transposed sparse products, the query scalars and ~3 m + d fixed-base multiplications, all on the
-//                      GPU; returns the "OWPK0001" / "OWVK0001" blobs of include/owshen_gpu.h
+//                      GPU; returns the OWPK0001 / OWVK0001 blobs of include/owshen_gpu.h
 #include "ctx.h"
 #include "msm.hip.h"
 #include "field.hip.h"
@@ -260,13 +260,6 @@ extern const uint8_t G2_GEN_BYTES[128] = {
     0xeb, 0x6d, 0x8c, 0xdb, 0xa5, 0x5e, 0xc8, 0x12, 0x5b, 0x97, 0x22, 0xd1, 0xdc, 0xda, 0xac, 0x55, 0xf3, 0x8e, 0xb3, 0x70, 0x33, 0x31,
     0x4b, 0xbc, 0x95, 0x33, 0x0c, 0x69, 0xad, 0x99, 0x9e, 0xec, 0x75, 0xf0, 0x5f, 0x58, 0xd0, 0x89, 0x06, 0x09};
 
-static inline size_t pad32(size_t n) { return (n + 31) / 32 * 32; }
-static void put_padded(std::vector<uint8_t>& out, const void* p, size_t n) {
-  const uint8_t* b = static_cast<const uint8_t*>(p);
-  out.insert(out.end(), b, b + n);
-  out.resize(out.size() + (pad32(n) - n), 0);  // every section is padded to a multiple of 32 B on its own
-}
-
 struct DevBuf {  // hipMalloc'd scratch released on every exit path
   std::vector<void*> ptrs;
   ~DevBuf() {
@@ -323,37 +316,6 @@ void csr_transpose(const std::vector<uint32_t>& ptr, const std::vector<uint32_t>
       tcol[pos] = (uint32_t)row;
       memcpy(&tval[(size_t)pos * 32], &val[(size_t)e * 32], 32);
     }
-}
-
-// "OWPK0001" and "OWVK0001" (include/owshen_gpu.h) from canonical group elements
-void key_blobs(const KeyParts& k, const QapRows& rows, std::vector<uint8_t>& pk, std::vector<uint8_t>& vk) {
-  pk.clear();
-  const uint64_t head[10] = {0x313030304b50574full, k.m, k.l, (uint64_t)k.log_d, k.n_rows, rows.col[0].size(), rows.col[1].size(), rows.col[2].size(), 0, 0};
-  pk.insert(pk.end(), (const uint8_t*)head, (const uint8_t*)head + 80);  // the 80-byte header is not padded
-  put_padded(pk, k.alpha1, 64);
-  put_padded(pk, k.beta1, 64);
-  put_padded(pk, k.delta1, 64);
-  pk.resize(pk.size() + 64, 0);
-  put_padded(pk, k.beta2, 128);
-  put_padded(pk, k.delta2, 128);
-  for (int q = 0; q < 3; q++) {
-    put_padded(pk, rows.ptr[q].data(), rows.ptr[q].size() * 4);
-    put_padded(pk, rows.col[q].data(), rows.col[q].size() * 4);
-    put_padded(pk, rows.val[q].data(), rows.val[q].size());
-  }
-  const size_t nl = k.m - k.l - 1, nh = ((size_t)1 << k.log_d) - 1;
-  const size_t q_bytes[5] = {k.m * 64, k.m * 64, k.m * 128, nl * 64, nh * 64};
-  for (int q = 0; q < 5; q++) put_padded(pk, k.query[q], q_bytes[q]);
-  // ---- "OWVK0001" | n_pub | alpha_g1 | beta_g2 | gamma_g2 | delta_g2 | IC
-  vk.clear();
-  vk.insert(vk.end(), (const uint8_t*)"OWVK0001", (const uint8_t*)"OWVK0001" + 8);
-  const uint64_t npub = k.l;
-  vk.insert(vk.end(), (const uint8_t*)&npub, (const uint8_t*)&npub + 8);
-  vk.insert(vk.end(), k.alpha1, k.alpha1 + 64);
-  vk.insert(vk.end(), k.beta2, k.beta2 + 128);
-  vk.insert(vk.end(), k.gamma2, k.gamma2 + 128);
-  vk.insert(vk.end(), k.delta2, k.delta2 + 128);
-  vk.insert(vk.end(), k.ic, k.ic + (k.l + 1) * 64);
 }
 
 int keygen_setup(og_ctx* ctx, const og_r1cs* r, const uint8_t toxic[160], std::vector<uint8_t>& pk, std::vector<uint8_t>& vk) {

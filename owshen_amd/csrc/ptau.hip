@@ -29,6 +29,7 @@
 #include "ec.hip.h"
 #include "snarkfile.hip.h"
 #include "keygen.h"
+#include "key_blob.h"
 #include "mimc7.hip.h"
 #include "msm.hip.h"
 #include "verify_tower.h"
@@ -397,23 +398,10 @@ int ptau_setup(og_ctx* ctx, const og_r1cs* r, const uint8_t* data, size_t len, s
 template <class T>
 static int smul_uniform(og_ctx* ctx, ZDev& dev, const uint8_t* in, size_t n, const K256& k, uint8_t* out, const std::string& who) {
   if (n == 0) return OG_OK;
-  constexpr size_t pb = Affine<T>::BYTES;
-  uint8_t *in_d, *out_d, *c_d, *f_d;
-  OG_TRY(dev.get(n * pb, &in_d));
-  OG_TRY(dev.get(n * pb, &out_d));
-  OG_TRY(dev.get(96, &c_d));
-  OG_TRY(dev.get(4, &f_d));
-  alignas(16) uint8_t consts[96];
-  lem_consts(pb == 128, false, consts);
-  OG_HIP(hipMemcpyAsync(in_d, in, n * pb, hipMemcpyHostToDevice, ctx->stream));
-  OG_HIP(hipMemcpyAsync(c_d, consts, 96, hipMemcpyHostToDevice, ctx->stream));
-  OG_HIP(hipMemsetAsync(f_d, 0, 4, ctx->stream));
-  hipLaunchKernelGGL(k_smul_uniform<T>, dim3(grid_for(n, 64)), dim3(64), 0, ctx->stream, in_d, n, k, c_d + 32, out_d, (uint32_t*)f_d);
-  OG_HIP(hipGetLastError());
   uint32_t flags = 0;
-  OG_HIP(hipMemcpyAsync(out, out_d, n * pb, hipMemcpyDeviceToHost, ctx->stream));
-  OG_HIP(hipMemcpyAsync(&flags, f_d, 4, hipMemcpyDeviceToHost, ctx->stream));
-  OG_HIP(hipStreamSynchronize(ctx->stream));
+  OG_TRY(lem_run(ctx, dev, Affine<T>::BYTES == 128, false, in, n, out, nullptr, &flags, [&](uint8_t* in_d, uint8_t* c_d, uint8_t* out_d, uint32_t* f_d) {
+    hipLaunchKernelGGL(k_smul_uniform<T>, dim3(grid_for(n, 64)), dim3(64), 0, ctx->stream, in_d, n, k, c_d + 32, out_d, f_d);
+  }));
   OG_REQUIRE(!(flags & 1), who + ": a point coordinate of the key is not below the base-field modulus");
   OG_REQUIRE(!(flags & 2), who + ": a point of the key is not on its curve");
   return OG_OK;
@@ -424,26 +412,13 @@ int pk_contribute(og_ctx* ctx, const uint8_t* pkb, size_t pk_len, const uint8_t*
   const std::string who = "og_pk_contribute";
   const Fr dv = zfr_load(dd);
   OG_REQUIRE(fe_lt_modulus(dv) && !dv.is_zero(), who + ": the contribution must be canonical (below the group order) and non-zero");
-  OG_REQUIRE(pk_len >= 80 + 512 && rd64(pkb) == 0x313030304b50574full, who + ": not an OWPK0001 blob");
-  uint64_t hd[10];
-  memcpy(hd, pkb, 80);
-  const uint64_t m = hd[1], l = hd[2], power = hd[3], n_rows = hd[4];
-  OG_REQUIRE(power >= 1 && power <= 28 && m >= 1 && l < m && m < (1ull << 31) && hd[8] <= 1 && hd[9] == 0, who + ": bad key header");
-  const uint64_t d = 1ull << power, nl = m - l - 1, nh = d - 1;
-  OG_REQUIRE(n_rows <= d, who + ": more rows than the domain holds");
-  OG_REQUIRE(vk_len == 16 + 64 + 3 * 128 + (l + 1) * 64 && memcmp(vkb, "OWVK0001", 8) == 0 && rd64(vkb + 8) == l,
-             who + ": the verifying key does not belong to this proving key");
-  OG_REQUIRE(memcmp(vkb + 16, pkb + 80, 64) == 0 && memcmp(vkb + 16 + 64, pkb + 80 + 256, 128) == 0 && memcmp(vkb + 16 + 64 + 256, pkb + 80 + 384, 128) == 0,
-             who + ": the verifying key's alpha / beta / delta differ from the proving key's");
-  size_t off = 80 + 512;
-  for (int k = 0; k < 3; k++) {
-    OG_REQUIRE(hd[5 + k] < (1ull << 32), who + ": nnz too large");
-    off += zpad32((n_rows + 1) * 4) + zpad32(hd[5 + k] * 4) + zpad32(hd[5 + k] * 32);
-    OG_REQUIRE(off <= pk_len, who + ": truncated key");
-  }
-  off += 2 * zpad32(m * 64) + zpad32(m * 128);
-  const size_t l_off = off, h_off = off + zpad32(nl * 64);
-  OG_REQUIRE(h_off + zpad32(nh * 64) == pk_len, who + ": key length does not match its header");
+  PkView pv;
+  VkView vv;
+  OG_TRY(pk_view(pkb, pk_len, who, &pv));  // (the matrices ride along unread: no CSR check)
+  OG_REQUIRE(pv.flags <= 1 && pv.word9 == 0, who + ": bad key header");
+  OG_TRY(vk_view(vkb, vk_len, who, &vv));
+  OG_REQUIRE(vk_is_of_pk(vv, pv), who + ": the verifying key does not belong to this proving key (n_pub, alpha, beta or delta differ)");
+  const size_t nl = pv.nl, nh = pv.nh, l_off = pv.off(pv.query[3]), h_off = pv.off(pv.query[4]);
   K256 kd, kinv;
   memcpy(kd.l, dd, 32);
   uint8_t inv_b[32];
@@ -463,9 +438,9 @@ int pk_contribute(og_ctx* ctx, const uint8_t* pkb, size_t pk_len, const uint8_t*
   OG_TRY(smul_uniform<Fq>(ctx, dev, lh.data(), nl + nh, kinv, lh_out.data(), who));
   memcpy(&pk[l_off], lh_out.data(), nl * 64);
   memcpy(&pk[h_off], lh_out.data() + nl * 64, nh * 64);
-  OG_TRY(smul_uniform<Fq>(ctx, dev, pkb + 80 + 128, 1, kd, &pk[80 + 128], who));    // delta1
-  OG_TRY(smul_uniform<Fq2>(ctx, dev, pkb + 80 + 384, 1, kd, &pk[80 + 384], who));   // delta2
-  memcpy(&vk[16 + 64 + 256], &pk[80 + 384], 128);
+  OG_TRY(smul_uniform<Fq>(ctx, dev, pv.delta1, 1, kd, &pk[PK_DELTA1], who));
+  OG_TRY(smul_uniform<Fq2>(ctx, dev, pv.delta2, 1, kd, &pk[PK_DELTA2], who));
+  memcpy(&vk[VK_DELTA2], &pk[PK_DELTA2], 128);
   return OG_OK;
 }
 
@@ -500,11 +475,6 @@ static void challenge_seed(const char* tag, std::initializer_list<std::pair<cons
   zfr_store(seed, fe_from_mont(fe_to_mont(zfr_load(h))));  // (any 256-bit value goes in, its residue comes out)
 }
 
-static bool all_zero(const uint8_t* p, size_t n) {
-  for (size_t i = 0; i < n; i++)
-    if (p[i]) return false;
-  return true;
-}
 static bool any_infinity(const uint8_t* pts, size_t n, size_t pb) {
   for (size_t i = 0; i < n; i++)
     if (all_zero(pts + i * pb, pb)) return true;
@@ -629,59 +599,19 @@ int ptau_verify(og_ctx* ctx, const uint8_t* data, size_t len, uint32_t* failed_o
 // n canonical affine points on the host -> affine Montgomery on the device; *flags: 1 a coordinate >= q, 2 a point off the curve
 template <class T>
 static int canon_to_mont(og_ctx* ctx, ZDev& dev, const uint8_t* in, size_t n, uint8_t** mont_d, uint32_t* flags) {
-  constexpr size_t pb = Affine<T>::BYTES;
-  uint8_t *in_d, *c_d, *f_d;
-  OG_TRY(dev.get(n * pb, &in_d));
-  OG_TRY(dev.get(n * pb, mont_d));
-  OG_TRY(dev.get(96, &c_d));
-  OG_TRY(dev.get(4, &f_d));
-  alignas(16) uint8_t consts[96];
-  lem_consts(pb == 128, false, consts);
-  OG_HIP(hipMemcpyAsync(in_d, in, n * pb, hipMemcpyHostToDevice, ctx->stream));
-  OG_HIP(hipMemcpyAsync(c_d, consts, 96, hipMemcpyHostToDevice, ctx->stream));
-  OG_HIP(hipMemsetAsync(f_d, 0, 4, ctx->stream));
-  hipLaunchKernelGGL(k_canon_to_mont<T>, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, in_d, n, c_d + 32, *mont_d, (uint32_t*)f_d);
-  OG_HIP(hipGetLastError());
-  OG_HIP(hipMemcpyAsync(flags, f_d, 4, hipMemcpyDeviceToHost, ctx->stream));
-  OG_HIP(hipStreamSynchronize(ctx->stream));
-  return OG_OK;
-}
-
-// where the parts of an OWPK0001 blob lie, by its own header; false: the header is out of range or disagrees with the length
-struct PkLayout {
-  size_t m, l, power, n_rows, nnz[3];
-  size_t mat[3][3];  // ptr | col | val of A, B, C
-  size_t a_off, l_off, h_off;
-};
-static bool pk_layout(const uint8_t* pk, size_t len, PkLayout* out) {
-  if (len < 80 + 512) return false;
-  uint64_t hd[10];
-  memcpy(hd, pk, 80);
-  if (!(hd[3] >= 1 && hd[3] <= 28 && hd[1] >= 1 && hd[2] < hd[1] && hd[1] < (1ull << 31) && hd[4] <= (1ull << hd[3]))) return false;
-  out->m = hd[1]; out->l = hd[2]; out->power = hd[3]; out->n_rows = hd[4];
-  size_t off = 80 + 512;
-  for (int k = 0; k < 3; k++) {
-    if (hd[5 + k] >= (1ull << 32)) return false;
-    out->nnz[k] = hd[5 + k];
-    out->mat[k][0] = off;
-    out->mat[k][1] = off += zpad32((out->n_rows + 1) * 4);
-    out->mat[k][2] = off += zpad32(out->nnz[k] * 4);
-    off += zpad32(out->nnz[k] * 32);
-    if (off > len) return false;
-  }
-  out->a_off = off;
-  out->l_off = off + 2 * zpad32(out->m * 64) + zpad32(out->m * 128);
-  out->h_off = out->l_off + zpad32((out->m - out->l - 1) * 64);
-  return out->h_off + zpad32((((size_t)1 << out->power) - 1) * 64) == len;
+  OG_TRY(dev.get(n * Affine<T>::BYTES, mont_d));
+  return lem_run(ctx, dev, Affine<T>::BYTES == 128, false, in, n, nullptr, *mont_d, flags, [&](uint8_t* in_d, uint8_t* c_d, uint8_t* out_d, uint32_t* f_d) {
+    hipLaunchKernelGGL(k_canon_to_mont<T>, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, in_d, n, c_d + 32, out_d, f_d);
+  });
 }
 
 int pk_verify(og_ctx* ctx, const og_r1cs* r, const uint8_t* data, size_t len, const uint8_t* pkb, size_t pk_len, const uint8_t* vkb, size_t vk_len,
               uint32_t* failed_out) {
   const std::string who = "og_pk_verify";
-  OG_REQUIRE(pk_len >= 80 + 512 && rd64(pkb) == 0x313030304b50574full, who + ": not an OWPK0001 blob");
-  OG_REQUIRE(vk_len >= 16 + 64 + 3 * 128 && memcmp(vkb, "OWVK0001", 8) == 0, who + ": not an OWVK0001 blob");
-  OG_REQUIRE(rd64(pkb + 64) == 0, who + ": the key carries header flag " + std::to_string(rd64(pkb + 64)) +
-                                      " (imported without its .r1cs: no C matrix) -- import it beside its .r1cs (og_zkey_import with r1cs) and verify that key");
+  OG_REQUIRE(pk_is_blob(pkb, pk_len), who + ": not an OWPK0001 blob");
+  OG_REQUIRE(vk_is_blob(vkb, vk_len), who + ": not an OWVK0001 blob");
+  OG_REQUIRE(rd64(pkb + PK_FLAGS) == 0, who + ": the key carries header flag " + std::to_string(rd64(pkb + PK_FLAGS)) +
+                                            " (imported without its .r1cs: no C matrix) -- import it beside its .r1cs (og_zkey_import with r1cs) and verify that key");
   {
     std::lock_guard<std::mutex> lk(ctx->mu);
     OG_TRY(ctx_is_idle(ctx, who));
@@ -690,30 +620,28 @@ int pk_verify(og_ctx* ctx, const og_r1cs* r, const uint8_t* data, size_t len, co
   OG_TRY(ptau_setup(ctx, r, data, len, pk0, vk0, who));
   uint8_t seed[32];
   challenge_seed("owshen_gpu og_pk_verify 1", {{data, len}, {pkb, pk_len}, {vkb, vk_len}}, seed);
-  PkLayout lay, lay0;
-  OG_REQUIRE(pk_layout(pk0.data(), pk0.size(), &lay0), who + ": internal: the rebuilt key does not parse");
-  if (!pk_layout(pkb, pk_len, &lay) || lay.m != lay0.m || lay.l != lay0.l || lay.power != lay0.power || memcmp(lay.nnz, lay0.nnz, sizeof lay.nnz) != 0 ||
+  PkView pv, pv0;
+  OG_REQUIRE(pk_view(pk0.data(), pk0.size(), who, &pv0) == OG_OK, who + ": internal: the rebuilt key does not parse");
+  // any other fault in the structure of the CALLER's key is a verdict, not an error (its message is replaced below)
+  if (pk_view(pkb, pk_len, who, &pv) != OG_OK || pv.m != pv0.m || pv.l != pv0.l || pv.log_d != pv0.log_d || memcmp(pv.nnz, pv0.nnz, sizeof pv.nnz) != 0 ||
       vk_len != vk0.size()) {
     *failed_out = 63u;  // another shape: no query of this key is the size of the circuit's, nothing else has anything to be compared with
     set_error(who + ": failed checks: " + failed_names(63u, PK_CHECK, 6) + " (the key's header or length is not this circuit's: nothing else can be compared)");
     return OG_OK;
   }
-  const size_t m = lay0.m, nl = m - lay0.l - 1, nh = ((size_t)1 << lay0.power) - 1;
-  const size_t vk_fixed = 16 + 64 + 2 * 128, ic_off = vk_fixed + 128;  // magic, n_pub, alpha, beta, gamma | delta | IC
+  const size_t nl = pv0.nl, nh = pv0.nh;
   uint32_t mask = 0;
   // the matrices row for row; a key that went through a .zkey counts its rows up to the domain: the rows it adds must be empty
-  bool mats = lay.n_rows >= lay0.n_rows;
+  bool mats = pv.n_rows >= pv0.n_rows;
   for (int k = 0; k < 3 && mats; k++) {
-    const uint8_t *pt = pkb + lay.mat[k][0], *pt0 = &pk0[lay0.mat[k][0]];
-    mats = memcmp(pt, pt0, (lay0.n_rows + 1) * 4) == 0 && memcmp(pkb + lay.mat[k][1], &pk0[lay0.mat[k][1]], lay0.nnz[k] * 4) == 0 &&
-           memcmp(pkb + lay.mat[k][2], &pk0[lay0.mat[k][2]], lay0.nnz[k] * 32) == 0;
-    for (size_t i = lay0.n_rows + 1; i <= lay.n_rows && mats; i++) mats = rd32(pt + i * 4) == lay0.nnz[k];
+    mats = memcmp(pv.ptr[k], pv0.ptr[k], (pv0.n_rows + 1) * 4) == 0 && memcmp(pv.col[k], pv0.col[k], pv0.nnz[k] * 4) == 0 &&
+           memcmp(pv.val[k], pv0.val[k], pv0.nnz[k] * 32) == 0;
+    for (size_t i = pv0.n_rows + 1; i <= pv.n_rows && mats; i++) mats = rd32(pv.ptr[k] + i * 4) == pv0.nnz[k];
   }
-  if (!mats || rd64(pkb + 72) != 0 || memcmp(pkb + 80, &pk0[80], 128) != 0 || memcmp(pkb + 80 + 256, &pk0[80 + 256], 128) != 0 ||
-      memcmp(vkb, vk0.data(), vk_fixed) != 0)
-    mask |= 1u;
-  if (memcmp(pkb + lay.a_off, &pk0[lay0.a_off], lay0.l_off - lay0.a_off) != 0) mask |= 2u;
-  if (memcmp(vkb + ic_off, &vk0[ic_off], vk_len - ic_off) != 0) mask |= 4u;
+  if (!mats || pv.word9 != 0 || memcmp(pv.alpha1, pv0.alpha1, 128) != 0 || memcmp(pv.beta2, pv0.beta2, 128) != 0 || memcmp(vkb, vk0.data(), VK_DELTA2) != 0)
+    mask |= 1u;  // (alpha1 | beta1 in one comparison; the verifying key up to its delta2)
+  if (memcmp(pv.query[0], pv0.query[0], pv0.off(pv0.query[3]) - pv0.off(pv0.query[0])) != 0) mask |= 2u;
+  if (memcmp(vkb + VK_IC, &vk0[VK_IC], vk_len - VK_IC) != 0) mask |= 4u;
 
   std::lock_guard<std::mutex> lk(ctx->mu);
   OG_TRY(ctx_is_idle(ctx, who));
@@ -725,7 +653,7 @@ int pk_verify(og_ctx* ctx, const og_r1cs* r, const uint8_t* data, size_t len, co
   OG_TRY(keep.get(32, &seed_d));
   OG_HIP(hipMemcpyAsync(seed_d, seed, 32, hipMemcpyHostToDevice, ctx->stream));
   // ---- delta
-  const uint8_t *d1 = pkb + 80 + 128, *d2 = pkb + 80 + 384;
+  const uint8_t *d1 = pv.delta1, *d2 = pv.delta2;
   bool d1_ok = !all_zero(d1, 64), d2_ok = !all_zero(d2, 128);
   {
     ZDev dev;
@@ -741,17 +669,17 @@ int pk_verify(og_ctx* ctx, const og_r1cs* r, const uint8_t* data, size_t len, co
       d2_ok = !outside;
     }
   }
-  if (!d1_ok || !d2_ok || memcmp(d2, vkb + vk_fixed, 128) != 0 || !pairing_eq(d1, G2_GEN_BYTES, G1_GEN_BYTES, d2)) mask |= 8u;
+  if (!d1_ok || !d2_ok || memcmp(d2, vkb + VK_DELTA2, 128) != 0 || !pairing_eq(d1, G2_GEN_BYTES, G1_GEN_BYTES, d2)) mask |= 8u;
   if (!d2_ok) mask |= 16u | 32u;  // nothing to check L and H against
   // ---- L and H: e(sum rho_i Q_i, delta2) = e(sum rho_i Q0_i, G2), Q0 the delta = 1 key's query
-  const struct { size_t off, off0, n; uint32_t bit; } qs[2] = {{lay.l_off, lay0.l_off, nl, 16u}, {lay.h_off, lay0.h_off, nh, 32u}};
+  const struct { const uint8_t *q, *q0; size_t n; uint32_t bit; } qs[2] = {{pv.query[3], pv0.query[3], nl, 16u}, {pv.query[4], pv0.query[4], nh, 32u}};
   for (const auto& q : qs) {
     if (!d2_ok || q.n == 0) continue;
     ZDev dev;
     uint8_t *q_m, *q0_m;
     uint32_t f = 0, f0 = 0;
-    OG_TRY(canon_to_mont<Fq>(ctx, dev, pkb + q.off, q.n, &q_m, &f));
-    OG_TRY(canon_to_mont<Fq>(ctx, dev, &pk0[q.off0], q.n, &q0_m, &f0));
+    OG_TRY(canon_to_mont<Fq>(ctx, dev, q.q, q.n, &q_m, &f));
+    OG_TRY(canon_to_mont<Fq>(ctx, dev, q.q0, q.n, &q0_m, &f0));
     OG_REQUIRE(f0 == 0, who + ": internal: the rebuilt key holds a point off the curve");
     if (f) {  // an entry that is not canonical or not on the curve
       mask |= q.bit;

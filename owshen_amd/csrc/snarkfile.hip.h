@@ -7,6 +7,7 @@
 #include "ctx.h"
 #include "field.hip.h"
 #include "ec.hip.h"
+#include "key_blob.h"  // rd32 / rd64, the padded writer
 #include <string.h>
 #include <stdlib.h>
 #include <map>
@@ -213,16 +214,6 @@ struct BinFile {
   uint32_t version = 0;
   std::map<uint32_t, std::pair<const uint8_t*, uint64_t>> sec;  // the first occurrence of every section id
 };
-static uint32_t rd32(const uint8_t* p) {
-  uint32_t v;
-  memcpy(&v, p, 4);
-  return v;
-}
-static uint64_t rd64(const uint8_t* p) {
-  uint64_t v;
-  memcpy(&v, p, 8);
-  return v;
-}
 static int binfile_parse(const uint8_t* p, size_t len, const char* magic, uint32_t max_version, const std::string& who, BinFile* out) {
   OG_REQUIRE(len >= 12 && memcmp(p, magic, 4) == 0, who + ": not a " + magic + " file");
   out->version = rd32(p + 4);
@@ -278,14 +269,17 @@ static void lem_consts(bool g2, bool to_file, uint8_t out[32 + 64]) {
   }
 }
 
-// file <-> canonical for `n` points of one group (host buffers in and out; `mont_d`, optional: the Montgomery copy stays on the device)
-static int lem_convert(og_ctx* ctx, ZDev& dev, bool g2, bool to_file, const uint8_t* in, size_t n, uint8_t* out, uint8_t* mont_d,
-                       const std::string& who) {
-  if (n == 0) return OG_OK;
+// What the checked point kernels' host sides share: n points of one group up, the constants of lem_consts beside them, a
+// zeroed flag word, ONE launch -- launch(in_d, consts_d, out_d, flags_d) -- and the flag word back, synchronised.  out: the
+// kernel's n points to the host, or null; out_d: where they lie on the device, or null for scratch of this call.  What a raised
+// flag means is the caller's business.
+template <class Launch>
+static int lem_run(og_ctx* ctx, ZDev& dev, bool g2, bool to_file, const uint8_t* in, size_t n, uint8_t* out, uint8_t* out_d, uint32_t* flags,
+                   Launch launch) {
   const size_t pb = g2 ? 128 : 64;
-  uint8_t *in_d, *out_d, *c_d, *f_d;
+  uint8_t *in_d, *c_d, *f_d;
   OG_TRY(dev.get(n * pb, &in_d));
-  OG_TRY(dev.get(n * pb, &out_d));
+  if (!out_d) OG_TRY(dev.get(n * pb, &out_d));
   OG_TRY(dev.get(96, &c_d));
   OG_TRY(dev.get(4, &f_d));
   alignas(16) uint8_t consts[96];
@@ -293,15 +287,25 @@ static int lem_convert(og_ctx* ctx, ZDev& dev, bool g2, bool to_file, const uint
   OG_HIP(hipMemcpyAsync(in_d, in, n * pb, hipMemcpyHostToDevice, ctx->stream));
   OG_HIP(hipMemcpyAsync(c_d, consts, 96, hipMemcpyHostToDevice, ctx->stream));
   OG_HIP(hipMemsetAsync(f_d, 0, 4, ctx->stream));
-  if (g2)
-    hipLaunchKernelGGL(k_lem_import<Fq2>, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, in_d, n, c_d, out_d, mont_d, (uint32_t*)f_d, to_file ? 1 : 0);
-  else
-    hipLaunchKernelGGL(k_lem_import<Fq>, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, in_d, n, c_d, out_d, mont_d, (uint32_t*)f_d, to_file ? 1 : 0);
+  launch(in_d, c_d, out_d, (uint32_t*)f_d);
   OG_HIP(hipGetLastError());
-  uint32_t flags = 0;
-  OG_HIP(hipMemcpyAsync(out, out_d, n * pb, hipMemcpyDeviceToHost, ctx->stream));
-  OG_HIP(hipMemcpyAsync(&flags, f_d, 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (out) OG_HIP(hipMemcpyAsync(out, out_d, n * pb, hipMemcpyDeviceToHost, ctx->stream));
+  OG_HIP(hipMemcpyAsync(flags, f_d, 4, hipMemcpyDeviceToHost, ctx->stream));
   OG_HIP(hipStreamSynchronize(ctx->stream));
+  return OG_OK;
+}
+
+// file <-> canonical for `n` points of one group (host buffers in and out; `mont_d`, optional: the Montgomery copy stays on the device)
+static int lem_convert(og_ctx* ctx, ZDev& dev, bool g2, bool to_file, const uint8_t* in, size_t n, uint8_t* out, uint8_t* mont_d,
+                       const std::string& who) {
+  if (n == 0) return OG_OK;
+  uint32_t flags = 0;
+  OG_TRY(lem_run(ctx, dev, g2, to_file, in, n, out, nullptr, &flags, [&](uint8_t* in_d, uint8_t* c_d, uint8_t* out_d, uint32_t* f_d) {
+    if (g2)
+      hipLaunchKernelGGL(k_lem_import<Fq2>, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, in_d, n, c_d, out_d, mont_d, f_d, to_file ? 1 : 0);
+    else
+      hipLaunchKernelGGL(k_lem_import<Fq>, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, in_d, n, c_d, out_d, mont_d, f_d, to_file ? 1 : 0);
+  }));
   OG_REQUIRE(!(flags & 1), who + ": a point coordinate is not below the base-field modulus");
   OG_REQUIRE(!(flags & 2), who + ": a point is not on the curve");
   return OG_OK;
@@ -358,13 +362,6 @@ static void pow_table(const Fr& a, const Fr& c, size_t count, std::vector<uint8_
     zfr_store(&out[k * 32], fe_from_mont(t));
     t = fe_mul(t, a);
   }
-}
-
-static inline size_t zpad32(size_t n) { return (n + 31) / 32 * 32; }
-static void zput(std::vector<uint8_t>& out, const void* p, size_t n) {
-  const uint8_t* b = static_cast<const uint8_t*>(p);
-  out.insert(out.end(), b, b + n);
-  out.resize(out.size() + (zpad32(n) - n), 0);
 }
 
 static int blob_out(const std::vector<uint8_t>& v, uint8_t** out, size_t* len, const char* who) {

@@ -7,19 +7,17 @@
 // final exponentiation.  It reuses the SAME 9 x 29-bit field layer and group law as the kernels, compiled for
 // the host (no GPU is touched: the verifier must work on a sequencer without one).
 #include "verify_tower.h"
+#include "key_blob.h"
 
 namespace og {
 
-// vk blob: "OWVK0001" | u64 n_pub | alpha_g1 (64) | beta_g2 (128) | gamma_g2 (128) | delta_g2 (128) | IC ((n_pub+1) x 64)
+// the verifying key's layout: key_blob.h
 int verify_cpu(const uint8_t* vk, size_t vk_len, const uint8_t* pub, size_t n_pub, const uint8_t* proof, int* ok) {
   *ok = 0;
-  OG_REQUIRE(vk_len >= 16 + 64 + 3 * 128 && memcmp(vk, "OWVK0001", 8) == 0, "og_verify: bad verifying key (want OWVK0001)");
-  uint64_t n_vk;
-  memcpy(&n_vk, vk + 8, 8);
-  OG_REQUIRE(n_vk == n_pub, "og_verify: number of public inputs does not match the verifying key");
-  OG_REQUIRE(n_pub <= ((size_t)1 << 24), "og_verify: too many public inputs");  // also keeps (n_pub + 1) * 64 from wrapping
-  OG_REQUIRE(vk_len == 16 + 64 + 3 * 128 + (n_pub + 1) * 64, "og_verify: verifying key length does not match its header");
-  const uint8_t *alpha_b = vk + 16, *beta_b = alpha_b + 64, *gamma_b = beta_b + 128, *delta_b = gamma_b + 128, *ic_b = delta_b + 128;
+  VkView v;
+  OG_TRY(vk_view(vk, vk_len, "og_verify", &v));
+  OG_REQUIRE(v.n_pub == n_pub, "og_verify: number of public inputs does not match the verifying key");
+  const uint8_t *alpha_b = v.alpha1, *beta_b = v.beta2, *gamma_b = v.gamma2, *delta_b = v.delta2, *ic_b = v.ic;
   G1A alpha, A, Cc, icp;
   G2A beta, gamma, delta, B;
   bool inf;

@@ -2,6 +2,7 @@
 // and affine step (verify_tower.h).  The kernels are in verify_gpu.hip.  Not part of libowshen_verify.so.
 #include "verify_tower.h"
 #include "verify_vk.h"
+#include "key_blob.h"
 
 namespace og {
 namespace {
@@ -47,13 +48,11 @@ bool f12_plain_is_one(const uint32_t limbs[108]) {
 }
 
 int vk_precompute(const uint8_t* vk, size_t vk_len, VkHost& out) {
-  // the same tests, in the same order, as verify_cpu: what makes og_verify answer "invalid key" makes og_vk_load answer it
-  OG_REQUIRE(vk_len >= 16 + 64 + 3 * 128 && memcmp(vk, "OWVK0001", 8) == 0, "og_vk_load: bad verifying key (want OWVK0001)");
-  uint64_t n_pub;
-  memcpy(&n_pub, vk + 8, 8);
-  OG_REQUIRE(n_pub <= ((uint64_t)1 << 24), "og_vk_load: too many public inputs");
-  OG_REQUIRE(vk_len == 16 + 64 + 3 * 128 + (n_pub + 1) * 64, "og_vk_load: verifying key length does not match its header");
-  const uint8_t *alpha_b = vk + 16, *beta_b = alpha_b + 64, *gamma_b = beta_b + 128, *delta_b = gamma_b + 128, *ic_b = delta_b + 128;
+  // the same tests as verify_cpu: what makes og_verify answer "invalid key" makes og_vk_load answer it
+  VkView v;
+  OG_TRY(vk_view(vk, vk_len, "og_vk_load", &v));
+  const uint64_t n_pub = v.n_pub;
+  const uint8_t *alpha_b = v.alpha1, *beta_b = v.beta2, *gamma_b = v.gamma2, *delta_b = v.delta2, *ic_b = v.ic;
   G1A alpha, icp;
   G2A beta, gamma, delta;
   bool inf;

@@ -1,4 +1,4 @@
-// snarkjs key and witness files at the boundary: `.zkey` -> this library's "OWPK0001" / "OWVK0001" blobs (og_zkey_import),
+// snarkjs key and witness files at the boundary: `.zkey` -> this library's OWPK0001 / OWVK0001 blobs (og_zkey_import),
 // the way back (og_zkey_export), `.wtns` <-> canonical witness bytes (og_wtns_read / og_wtns_write).
 //
 // No reference counterpart: the snapshot holds no prover and no key; the lineage BASELINE.json's north_star
@@ -29,6 +29,7 @@
 #include "field.hip.h"
 #include "ec.hip.h"
 #include "snarkfile.hip.h"  // the container, the point decode kernel, the DFT over points: shared with ptau.hip
+#include "key_blob.h"
 #include <string.h>
 #include <stdlib.h>
 #include <algorithm>
@@ -125,11 +126,10 @@ int zkey_import(og_ctx* ctx, const uint8_t* data, size_t len, const og_r1cs* r1c
     OG_REQUIRE(mt <= 1 && c < d && sg < m && fe_lt_modulus(raw), who + ": coefficient " + std::to_string(i) + " out of range");
     ent[mt].push_back({(uint32_t)((c * kinv) & (d - 1)), sg, fe_mul(fe_to_mont(raw), ri2)});
   }
-  std::vector<uint32_t> ptr[3], col[3];
-  std::vector<uint8_t> val[3];
-  for (int k = 0; k < 2; k++) zcsr(ent[k], d, ptr[k], col[k], val[k]);
-  ptr[2].assign(d + 1, 0);
-  uint64_t flags = 1;
+  QapRows rows;  // over all d rows of the domain
+  for (int k = 0; k < 2; k++) zcsr(ent[k], d, rows.ptr[k], rows.col[k], rows.val[k]);
+  rows.ptr[2].assign(d + 1, 0);
+  uint64_t flags = 1;  // no .r1cs given: C z = (A z) o (B z)
   if (r1cs) {
     const uint64_t nc = r1cs->n_constraints;
     OG_REQUIRE(r1cs->n_wires == m && r1cs->n_pub == l, who + ": the .r1cs has " + std::to_string(r1cs->n_wires) + " wires / " + std::to_string(r1cs->n_pub) +
@@ -150,9 +150,9 @@ int zkey_import(og_ctx* ctx, const uint8_t* data, size_t len, const og_r1cs* r1c
     std::vector<uint8_t> rv;
     for (int k = 0; k < 2; k++) {
       zcsr(re[k], d, rp, rc, rv);
-      OG_REQUIRE(rp == ptr[k] && rc == col[k] && rv == val[k], who + std::string(": the .r1cs is not this key's circuit (matrix ") + (k ? "B" : "A") + " differs)");
+      OG_REQUIRE(rp == rows.ptr[k] && rc == rows.col[k] && rv == rows.val[k], who + std::string(": the .r1cs is not this key's circuit (matrix ") + (k ? "B" : "A") + " differs)");
     }
-    zcsr(re[2], d, ptr[2], col[2], val[2]);
+    zcsr(re[2], d, rows.ptr[2], rows.col[2], rows.val[2]);
     flags = 0;
   }
   // ---- points
@@ -190,38 +190,15 @@ int zkey_import(og_ctx* ctx, const uint8_t* data, size_t len, const og_r1cs* r1c
     pow_table(dom.psi, fe_neg(two), d, post);
     OG_TRY(ecntt_g1(ctx, dev, hm_d, z.power, tw, nullptr, &post, d - 1, hq.data()));
   }
-  // ---- "OWPK0001" (groth16.hip pk_load_impl); header flag 1 (no .r1cs given): C z = (A z) o (B z)
-  pk.clear();
-  const uint64_t head[10] = {0x313030304b50574full, m, l, (uint64_t)z.power, d, col[0].size(), col[1].size(), col[2].size(), flags, 0};
-  pk.insert(pk.end(), (const uint8_t*)head, (const uint8_t*)head + 80);
-  const uint8_t *alpha1 = &g1[0], *beta1 = &g1[64], *delta1 = &g1[128], *ic = &g1[192];
-  const uint8_t *aq = ic + (l + 1) * 64, *b1q = aq + m * 64, *cq = b1q + m * 64;
-  const uint8_t *beta2 = &g2[0], *gamma2 = &g2[128], *delta2 = &g2[256], *b2q = &g2[384];
-  zput(pk, alpha1, 64);
-  zput(pk, beta1, 64);
-  zput(pk, delta1, 64);
-  pk.resize(pk.size() + 64, 0);
-  zput(pk, beta2, 128);
-  zput(pk, delta2, 128);
-  for (int k = 0; k < 3; k++) {
-    zput(pk, ptr[k].data(), ptr[k].size() * 4);
-    zput(pk, col[k].data(), col[k].size() * 4);
-    zput(pk, val[k].data(), val[k].size());
-  }
-  zput(pk, aq, m * 64);
-  zput(pk, b1q, m * 64);
-  zput(pk, b2q, m * 128);
-  zput(pk, cq, nl * 64);
-  zput(pk, hq.data(), hq.size());
-  // ---- "OWVK0001" | n_pub | alpha_g1 | beta_g2 | gamma_g2 | delta_g2 | IC
-  vk.clear();
-  vk.insert(vk.end(), (const uint8_t*)"OWVK0001", (const uint8_t*)"OWVK0001" + 8);
-  vk.insert(vk.end(), (const uint8_t*)&l, (const uint8_t*)&l + 8);
-  vk.insert(vk.end(), alpha1, alpha1 + 64);
-  vk.insert(vk.end(), beta2, beta2 + 128);
-  vk.insert(vk.end(), gamma2, gamma2 + 128);
-  vk.insert(vk.end(), delta2, delta2 + 128);
-  vk.insert(vk.end(), ic, ic + (l + 1) * 64);
+  const uint8_t* ic = &g1[192];
+  KeyParts parts;
+  parts.m = m; parts.l = l; parts.log_d = z.power; parts.n_rows = d; parts.flags = flags;
+  parts.alpha1 = &g1[0]; parts.beta1 = &g1[64]; parts.delta1 = &g1[128];
+  parts.beta2 = &g2[0]; parts.gamma2 = &g2[128]; parts.delta2 = &g2[256];
+  parts.ic = ic;
+  parts.query[0] = ic + (l + 1) * 64; parts.query[1] = parts.query[0] + m * 64; parts.query[2] = &g2[384];
+  parts.query[3] = parts.query[1] + m * 64; parts.query[4] = hq.data();
+  key_blobs(parts, rows, pk, vk);
   return OG_OK;
 }
 
@@ -231,32 +208,15 @@ int zkey_import(og_ctx* ctx, const uint8_t* data, size_t len, const og_r1cs* r1c
 // (the quotient has degree <= d - 2, so its d-th coefficient never meets a base); section 10 says "no contributions".
 int zkey_export(og_ctx* ctx, const uint8_t* pkb, size_t pk_len, const uint8_t* vkb, size_t vk_len, std::vector<uint8_t>& out) {
   const std::string who = "og_zkey_export";
-  OG_REQUIRE(pk_len >= 80 + 512 && rd64(pkb) == 0x313030304b50574full, who + ": not an OWPK0001 blob");
-  uint64_t hd[10];
-  memcpy(hd, pkb, 80);
-  const uint64_t m = hd[1], l = hd[2], power = hd[3], n_rows = hd[4];
-  OG_REQUIRE(power >= 1 && power <= 27 && m >= 1 && l < m && m < (1ull << 31), who + ": bad key header");
-  const uint64_t d = 1ull << power, nl = m - l - 1, nh = d - 1;
-  OG_REQUIRE(n_rows <= d, who + ": more rows than the domain holds");
-  OG_REQUIRE(vk_len == 16 + 64 + 3 * 128 + (l + 1) * 64 && memcmp(vkb, "OWVK0001", 8) == 0 && rd64(vkb + 8) == l,
-             who + ": the verifying key does not belong to this proving key");
-  size_t off = 80 + 512;
-  const uint8_t *ptr_h[3], *col_h[3], *val_h[3];
-  for (int k = 0; k < 3; k++) {
-    OG_REQUIRE(hd[5 + k] < (1ull << 32), who + ": nnz too large");
-    ptr_h[k] = pkb + off; off += zpad32((n_rows + 1) * 4);
-    col_h[k] = pkb + off; off += zpad32(hd[5 + k] * 4);
-    val_h[k] = pkb + off; off += zpad32(hd[5 + k] * 32);
-    OG_REQUIRE(off <= pk_len, who + ": truncated key");
-  }
-  const uint8_t* q_h[5];
-  const size_t q_n[5] = {m, m, m, nl, nh};
-  const size_t q_pb[5] = {64, 64, 128, 64, 64};
-  for (int k = 0; k < 5; k++) {
-    q_h[k] = pkb + off;
-    off += zpad32(q_n[k] * q_pb[k]);
-  }
-  OG_REQUIRE(off == pk_len, who + ": key length does not match its header");
+  PkView pv;
+  VkView vv;
+  OG_TRY(pk_view(pkb, pk_len, who, &pv));  // (header words 8 and 9 are not looked at, nor is the C matrix: neither goes into the file)
+  const uint64_t m = pv.m, l = pv.l, power = pv.log_d, n_rows = pv.n_rows, d = pv.d, nl = pv.nl, nh = pv.nh;
+  OG_REQUIRE(power <= 27, who + ": bad key header (a .zkey's domain holds at most 2^27 points)");
+  OG_TRY(vk_view(vkb, vk_len, who, &vv));
+  OG_REQUIRE(vk_is_of_pk(vv, pv), who + ": the verifying key does not belong to this proving key (n_pub, alpha, beta or delta differ)");
+  OG_TRY(pk_csr_check(pv, 2, who));
+  const uint8_t* const* q_h = pv.query;
   ZDomain dom;
   OG_TRY(zdomain((int)power, who, &dom));
   // ---- coefficients: row i -> constraint i k mod d, value x 2^512
@@ -265,16 +225,11 @@ int zkey_export(og_ctx* ctx, const uint8_t* pkb, size_t pk_len, const uint8_t* v
   std::vector<uint8_t> cs(4);
   uint64_t n_coef = 0;
   for (int k = 0; k < 2; k++) {
-    const uint32_t* p = (const uint32_t*)ptr_h[k];
-    const uint32_t* c = (const uint32_t*)col_h[k];
-    OG_REQUIRE(p[0] == 0 && p[n_rows] == hd[5 + k], who + ": CSR row pointers inconsistent");
     for (uint64_t row = 0; row < n_rows; row++) {
-      OG_REQUIRE(p[row] <= p[row + 1] && p[row + 1] <= hd[5 + k], who + ": CSR row pointers not monotone");
-      for (uint32_t e = p[row]; e < p[row + 1]; e++) {
-        OG_REQUIRE(c[e] < m, who + ": CSR column out of range");
-        const Fr v = zfr_load(val_h[k] + (size_t)e * 32);
+      for (uint32_t e = rd32(pv.ptr[k] + row * 4), end = rd32(pv.ptr[k] + row * 4 + 4); e < end; e++) {
+        const Fr v = zfr_load(pv.val[k] + (size_t)e * 32);
         OG_REQUIRE(fe_lt_modulus(v), who + ": coefficient not canonical");
-        const uint32_t rec[3] = {(uint32_t)k, (uint32_t)((row * dom.k) & (d - 1)), c[e]};
+        const uint32_t rec[3] = {(uint32_t)k, (uint32_t)((row * dom.k) & (d - 1)), rd32(pv.col[k] + (size_t)e * 4)};
         cs.insert(cs.end(), (const uint8_t*)rec, (const uint8_t*)rec + 12);
         cs.resize(cs.size() + 32);
         zfr_store(&cs[cs.size() - 32], fe_from_mont(fe_mul(fe_to_mont(v), r2)));
@@ -295,21 +250,19 @@ int zkey_export(og_ctx* ctx, const uint8_t* pkb, size_t pk_len, const uint8_t* v
   std::vector<uint8_t> g1_in(n1 * 64), g1(n1 * 64), g2_in(n2 * 128), g2(n2 * 128), hsec(d * 64);
   {
     uint8_t* o = g1_in.data();
-    memcpy(o, pkb + 80, 64); o += 64;        // alpha1
-    memcpy(o, pkb + 80 + 64, 64); o += 64;   // beta1
-    memcpy(o, pkb + 80 + 128, 64); o += 64;  // delta1
-    memcpy(o, vkb + 16 + 64 + 384, (l + 1) * 64); o += (l + 1) * 64;
+    memcpy(o, pv.alpha1, 64); o += 64;
+    memcpy(o, pv.beta1, 64); o += 64;
+    memcpy(o, pv.delta1, 64); o += 64;
+    memcpy(o, vv.ic, (l + 1) * 64); o += (l + 1) * 64;
     memcpy(o, q_h[0], m * 64); o += m * 64;
     memcpy(o, q_h[1], m * 64); o += m * 64;
     memcpy(o, q_h[3], nl * 64);
     uint8_t* q = g2_in.data();
-    memcpy(q, pkb + 80 + 256, 128); q += 128;      // beta2
-    memcpy(q, vkb + 16 + 64 + 128, 128); q += 128;  // gamma2
-    memcpy(q, pkb + 80 + 384, 128); q += 128;      // delta2
+    memcpy(q, pv.beta2, 128); q += 128;
+    memcpy(q, vv.gamma2, 128); q += 128;
+    memcpy(q, pv.delta2, 128); q += 128;
     memcpy(q, q_h[2], m * 128);
   }
-  OG_REQUIRE(memcmp(vkb + 16, pkb + 80, 64) == 0 && memcmp(vkb + 16 + 64, pkb + 80 + 256, 128) == 0 && memcmp(vkb + 16 + 64 + 256, pkb + 80 + 384, 128) == 0,
-             who + ": the verifying key's alpha / beta / delta differ from the proving key's");
   OG_TRY(lem_convert(ctx, dev, false, true, g1_in.data(), n1, g1.data(), nullptr, who));
   OG_TRY(lem_convert(ctx, dev, true, true, g2_in.data(), n2, g2.data(), nullptr, who));
   {
