@@ -352,6 +352,41 @@ int og_deposit_witness_d(og_ctx* ctx, const uint8_t* inputs_d, size_t n, uint8_t
 int og_deposit_prove_batch_d(og_ctx* ctx, const og_pk* pk, const uint8_t* inputs_d, size_t n, const uint8_t* rs,
                              uint8_t* proofs_out, uint8_t* public_out);
 
+/* ---- split statement: withdraw part of a note, keep the rest as a fresh change note ----------------------------------------------
+ * "I know a note under `root` worth `amount` of `token`.  I take `amount_out` of it out to `recipient`.  The rest, change =
+ * amount - amount_out, goes into the new leaf `change_leaf`."  (No reference counterpart: the snapshot's withdraw burns a whole
+ * amount, /root/reference/src/services/api_services/withdraw.rs:27-71.)
+ * public (n_pub = 7, verifier order): root, nullifier_hash, recipient, amount_out, token, chain_id, change_leaf
+ * private: nullifier, secret, amount, change_commitment, change, a depth-`depth` MiMC7 Merkle path.  With H = MultiMiMC7 2-to-1:
+ *   leaf = H(H(nullifier, secret), H(amount, token)) is under root at `index`;  nullifier_hash = H(nullifier, 0);
+ *   amount_out + change = amount with amount_out < 2^128 and change < 2^128 (a 128-bit decomposition each: the sum stays below
+ *   2^129 < r and cannot wrap -- this is what stops an overdraw);
+ *   change_leaf = H(change_commitment, H(change, token)) -- the leaf shape of a deposit, so the change note is later spent by the
+ *   withdraw or the split statement like any other;  recipient and chain_id are bound by a square each.
+ * `amount` is PRIVATE here: only amount_out is revealed, not the size of the note that was spent.  change_commitment is an
+ * unconstrained private input, c' = H(nullifier', secret') formed by the prover off-circuit (a c' nobody can open harms only
+ * the prover: the argument of the deposit statement).  amount_out = 0 with somebody else's c' is a transfer inside the pool;
+ * amount_out = amount leaves a zero-value change note.  The ledger's part: og_verify the proof, check that root is known and
+ * nullifier_hash unspent, pay amount_out, append change_leaf (og_mimc7_append_d).
+ * Wire and row order: tests/split_spec.py (the spec), og_split_r1cs / owshen_amd/circuit.py split_r1cs (the R1CS):
+ *   n_wires = 271 + 3 depth + (6 + depth) 730 - 3, n_constraints = 261 + 2 depth + (6 + depth) 730 (28 104 / 28 065 at depth
+ *   32: domain 2^15).  depth 1..64; n <= 65 535 per og_split_witness_d call.  shape[0..2] = n_wires, n_constraints, n_pub.
+ * inputs_d: n records of (9 + depth) x 32 B canonical little-endian:
+ *   nullifier | secret | amount | recipient | amount_out | index (u64, low bytes) | token | chain_id | change_commitment | siblings[depth]
+ * witness_out_d: n x n_wires x 32 B.  og_split_prove_batch_d: records -> proofs (rs: n x 64 B host, proofs_out: n x 256 B host,
+ * public_out (host, may be NULL): n x 7 x 32 B in verifier order -- root, nullifier_hash and change_leaf are COMPUTED by the
+ * witness generator).  Same bytes as og_split_witness_d + og_prove_batch_d.  The key must have this shape's wire count and n_pub.
+ * OG_ERR_INVALID, before anything is proved: a malformed record; og_last_error names the record and its lowest offending field
+ * ("input record 3: field 4 (amount_out)"; 0 nullifier, 1 secret, 2 amount, 3 recipient, 4 amount_out, 5 index, 6 token,
+ * 7 chain_id, 8 change_commitment, 9 + l sibling l): any field >= r; an index that does not fit the tree; field 2 if amount >=
+ * 2^128; field 4 if amount_out >= 2^128 or amount_out > amount (compared as integers).  There is no submit / job form, no
+ * multi-GPU form and no window-sharded form of this statement, and og_set_host_chains does not change how its witnesses are
+ * generated. */
+int og_split_shape(int depth, uint64_t shape[3]);
+int og_split_witness_d(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, uint8_t* witness_out_d);
+int og_split_prove_batch_d(og_ctx* ctx, const og_pk* pk, int depth, const uint8_t* inputs_d, size_t n, const uint8_t* rs,
+                           uint8_t* proofs_out, uint8_t* public_out);
+
 /* The same call in two halves, for a host that keeps requests flowing (a sequencer proving batch after batch): submit
  * enqueues ALL the work of the batch on the ctx's streams and returns; og_job_wait blocks until it is done, fills
  * proofs_out / public_out (which, like rs, must stay valid until then) and frees the job.  At most two calls may be in
@@ -422,6 +457,8 @@ typedef struct og_r1cs og_r1cs;
 int og_withdraw_r1cs(og_ctx* ctx, int depth, uint64_t n_pad3, uint64_t n_pad2, int dense, og_r1cs** out);
 /* the statement of og_deposit_witness_d (wire and row order: oracle/py/deposit.py) */
 int og_deposit_r1cs(og_ctx* ctx, og_r1cs** out);
+/* the statement of og_split_witness_d at this depth (wire and row order: tests/split_spec.py) */
+int og_split_r1cs(og_ctx* ctx, int depth, og_r1cs** out);
 int og_r1cs_from_csr(uint64_t n_wires, uint64_t n_pub, uint64_t n_constraints, const uint32_t* const ptr[3],
                      const uint32_t* const col[3], const uint8_t* const val[3], og_r1cs** out);
 void og_r1cs_free(og_r1cs* r1cs);

@@ -19,6 +19,9 @@ points, Fr NTT 2^17"): n_wires = 2^18, domain 2^17.
 
 Only index arrays and constants are produced here (numpy); there is no host-side witness
 generator -- the witness comes from og_withdraw_witness_d.
+
+The deposit and the split statement (oracle/py/deposit.py, tests/split_spec.py are their specs) follow further down, built with
+the same gadget builder.
 """
 import ctypes as C
 
@@ -375,6 +378,114 @@ def deposit_prove(ctx, pk, inputs_d, rs, return_public=False):
     ctx._check(ctx._lib.og_deposit_prove_batch_d(ctx._h, pk._h, ctx.ptr(inputs_d), n, rsb.ctypes.data_as(C.c_void_p),
                                                  out.ctypes.data_as(C.c_void_p), pub.ctypes.data_as(C.c_void_p) if return_public else None))
     return (out, pub) if return_public else out
+
+
+# ---- the split statement (tests/split_spec.py is the spec; witness.hip k_split_core fills the wires) --------------------------------
+# public: root, nullifier_hash, recipient, amount_out, token, chain_id, change_leaf; private: nullifier, secret, amount,
+# change_commitment, change, the path.  leaf = H(H(nullifier, secret), H(amount, token)) under root; amount_out + change = amount,
+# both below 2^128 by a bit decomposition; change_leaf = H(change_commitment, H(change, token)).  The reference's withdraw
+# (/root/reference/src/services/api_services/withdraw.rs:27-71) burns a whole amount; with this statement part of a note leaves
+# the pool and the rest stays in it as a fresh note.
+S_N_PUB, S_N_REC, S_N_BITS = 7, 9, 128
+(SW_ROOT, SW_NH, SW_RECIPIENT, SW_AMOUNT_OUT, SW_TOKEN, SW_CHAIN, SW_CHANGE_LEAF, SW_NULLIFIER, SW_SECRET, SW_AMOUNT, SW_CHANGE_COMMITMENT,
+ SW_CHANGE) = range(1, 13)
+
+
+def split_shape(depth):
+    """(n_wires, n_constraints): (28104, 28065) at depth 32"""
+    return 1 + S_N_PUB + 5 + 2 * depth + 2 + 2 * S_N_BITS + depth + (6 + depth) * 730 - 3, 3 + 2 * (S_N_BITS + 1) + 2 * depth + (6 + depth) * 730
+
+
+def split_r1cs(mimc7_constants, depth=32):
+    """the split statement as an R1CS (the same gadget builder as the withdraw circuit); no padding gates"""
+    assert depth >= 1 and len(mimc7_constants) == N_ROUNDS
+    n_wires, n_constraints = split_shape(depth)
+    bld = _Builder([int(c) for c in mimc7_constants])
+    bld.alloc(1 + S_N_PUB + 5)
+    w_sib = bld.alloc(depth)
+    w_bit = bld.alloc(depth)
+    w_rsq = bld.alloc()
+    w_csq = bld.alloc()
+    w_obit = bld.alloc(S_N_BITS)
+    w_cbit = bld.alloc(S_N_BITS)
+    bld.enforce([(SW_RECIPIENT, 1)], [(SW_RECIPIENT, 1)], [(w_rsq, 1)])
+    bld.enforce([(SW_CHAIN, 1)], [(SW_CHAIN, 1)], [(w_csq, 1)])
+    bld.enforce([(SW_AMOUNT_OUT, 1), (SW_CHANGE, 1)], [(0, 1)], [(SW_AMOUNT, 1)])
+    for value, bits in ((SW_AMOUNT_OUT, w_obit), (SW_CHANGE, w_cbit)):   # value < 2^128: boolean bits, then the recomposition
+        for i in range(S_N_BITS):
+            bld.enforce([(bits + i, 1)], [(bits + i, 1), (0, R - 1)], [])
+        bld.enforce([(bits + i, 1 << i) for i in range(S_N_BITS)], [(0, 1)], [(value, 1)])
+    inner = bld.hash2([(SW_NULLIFIER, 1)], [(SW_SECRET, 1)])
+    asset = bld.hash2([(SW_AMOUNT, 1)], [(SW_TOKEN, 1)])
+    cur = bld.hash2([(inner, 1)], [(asset, 1)])
+    bld.hash2([(SW_NULLIFIER, 1)], [], out_wire=SW_NH)
+    for l in range(depth):
+        b, s = w_bit + l, w_sib + l
+        bld.enforce([(b, 1)], [(b, 1), (0, R - 1)], [])
+        left = bld.alloc()
+        bld.enforce([(b, 1)], [(s, 1), (cur, R - 1)], [(left, 1), (cur, R - 1)])
+        right = [(s, 1), (cur, 1), (left, R - 1)]
+        cur = bld.hash2([(left, 1)], right, out_wire=SW_ROOT if l == depth - 1 else None)
+    change_asset = bld.hash2([(SW_CHANGE, 1)], [(SW_TOKEN, 1)])
+    bld.hash2([(SW_CHANGE_COMMITMENT, 1)], [(change_asset, 1)], out_wire=SW_CHANGE_LEAF)
+    assert bld.next == n_wires
+    none = np.zeros(0, dtype=np.int64)
+    pad = (none, none, none)
+    r1cs = R1CS(n_wires, S_N_PUB, _csr(bld.a, *pad, n_wires), _csr(bld.b, *pad, n_wires), _csr(bld.c, *pad, n_wires))
+    assert r1cs.n_constraints == n_constraints
+    return r1cs
+
+
+def split_r1cs_native(ctx, depth=32):
+    """the same statement built by the library (og_split_r1cs: what a Rust host calls)"""
+    h = C.c_void_p()
+    ctx._check(ctx._lib.og_split_r1cs(ctx._h, depth, C.byref(h)))
+    return _r1cs_from_handle(ctx, h)
+
+
+def pack_split_inputs(nullifier, secret, amount, recipient, amount_out, index, siblings, token=0, chain_id=0, change_commitment=0):
+    """one split record: (9 + depth) x 32 B (include/owshen_gpu.h):
+    nullifier | secret | amount | recipient | amount_out | index | token | chain_id | change_commitment | siblings[depth]"""
+    vals = [nullifier, secret, amount, recipient, amount_out, index, token, chain_id, change_commitment] + list(siblings)
+    return np.frombuffer(b"".join(int(v).to_bytes(32, "little") for v in vals), dtype=np.uint8).reshape(-1, 32).copy()
+
+
+def split_witness(ctx, depth, inputs_d):
+    """inputs_d: device uint8 [n, 9 + depth, 32] -> device uint8 [n, n_wires, 32] (og_split_witness_d)"""
+    n = inputs_d.shape[0]
+    assert tuple(inputs_d.shape[1:]) == (S_N_REC + depth, 32)
+    shp = (C.c_uint64 * 3)()
+    ctx._check(ctx._lib.og_split_shape(depth, shp))
+    assert (int(shp[0]), int(shp[1]), int(shp[2])) == (*split_shape(depth), S_N_PUB), "circuit.py and witness.hip disagree on the split shape"
+    out = ctx.empty(n, int(shp[0]), 32)
+    ctx._pre()
+    ctx._check(ctx._lib.og_split_witness_d(ctx._h, depth, ctx.ptr(inputs_d), n, ctx.ptr(out)))
+    return out
+
+
+def split_prove(ctx, pk, depth, inputs_d, rs, return_public=False):
+    """inputs_d: device uint8 [n, 9 + depth, 32]; rs: (r, s) pairs or uint8 [n, 64] -> np.uint8 [n, 256] (og_split_prove_batch_d);
+    return_public: also (root, nullifier_hash, recipient, amount_out, token, chain_id, change_leaf) of every proof, np.uint8 [n, 7, 32]"""
+    n = inputs_d.shape[0]
+    assert tuple(inputs_d.shape[1:]) == (S_N_REC + depth, 32)
+    rsb = pk._rs_bytes(rs)
+    assert rsb.shape[0] == n
+    out = np.zeros((n, 256), dtype=np.uint8)
+    pub = np.zeros((n, S_N_PUB, 32), dtype=np.uint8) if return_public else None
+    ctx._pre()
+    ctx._check(ctx._lib.og_split_prove_batch_d(ctx._h, pk._h, depth, ctx.ptr(inputs_d), n, rsb.ctypes.data_as(C.c_void_p),
+                                               out.ctypes.data_as(C.c_void_p), pub.ctypes.data_as(C.c_void_p) if return_public else None))
+    return (out, pub) if return_public else out
+
+
+def split_change_leaf(change_commitment, change, token, ctx):
+    """the ledger's side of a split: the leaf of the change note, H(change_commitment, H(change, token)), through og_mimc7_hash2_d
+    (the value of public input 7; what og_mimc7_append_d appends).  Returns an int."""
+    def dev(v):
+        return ctx.to_device(np.frombuffer(int(v).to_bytes(32, "little"), dtype=np.uint8).reshape(1, 32).copy())
+
+    leaf = ctx.mimc7_hash2(dev(change_commitment), ctx.mimc7_hash2(dev(change), dev(token)))
+    return int.from_bytes(ctx.to_host(leaf).tobytes(), "little")
 
 
 class ProveJob:

@@ -8,6 +8,8 @@
 //
 //   og_withdraw_r1cs   constraint rows of the depth-D MiMC7 Merkle withdraw circuit (+ synthetic padding gates, + the two
 //                      optional density rows), CSR, canonical 32-byte coefficients
+//   og_deposit_r1cs / og_split_r1cs   the deposit and the split statement, with the same builder (oracle/py/deposit.py,
+//                      tests/split_spec.py)
 //   og_r1cs_from_csr   any R1CS the caller built
 //   og_setup           Groth16 key generation from (tau, alpha, beta, gamma, delta): Lagrange evaluations, the three
 //                      transposed sparse products, the query scalars and ~3 m + d fixed-base multiplications, all on the
@@ -200,6 +202,54 @@ int deposit_r1cs_build(const uint8_t* mimc_consts, og_r1cs* r) {
   b.enforce(R1csBuilder::one(DW_DEPOSITOR), R1csBuilder::one(DW_DEPOSITOR), R1csBuilder::one(w_dsq));  // binds the depositor to the proof
   b.hash2(R1csBuilder::one(DW_NULLIFIER), R1csBuilder::one(DW_SECRET), (int)DW_COMMITMENT);
   OG_REQUIRE(b.next == r->n_wires && r->n_constraints == shp[1], "og_deposit_r1cs: internal shape mismatch");
+  return OG_OK;
+}
+
+// the split statement (tests/split_spec.py; witness.hip k_split_core): withdraw part of a note, the rest into a change note
+int split_shape_query(int depth, uint64_t out[3]);
+int split_r1cs_build(const uint8_t* mimc_consts, int depth, og_r1cs* r) {
+  uint64_t shp[3];
+  OG_TRY(split_shape_query(depth, shp));
+  r->n_wires = shp[0];
+  r->n_pub = shp[2];
+  for (int k = 0; k < 3; k++) r->ptr[k].assign(1, 0u);
+  R1csBuilder b{r, 0, mimc_consts};
+  const HFr m1 = hfr_neg_one();
+  constexpr uint32_t SW_ROOT = 1, SW_NH = 2, SW_RECIPIENT = 3, SW_AMOUNT_OUT = 4, SW_TOKEN = 5, SW_CHAIN = 6, SW_CHANGE_LEAF = 7, SW_NULLIFIER = 8,
+                     SW_SECRET = 9, SW_AMOUNT = 10, SW_CHANGE_COMMITMENT = 11, SW_CHANGE = 12;
+  OG_REQUIRE(r->n_pub == 7, "og_split_r1cs: the statement has seven public inputs");
+  b.alloc(1 + 7 + 5);
+  const uint32_t w_sib = b.alloc(depth), w_bit = b.alloc(depth), w_rsq = b.alloc(), w_csq = b.alloc();
+  const uint32_t w_obit = b.alloc(128), w_cbit = b.alloc(128);
+  b.enforce(R1csBuilder::one(SW_RECIPIENT), R1csBuilder::one(SW_RECIPIENT), R1csBuilder::one(w_rsq));
+  b.enforce(R1csBuilder::one(SW_CHAIN), R1csBuilder::one(SW_CHAIN), R1csBuilder::one(w_csq));
+  b.enforce(LC{{SW_AMOUNT_OUT, hfr_u64(1)}, {SW_CHANGE, hfr_u64(1)}}, R1csBuilder::one(0), R1csBuilder::one(SW_AMOUNT));  // amount_out + change = amount
+  for (int v = 0; v < 2; v++) {  // amount_out, then change: 128 boolean rows and the recomposition, so that each is < 2^128
+    const uint32_t bits = v ? w_cbit : w_obit;
+    LC sum;
+    for (uint32_t i = 0; i < 128; i++) {
+      b.enforce(R1csBuilder::one(bits + i), LC{{bits + i, hfr_u64(1)}, {0u, m1}}, LC{});
+      HFr p2 = {{0, 0, 0, 0}};
+      p2.v[i >> 6] = 1ull << (i & 63);
+      sum.push_back({bits + i, p2});
+    }
+    b.enforce(sum, R1csBuilder::one(0), R1csBuilder::one(v ? SW_CHANGE : SW_AMOUNT_OUT));
+  }
+  const uint32_t inner = b.hash2(R1csBuilder::one(SW_NULLIFIER), R1csBuilder::one(SW_SECRET));
+  const uint32_t asset = b.hash2(R1csBuilder::one(SW_AMOUNT), R1csBuilder::one(SW_TOKEN));
+  uint32_t cur = b.hash2(R1csBuilder::one(inner), R1csBuilder::one(asset));
+  b.hash2(R1csBuilder::one(SW_NULLIFIER), LC{}, (int)SW_NH);
+  for (int l = 0; l < depth; l++) {
+    const uint32_t bit = w_bit + l, s = w_sib + l;
+    b.enforce(R1csBuilder::one(bit), LC{{bit, hfr_u64(1)}, {0u, m1}}, LC{});              // bit (bit - 1) = 0
+    const uint32_t left = b.alloc();
+    b.enforce(R1csBuilder::one(bit), LC{{s, hfr_u64(1)}, {cur, m1}}, LC{{left, hfr_u64(1)}, {cur, m1}});  // left = cur + bit (s - cur)
+    const LC right{{s, hfr_u64(1)}, {cur, hfr_u64(1)}, {left, m1}};
+    cur = b.hash2(R1csBuilder::one(left), right, l == depth - 1 ? (int)SW_ROOT : -1);
+  }
+  const uint32_t change_asset = b.hash2(R1csBuilder::one(SW_CHANGE), R1csBuilder::one(SW_TOKEN));
+  b.hash2(R1csBuilder::one(SW_CHANGE_COMMITMENT), R1csBuilder::one(change_asset), (int)SW_CHANGE_LEAF);
+  OG_REQUIRE(b.next == r->n_wires && r->n_constraints == shp[1], "og_split_r1cs: internal shape mismatch");
   return OG_OK;
 }
 
@@ -420,6 +470,21 @@ int og_deposit_r1cs(og_ctx* ctx, og_r1cs** out) {
     *out = nullptr;
     og_r1cs* r = new og_r1cs();
     int rc = deposit_r1cs_build(ctx->mimc_consts_canon, r);
+    if (rc != OG_OK) {
+      delete r;
+      return rc;
+    }
+    *out = r;
+    return OG_OK;
+  });
+}
+
+int og_split_r1cs(og_ctx* ctx, int depth, og_r1cs** out) {
+  return guarded([&]() -> int {
+    OG_REQUIRE(ctx != nullptr && out != nullptr, "og_split_r1cs: null argument");
+    *out = nullptr;
+    og_r1cs* r = new og_r1cs();
+    int rc = split_r1cs_build(ctx->mimc_consts_canon, depth, r);
     if (rc != OG_OK) {
       delete r;
       return rc;

@@ -7,6 +7,7 @@
 //   k_withdraw_core  one lane per proof: public inputs, the (4 + depth) MultiMiMC7 gadgets with every
 //                    intermediate power (t^2, t^4, t^6, t^7 per round), the Merkle selectors
 //   k_withdraw_pad   one lane per padding unit (a 3-wire gate or a 64-gate chained segment)
+//   k_deposit_witness / k_split_core   the deposit and the split statement (further down), one lane per request
 //
 // Input record per proof, (8 + depth) x 32 B canonical LE:
 //   nullifier | secret | amount | recipient | pad_seed | index (u64 in the low bytes) | token | chain_id | siblings[depth]
@@ -882,6 +883,222 @@ int deposit_witness(og_ctx* ctx, const uint8_t* inputs_d, size_t n, uint8_t* out
   hipLaunchKernelGGL(k_deposit_witness, dim3(grid_for(n, 64)), dim3(64), 0, ctx->stream, (const uint32_t*)ctx->mimc_consts_d, inputs_d, n, out_d);
   OG_HIP(hipGetLastError());
   hipLaunchKernelGGL(k_wires_from_mont, dim3(grid_for(D_WIRES, 256), (unsigned)n), dim3(256), 0, ctx->stream, out_d, (size_t)D_WIRES, D_WIRES, 1u);
+  OG_HIP(hipGetLastError());
+  return OG_OK;
+}
+
+// ---- the split statement: withdraw part of a note, keep the rest as a change note ---------------------------------------------------
+// Spec: tests/split_spec.py.  public: root, nullifier_hash, recipient, amount_out, token, chain_id, change_leaf (n_pub = 7); private:
+// nullifier, secret, amount, change_commitment, change, the path.  The note leaf = H(H(nullifier, secret), H(amount, token)) lies under
+// root, nullifier_hash = H(nullifier, 0), amount_out + change = amount with both below 2^128 (a 128-bit decomposition each: the sum
+// cannot wrap, which is what stops an overdraw), change_leaf = H(change_commitment, H(change, token)) -- a leaf of the deposit
+// shape, which og_mimc7_append_d appends.  `amount` is private here.  No reference counterpart (the snapshot's withdraw is a whole-
+// amount ECDSA-authorised burn, /root/reference/src/services/api_services/withdraw.rs:27-71).
+// Input record per request, (9 + depth) x 32 B canonical LE:
+//   nullifier | secret | amount | recipient | amount_out | index (u64 in the low bytes) | token | chain_id | change_commitment | siblings[depth]
+// Wires:
+//   0 one | 1 root | 2 nullifier_hash | 3 recipient | 4 amount_out | 5 token | 6 chain_id | 7 change_leaf
+//   8 nullifier | 9 secret | 10 amount | 11 change_commitment | 12 change | 13.. siblings[D] | index bits[D] | recipient^2 | chain_id^2
+//   | amount_out bits[128] (LSB first) | change bits[128] | the gadgets: inner, asset, leaf, nullifier_hash (out = wire 2), level
+//   0..D-1 (the last one's out = wire 1), change_asset = H(change, token), change_leaf = H(change_commitment, change_asset) (out = wire 7)
+constexpr int S_PUB = 7;
+constexpr int S_REC = 9;  // fields of a split record before the siblings
+constexpr int S_BITS = 128;
+
+struct SplitShape {
+  uint64_t n_wires, n_constraints, first_bit_wire;
+};
+
+static SplitShape split_shape(int depth) {
+  SplitShape s;
+  const uint64_t hashes = 6 + (uint64_t)depth;
+  s.first_bit_wire = 1 + S_PUB + 5 + 2 * (uint64_t)depth + 2;
+  s.n_wires = s.first_bit_wire + 2 * S_BITS + depth + hashes * 730 - 3;  // (the gadgets follow the bit wires)
+  s.n_constraints = 3 + 2 * (S_BITS + 1) + 2 * (uint64_t)depth + hashes * 730;
+  return s;
+}
+
+// One lane per request, as k_withdraw_core<false>: the (6 + depth) MultiMiMC7 gadgets run through ONE inlined permutation body (rolled
+// loops over gadgets, the two permutations of a gadget, and the 91 rounds), no device-function calls; Montgomery values are stored
+// and k_wires_from_mont converts them afterwards, in parallel.  `change` and the 256 bit wires come from the record's integer words
+// (the records are checked first: amount_out <= amount < 2^128, so the difference does not borrow).
+__global__ void __launch_bounds__(64) k_split_core(const uint32_t* __restrict__ consts, const uint8_t* __restrict__ inputs, int depth,
+                                                  size_t n_wires, uint32_t first_bit_wire, size_t n, uint8_t* __restrict__ out) {
+  OG_FILLER_PRIO();
+  const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= n) return;
+  const uint8_t* in = inputs + g * (size_t)(S_REC + depth) * 32;
+  WireWriterT<false> ww{out + g * n_wires * 32, first_bit_wire};
+  const Fr nullifier = fe_to_mont(fe_load<FrParams>(in));
+  const Fr secret = fe_to_mont(fe_load<FrParams>(in + 32));
+  const Fr amount = fe_to_mont(fe_load<FrParams>(in + 64));
+  const Fr recipient = fe_to_mont(fe_load<FrParams>(in + 96));
+  const Fr amount_out = fe_to_mont(fe_load<FrParams>(in + 128));
+  const uint64_t index = *reinterpret_cast<const uint64_t*>(in + 160);
+  const Fr token = fe_to_mont(fe_load<FrParams>(in + 192));
+  const Fr chain_id = fe_to_mont(fe_load<FrParams>(in + 224));
+  const Fr change_commitment = fe_to_mont(fe_load<FrParams>(in + 256));
+  // change = amount - amount_out on the integer words
+  const uint64_t a_lo = *reinterpret_cast<const uint64_t*>(in + 64), a_hi = *reinterpret_cast<const uint64_t*>(in + 72);
+  const uint64_t o_lo = *reinterpret_cast<const uint64_t*>(in + 128), o_hi = *reinterpret_cast<const uint64_t*>(in + 136);
+  const uint64_t c_lo = a_lo - o_lo, c_hi = a_hi - o_hi - (a_lo < o_lo ? 1u : 0u);
+  const uint32_t cw[8] = {(uint32_t)c_lo, (uint32_t)(c_lo >> 32), (uint32_t)c_hi, (uint32_t)(c_hi >> 32), 0u, 0u, 0u, 0u};
+  const Fr change = fe_to_mont(fe_from_words<FrParams>(cw));
+  ww.put(0, Fr::one());
+  ww.put(3, recipient);
+  ww.put(4, amount_out);
+  ww.put(5, token);
+  ww.put(6, chain_id);
+  ww.put(8, nullifier);
+  ww.put(9, secret);
+  ww.put(10, amount);
+  ww.put(11, change_commitment);
+  ww.put(12, change);
+  for (int l = 0; l < depth; l++) {
+    ww.put(13 + l, fe_to_mont(fe_load<FrParams>(in + (size_t)(S_REC + l) * 32)));
+    ww.put(13 + depth + l, ((index >> l) & 1) ? Fr::one() : Fr::zero());
+  }
+  ww.put(13 + 2 * depth, fe_sqr(recipient));
+  ww.put(14 + 2 * depth, fe_sqr(chain_id));
+#pragma unroll 1
+  for (int v = 0; v < 2; v++) {  // the bits of amount_out, then of change, LSB first
+    const uint64_t lo = v ? c_lo : o_lo, hi = v ? c_hi : o_hi;
+#pragma unroll 1
+    for (int i = 0; i < S_BITS; i++) ww.push((((i < 64 ? lo : hi) >> (i & 63)) & 1) ? Fr::one() : Fr::zero());
+  }
+  // gadget 0: inner = H(nullifier, secret); 1: asset = H(amount, token); 2: leaf = H(inner, asset); 3: nullifier_hash =
+  // H(nullifier, 0) -> wire 2; 4 + l: level l of the path (wire 1 = root for the last level); 4 + depth: change_asset =
+  // H(change, token); 5 + depth: change_leaf = H(change_commitment, change_asset) -> wire 7
+  Fr cur = Fr::zero(), inner = Fr::zero();
+#pragma unroll 1
+  for (int h = 0; h < 6 + depth; h++) {
+    Fr l_in, r_in;
+    int out_wire = -1;
+    if (h == 0) {
+      l_in = nullifier; r_in = secret;
+    } else if (h == 1) {
+      l_in = amount; r_in = token;
+    } else if (h == 2) {
+      l_in = inner; r_in = cur;
+    } else if (h == 3) {
+      l_in = nullifier; r_in = Fr::zero(); out_wire = 2;
+    } else if (h < 4 + depth) {
+      const int lvl = h - 4;
+      const Fr sib = fe_to_mont(fe_load<FrParams>(in + (size_t)(S_REC + lvl) * 32));
+      const bool right_child = (index >> lvl) & 1;
+      l_in = right_child ? sib : cur;
+      r_in = right_child ? cur : sib;
+      ww.push(l_in);  // the `left` selector wire
+      if (lvl == depth - 1) out_wire = 1;
+    } else if (h == 4 + depth) {
+      l_in = change; r_in = token;
+    } else {
+      l_in = change_commitment; r_in = cur; out_wire = 7;
+    }
+    // MultiMiMC7([l, r], key 0): k1 = l + E_0(l); out = 2 k1 + r + E_k1(r), with E_k(x) = x_91 + k
+    Fr k = Fr::zero(), x = l_in, k1 = Fr::zero();
+#pragma unroll 1
+    for (int p = 0; p < 2; p++) {
+#pragma unroll 1
+      for (int i = 0; i < MIMC7_ROUNDS; i++) {
+        const Fr t = fe_add3_weak(x, k, mimc7_const(consts, i));  // < 5N, only ever multiplied
+        const Fr t2 = fe_sqr(t);
+        const Fr t4 = fe_sqr(t2);
+        const Fr t6 = fe_mul(t4, t2);
+        x = fe_mul(t6, t);
+        ww.push(t2);
+        ww.push(t4);
+        ww.push(t6);
+        ww.push(x);
+      }
+      if (p == 0) {
+        k1 = fe_add(l_in, x);
+        ww.push(k1);
+        k = k1;
+        x = r_in;
+      }
+    }
+    const Fr hout = fe_add(fe_add(fe_dbl(k1), r_in), x);
+    if (out_wire < 0) ww.push(hout); else ww.put((uint32_t)out_wire, hout);
+    if (h == 0) inner = hout;
+    if (h != 3) cur = hout;
+  }
+}
+
+// Boundary check of the split records, one lane per field as k_check_records: every field canonical (< r), the index inside the
+// tree, amount < 2^128 (field 2), amount_out < 2^128 and amount_out <= amount (field 4) -- compared on the integer words, not in the
+// field.  bad[g] = lowest offending field of record g (the caller initialises it to 0xffffffff): 0 nullifier, 1 secret, 2 amount,
+// 3 recipient, 4 amount_out, 5 index, 6 token, 7 chain_id, 8 change_commitment, 9 + l sibling l.
+__global__ void __launch_bounds__(64) k_check_split_records(const uint8_t* __restrict__ inputs, int depth, size_t n, uint32_t* __restrict__ bad) {
+  OG_FILLER_PRIO();
+  const size_t g = blockIdx.y;
+  const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= n || f >= (uint32_t)(S_REC + depth)) return;
+  const uint8_t* rec = inputs + g * (size_t)(S_REC + depth) * 32;
+  const uint8_t* p = rec + (size_t)f * 32;
+  bool ok = fe_lt_modulus(fe_load<FrParams>(p));
+  const uint32_t* w = reinterpret_cast<const uint32_t*>(p);
+  if (f == 2 || f == 4) ok = ok && (w[4] | w[5] | w[6] | w[7]) == 0;
+  if (f == 4) {  // amount_out <= amount, most significant word first
+    const uint32_t* a = reinterpret_cast<const uint32_t*>(rec + 64);
+    bool gt = false, decided = false;
+    for (int i = 7; i >= 0; i--) {
+      if (!decided && w[i] != a[i]) { gt = w[i] > a[i]; decided = true; }
+    }
+    ok = ok && !gt;
+  }
+  if (f == 5) {  // index
+    ok = ok && (w[2] | w[3] | w[4] | w[5] | w[6] | w[7]) == 0;
+    const uint64_t idx = (uint64_t)w[0] | ((uint64_t)w[1] << 32);
+    ok = ok && (depth >= 64 || (idx >> depth) == 0);
+  }
+  if (!ok) atomicMin(&bad[g], f);
+}
+
+int split_shape_query(int depth, uint64_t out[3]) {
+  OG_REQUIRE(depth >= 1 && depth <= 64, "split: depth must be 1..64");
+  const SplitShape s = split_shape(depth);
+  out[0] = s.n_wires; out[1] = s.n_constraints; out[2] = S_PUB;
+  return OG_OK;
+}
+
+// OG_ERR_INVALID names the first malformed record and its lowest offending field (`base` = index of record 0 in the caller's
+// batch); blocking
+int split_records_ok(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, size_t base) {
+  OG_REQUIRE(depth >= 1 && depth <= 64, "split: depth must be 1..64");
+  OG_REQUIRE(n <= 65535, "split: at most 65535 records per call");  // (the record index is grid.y)
+  if (n == 0) return OG_OK;
+  uint32_t* bad_d = nullptr;
+  OG_TRY(arena_get(ctx, "sp.bad", n * 4, (void**)&bad_d));
+  OG_HIP(hipMemsetAsync(bad_d, 0xff, n * 4, ctx->stream));
+  hipLaunchKernelGGL(k_check_split_records, dim3(grid_for(S_REC + depth, 64), (unsigned)n), dim3(64), 0, ctx->stream, inputs_d, depth, n, bad_d);
+  OG_HIP(hipGetLastError());
+  std::vector<uint32_t> b(n);
+  OG_HIP(hipMemcpyAsync(b.data(), bad_d, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+  OG_HIP(hipStreamSynchronize(ctx->stream));
+  static const char* names[S_REC] = {"nullifier", "secret", "amount", "recipient", "amount_out", "index", "token", "chain_id", "change_commitment"};
+  for (size_t g = 0; g < n; g++)
+    if (b[g] != 0xffffffffu) {
+      const std::string name = b[g] < (uint32_t)S_REC ? std::string(names[b[g]]) : "sibling " + std::to_string(b[g] - S_REC);
+      set_error("og_split: input record " + std::to_string(base + g) + ": field " + std::to_string(b[g]) + " (" + name +
+                ") is not a valid value (>= r, an index outside the tree, an amount >= 2^128, or amount_out > amount)");
+      return OG_ERR_INVALID;
+    }
+  return OG_OK;
+}
+
+// records (checked: split_records_ok) -> n x n_wires x 32 B canonical
+int split_witness(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, uint8_t* out_d) {
+  OG_REQUIRE(depth >= 1 && depth <= 64, "split: depth must be 1..64");
+  OG_REQUIRE(n <= 65535, "split: at most 65535 witnesses per call");
+  if (n == 0) return OG_OK;
+  const SplitShape s = split_shape(depth);
+  ProfScope ps(ctx, PROF_WITNESS, (double)n);
+  hipLaunchKernelGGL(k_split_core, dim3(grid_for(n, 64)), dim3(64), 0, ctx->stream, (const uint32_t*)ctx->mimc_consts_d, inputs_d, depth,
+                     (size_t)s.n_wires, (uint32_t)s.first_bit_wire, n, out_d);
+  OG_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_wires_from_mont, dim3(grid_for(s.n_wires, 256), (unsigned)n), dim3(256), 0, ctx->stream, out_d, (size_t)s.n_wires,
+                     (uint32_t)s.n_wires, 1u);
   OG_HIP(hipGetLastError());
   return OG_OK;
 }
