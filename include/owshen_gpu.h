@@ -387,6 +387,47 @@ int og_split_witness_d(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n
 int og_split_prove_batch_d(og_ctx* ctx, const og_pk* pk, int depth, const uint8_t* inputs_d, size_t n, const uint8_t* rs,
                            uint8_t* proofs_out, uint8_t* public_out);
 
+/* ---- join statement: merge two notes into one (the inverse of split) ---------------------------------------------------------------
+ * "I know two different notes under `root`, worth `amount_a` and `amount_b` of the same token.  Both are spent.  Their sum goes
+ * into the new leaf `out_leaf`."  Nothing leaves the pool.  (No reference counterpart: the snapshot has no circuit.)
+ * public (n_pub = 5, verifier order): root, nullifier_hash_a, nullifier_hash_b, chain_id, out_leaf
+ * private: per note nullifier, secret, amount and a depth-`depth` MiMC7 Merkle path; token (ONE wire shared by all three asset
+ * hashes; private because nothing is paid out); out_commitment; sum; nh_diff_inv.  With H = MultiMiMC7 2-to-1, for x in {a, b}:
+ *   leaf_x = H(H(nullifier_x, secret_x), H(amount_x, token)) is under root at `index_x`;  nullifier_hash_x = H(nullifier_x, 0);
+ *   the last level of BOTH walks has the root wire as its output -- that is what says "the same root", there is no equality row;
+ *   amount_a + amount_b = sum with amount_a, amount_b and sum each < 2^128 (a 128-bit decomposition each: the two input checks
+ *   keep the sum below 2^129 < r whatever a ledger appended, the check on sum keeps the new note spendable by split);
+ *   (nullifier_hash_a - nullifier_hash_b) nh_diff_inv = 1 -- the same note counted twice is unprovable, whatever the order in
+ *   which a ledger marks nullifiers;  out_leaf = H(out_commitment, H(sum, token)), the leaf shape of a deposit;  chain_id is bound
+ *   by its square.
+ * out_commitment is an unconstrained private input, c' = H(nullifier', secret') formed off-circuit, as in split.  The ledger's
+ * part, in order: og_verify the proof, check that root is known, check that BOTH nullifier hashes are unspent, mark both, append
+ * out_leaf (og_mimc7_append_d).
+ * Wire and row order: tests/join_spec.py (the spec), og_join_r1cs / owshen_amd/circuit.py join_r1cs (the R1CS):
+ *   n_wires = 396 + 6 depth + (10 + 2 depth) 730, n_constraints = 390 + 4 depth + (10 + 2 depth) 730 (54 608 / 54 538 at depth 32:
+ *   74 hashes, domain 2^16).  depth 1..64; n <= 65 535 per og_join_witness_d call.  shape[0..2] = n_wires, n_constraints, n_pub.
+ * inputs_d: n records of (11 + 2 depth) x 32 B canonical little-endian:
+ *   nullifier_a | secret_a | amount_a | index_a (u64, low bytes) | nullifier_b | secret_b | amount_b | index_b | token | chain_id
+ *   | out_commitment | siblings_a[depth] | siblings_b[depth]
+ * witness_out_d: n x n_wires x 32 B.  og_join_prove_batch_d: records -> proofs (rs: n x 64 B host, proofs_out: n x 256 B host,
+ * public_out (host, may be NULL): n x 5 x 32 B in verifier order -- root, both nullifier hashes and out_leaf are COMPUTED by the
+ * witness generator).  Same bytes as og_join_witness_d + og_prove_batch_d.  The key must have this shape's wire count and n_pub.
+ * OG_ERR_INVALID, before anything is proved: a malformed record; og_last_error names the record and its lowest offending field
+ * ("input record 3: field 6 (amount_b)"; 0 nullifier_a, 1 secret_a, 2 amount_a, 3 index_a, 4 nullifier_b, 5 secret_b, 6 amount_b,
+ * 7 index_b, 8 token, 9 chain_id, 10 out_commitment, 11 + l sibling a of level l, 11 + depth + l sibling b of level l): any
+ * field >= r; an index that does not fit the tree (3 or 7); field 2 if amount_a >= 2^128; field 6 if amount_b >= 2^128 or
+ * amount_a + amount_b >= 2^128 (compared as integers); field 4 if nullifier_b == nullifier_a (nh_diff_inv would not exist).
+ * Two notes whose walks end in DIFFERENT roots cannot be seen at that boundary: og_join_witness_d fills the root wire from note
+ * a's walk, and og_join_prove_batch_d answers OG_ERR_UNSATISFIED through the prover's row check.
+ * The witness generator gives every request two lanes, one per note, through one rolled permutation body.  Out of scope for this
+ * statement: the lane-pair round (t^4 beside t^3), the wave-per-request walk, the wave-wide (w9) form and host chains
+ * (og_set_host_chains does not change how its witnesses are generated); there is no submit / job form, no multi-GPU form and no
+ * window-sharded form of the call. */
+int og_join_shape(int depth, uint64_t shape[3]);
+int og_join_witness_d(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, uint8_t* witness_out_d);
+int og_join_prove_batch_d(og_ctx* ctx, const og_pk* pk, int depth, const uint8_t* inputs_d, size_t n, const uint8_t* rs,
+                          uint8_t* proofs_out, uint8_t* public_out);
+
 /* The same call in two halves, for a host that keeps requests flowing (a sequencer proving batch after batch): submit
  * enqueues ALL the work of the batch on the ctx's streams and returns; og_job_wait blocks until it is done, fills
  * proofs_out / public_out (which, like rs, must stay valid until then) and frees the job.  At most two calls may be in
@@ -459,6 +500,8 @@ int og_withdraw_r1cs(og_ctx* ctx, int depth, uint64_t n_pad3, uint64_t n_pad2, i
 int og_deposit_r1cs(og_ctx* ctx, og_r1cs** out);
 /* the statement of og_split_witness_d at this depth (wire and row order: tests/split_spec.py) */
 int og_split_r1cs(og_ctx* ctx, int depth, og_r1cs** out);
+/* the statement of og_join_witness_d at this depth (wire and row order: tests/join_spec.py) */
+int og_join_r1cs(og_ctx* ctx, int depth, og_r1cs** out);
 int og_r1cs_from_csr(uint64_t n_wires, uint64_t n_pub, uint64_t n_constraints, const uint32_t* const ptr[3],
                      const uint32_t* const col[3], const uint8_t* const val[3], og_r1cs** out);
 void og_r1cs_free(og_r1cs* r1cs);

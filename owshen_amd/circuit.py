@@ -20,8 +20,8 @@ points, Fr NTT 2^17"): n_wires = 2^18, domain 2^17.
 Only index arrays and constants are produced here (numpy); there is no host-side witness
 generator -- the witness comes from og_withdraw_witness_d.
 
-The deposit and the split statement (oracle/py/deposit.py, tests/split_spec.py are their specs) follow further down, built with
-the same gadget builder.
+The deposit, the split and the join statement (oracle/py/deposit.py, tests/split_spec.py, tests/join_spec.py are their specs)
+follow further down, built with the same gadget builder.
 """
 import ctypes as C
 
@@ -485,6 +485,118 @@ def split_change_leaf(change_commitment, change, token, ctx):
         return ctx.to_device(np.frombuffer(int(v).to_bytes(32, "little"), dtype=np.uint8).reshape(1, 32).copy())
 
     leaf = ctx.mimc7_hash2(dev(change_commitment), ctx.mimc7_hash2(dev(change), dev(token)))
+    return int.from_bytes(ctx.to_host(leaf).tobytes(), "little")
+
+
+# ---- the join statement (tests/join_spec.py is the spec; witness.hip k_join_core fills the wires) -----------------------------------
+# public: root, nullifier_hash_a, nullifier_hash_b, chain_id, out_leaf; private: per note nullifier, secret, amount and a path; token,
+# out_commitment, sum, nh_diff_inv.  Both notes lie under root (both walks end in wire 1), amount_a + amount_b = sum with all three
+# below 2^128 by a bit decomposition, (nullifier_hash_a - nullifier_hash_b) nh_diff_inv = 1, out_leaf = H(out_commitment,
+# H(sum, token)).  The inverse of split: two notes are spent, one note worth their sum is created, nothing leaves the pool.
+J_N_PUB, J_N_REC, J_N_BITS = 5, 11, 128
+JW_ROOT, JW_NH_A, JW_NH_B, JW_CHAIN, JW_OUT_LEAF = range(1, 6)
+JW_NOTE_A, JW_NOTE_B = 6, 9                    # a note: nullifier, secret, amount
+JW_TOKEN, JW_OUT_COMMITMENT, JW_SUM, JW_NH_DIFF_INV = range(12, 16)
+
+
+def join_shape(depth):
+    """(n_wires, n_constraints): (54608, 54538) at depth 32"""
+    return 396 + 6 * depth + (10 + 2 * depth) * 730, 390 + 4 * depth + (10 + 2 * depth) * 730
+
+
+def join_r1cs(mimc7_constants, depth=32):
+    """the join statement as an R1CS (the same gadget builder as the withdraw circuit); no padding gates"""
+    assert depth >= 1 and len(mimc7_constants) == N_ROUNDS
+    n_wires, n_constraints = join_shape(depth)
+    bld = _Builder([int(c) for c in mimc7_constants])
+    bld.alloc(1 + J_N_PUB + 10)
+    w_sib = bld.alloc(2 * depth)
+    w_bit = bld.alloc(2 * depth)
+    w_csq = bld.alloc()
+    w_bits = bld.alloc(3 * J_N_BITS)
+    bld.enforce([(JW_CHAIN, 1)], [(JW_CHAIN, 1)], [(w_csq, 1)])
+    bld.enforce([(JW_NOTE_A + 2, 1), (JW_NOTE_B + 2, 1)], [(0, 1)], [(JW_SUM, 1)])
+    bld.enforce([(JW_NH_A, 1), (JW_NH_B, R - 1)], [(JW_NH_DIFF_INV, 1)], [(0, 1)])      # two different notes
+    for v, value in enumerate((JW_NOTE_A + 2, JW_NOTE_B + 2, JW_SUM)):   # value < 2^128: boolean bits, then the recomposition
+        bits = w_bits + v * J_N_BITS
+        for i in range(J_N_BITS):
+            bld.enforce([(bits + i, 1)], [(bits + i, 1), (0, R - 1)], [])
+        bld.enforce([(bits + i, 1 << i) for i in range(J_N_BITS)], [(0, 1)], [(value, 1)])
+    for x, (note, w_nh) in enumerate(((JW_NOTE_A, JW_NH_A), (JW_NOTE_B, JW_NH_B))):   # both walks end in wire 1
+        inner = bld.hash2([(note, 1)], [(note + 1, 1)])
+        asset = bld.hash2([(note + 2, 1)], [(JW_TOKEN, 1)])
+        cur = bld.hash2([(inner, 1)], [(asset, 1)])
+        bld.hash2([(note, 1)], [], out_wire=w_nh)
+        for l in range(depth):
+            b, s = w_bit + x * depth + l, w_sib + x * depth + l
+            bld.enforce([(b, 1)], [(b, 1), (0, R - 1)], [])
+            left = bld.alloc()
+            bld.enforce([(b, 1)], [(s, 1), (cur, R - 1)], [(left, 1), (cur, R - 1)])
+            right = [(s, 1), (cur, 1), (left, R - 1)]
+            cur = bld.hash2([(left, 1)], right, out_wire=JW_ROOT if l == depth - 1 else None)
+    out_asset = bld.hash2([(JW_SUM, 1)], [(JW_TOKEN, 1)])
+    bld.hash2([(JW_OUT_COMMITMENT, 1)], [(out_asset, 1)], out_wire=JW_OUT_LEAF)
+    assert bld.next == n_wires
+    none = np.zeros(0, dtype=np.int64)
+    pad = (none, none, none)
+    r1cs = R1CS(n_wires, J_N_PUB, _csr(bld.a, *pad, n_wires), _csr(bld.b, *pad, n_wires), _csr(bld.c, *pad, n_wires))
+    assert r1cs.n_constraints == n_constraints
+    return r1cs
+
+
+def join_r1cs_native(ctx, depth=32):
+    """the same statement built by the library (og_join_r1cs: what a Rust host calls)"""
+    h = C.c_void_p()
+    ctx._check(ctx._lib.og_join_r1cs(ctx._h, depth, C.byref(h)))
+    return _r1cs_from_handle(ctx, h)
+
+
+def pack_join_inputs(nullifier_a, secret_a, amount_a, index_a, siblings_a, nullifier_b, secret_b, amount_b, index_b, siblings_b, token=0,
+                     chain_id=0, out_commitment=0):
+    """one join record: (11 + 2 depth) x 32 B (include/owshen_gpu.h):
+    nullifier_a | secret_a | amount_a | index_a | nullifier_b | secret_b | amount_b | index_b | token | chain_id | out_commitment
+    | siblings_a[depth] | siblings_b[depth]"""
+    assert len(siblings_a) == len(siblings_b)
+    vals = [nullifier_a, secret_a, amount_a, index_a, nullifier_b, secret_b, amount_b, index_b, token, chain_id, out_commitment]
+    vals += list(siblings_a) + list(siblings_b)
+    return np.frombuffer(b"".join(int(v).to_bytes(32, "little") for v in vals), dtype=np.uint8).reshape(-1, 32).copy()
+
+
+def join_witness(ctx, depth, inputs_d):
+    """inputs_d: device uint8 [n, 11 + 2 depth, 32] -> device uint8 [n, n_wires, 32] (og_join_witness_d)"""
+    n = inputs_d.shape[0]
+    assert tuple(inputs_d.shape[1:]) == (J_N_REC + 2 * depth, 32)
+    shp = (C.c_uint64 * 3)()
+    ctx._check(ctx._lib.og_join_shape(depth, shp))
+    assert (int(shp[0]), int(shp[1]), int(shp[2])) == (*join_shape(depth), J_N_PUB), "circuit.py and witness.hip disagree on the join shape"
+    out = ctx.empty(n, int(shp[0]), 32)
+    ctx._pre()
+    ctx._check(ctx._lib.og_join_witness_d(ctx._h, depth, ctx.ptr(inputs_d), n, ctx.ptr(out)))
+    return out
+
+
+def join_prove(ctx, pk, depth, inputs_d, rs, return_public=False):
+    """inputs_d: device uint8 [n, 11 + 2 depth, 32]; rs: (r, s) pairs or uint8 [n, 64] -> np.uint8 [n, 256] (og_join_prove_batch_d);
+    return_public: also (root, nullifier_hash_a, nullifier_hash_b, chain_id, out_leaf) of every proof, np.uint8 [n, 5, 32]"""
+    n = inputs_d.shape[0]
+    assert tuple(inputs_d.shape[1:]) == (J_N_REC + 2 * depth, 32)
+    rsb = pk._rs_bytes(rs)
+    assert rsb.shape[0] == n
+    out = np.zeros((n, 256), dtype=np.uint8)
+    pub = np.zeros((n, J_N_PUB, 32), dtype=np.uint8) if return_public else None
+    ctx._pre()
+    ctx._check(ctx._lib.og_join_prove_batch_d(ctx._h, pk._h, depth, ctx.ptr(inputs_d), n, rsb.ctypes.data_as(C.c_void_p),
+                                              out.ctypes.data_as(C.c_void_p), pub.ctypes.data_as(C.c_void_p) if return_public else None))
+    return (out, pub) if return_public else out
+
+
+def join_out_leaf(out_commitment, total, token, ctx):
+    """the ledger's and the receiver's side of a join: the leaf of the joined note, H(out_commitment, H(sum, token)), through
+    og_mimc7_hash2_d (the value of public input 5; what og_mimc7_append_d appends).  Returns an int."""
+    def dev(v):
+        return ctx.to_device(np.frombuffer(int(v).to_bytes(32, "little"), dtype=np.uint8).reshape(1, 32).copy())
+
+    leaf = ctx.mimc7_hash2(dev(out_commitment), ctx.mimc7_hash2(dev(total), dev(token)))
     return int.from_bytes(ctx.to_host(leaf).tobytes(), "little")
 
 

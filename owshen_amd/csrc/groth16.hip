@@ -1483,25 +1483,21 @@ int deposit_prove_batch(og_ctx* ctx, const og_pk* pk, const uint8_t* inputs_d, s
   return OG_OK;
 }
 
-// split records -> proofs of the split statement (witness.hip, tests/split_spec.py): per slab -- sized as the small-circuit branch
-// of withdraw_prove_batch -- check the records, generate the witnesses in one launch, then the ordinary batched prover
-int split_shape_query(int, uint64_t out[3]);
-int split_records_ok(og_ctx*, int, const uint8_t*, size_t, size_t);
-int split_witness(og_ctx*, int, const uint8_t*, size_t, uint8_t*);
-int split_prove_batch(og_ctx* ctx, const og_pk* pk, int depth, const uint8_t* inputs_d, size_t n, const uint8_t* rs, uint8_t* proofs,
-                      uint8_t* pub_out) {
-  uint64_t shp[3];
-  OG_TRY(split_shape_query(depth, shp));
-  OG_REQUIRE(shp[0] == pk->m && shp[2] == pk->n_pub, "og_split_prove_batch_d: the key is not for this split-statement shape");
-  const size_t rec = (size_t)(9 + depth) * 32;
+// records -> proofs for the statements whose witnesses depend on a depth alone (split, join): per slab -- sized as the small-circuit
+// branch of withdraw_prove_batch -- check the records, generate the witnesses in one launch, then the ordinary batched prover.
+// `rec`: bytes per record; records_ok / witness: the statement's boundary check and its witness launch (witness.hip)
+typedef int (*records_ok_fn)(og_ctx*, int, const uint8_t*, size_t, size_t);
+typedef int (*witness_fn)(og_ctx*, int, const uint8_t*, size_t, uint8_t*);
+static int records_prove_batch(og_ctx* ctx, const og_pk* pk, int depth, size_t rec, records_ok_fn records_ok, witness_fn witness,
+                               const uint8_t* inputs_d, size_t n, const uint8_t* rs, uint8_t* proofs, uint8_t* pub_out) {
   const size_t slab = std::min<size_t>(65535, std::max<size_t>(1, std::min<size_t>(n, ((size_t)16 << 30) / (pk->m * 32))));
   uint8_t* z_d = nullptr;
   OG_TRY(arena_get(ctx, "g16.zall", slab * pk->m * 32, (void**)&z_d));
   for (size_t g0 = 0; g0 < n;) {
     const size_t cnt = std::min(slab, n - g0);
-    OG_TRY(split_records_ok(ctx, depth, inputs_d + g0 * rec, cnt, g0));
-    OG_TRY(split_witness(ctx, depth, inputs_d + g0 * rec, cnt, z_d));
-    OG_HIP(hipStreamSynchronize(ctx->stream));  // both lanes read the slab
+    OG_TRY(records_ok(ctx, depth, inputs_d + g0 * rec, cnt, g0));
+    OG_TRY(witness(ctx, depth, inputs_d + g0 * rec, cnt, z_d));
+    OG_HIP(hipStreamSynchronize(ctx->stream));  // both streams of the prover read the slab
     size_t bad = 0;
     int r = prove_batch_impl(ctx, pk, z_d, cnt, rs + g0 * 64, proofs + g0 * 256, &bad, nullptr, pub_out ? pub_out + g0 * pk->n_pub * 32 : nullptr, true);
     if (r == OG_ERR_UNSATISFIED)
@@ -1510,6 +1506,31 @@ int split_prove_batch(og_ctx* ctx, const og_pk* pk, int depth, const uint8_t* in
     g0 += cnt;
   }
   return OG_OK;
+}
+
+// split records -> proofs of the split statement (witness.hip, tests/split_spec.py)
+int split_shape_query(int, uint64_t out[3]);
+int split_records_ok(og_ctx*, int, const uint8_t*, size_t, size_t);
+int split_witness(og_ctx*, int, const uint8_t*, size_t, uint8_t*);
+int split_prove_batch(og_ctx* ctx, const og_pk* pk, int depth, const uint8_t* inputs_d, size_t n, const uint8_t* rs, uint8_t* proofs,
+                      uint8_t* pub_out) {
+  uint64_t shp[3];
+  OG_TRY(split_shape_query(depth, shp));
+  OG_REQUIRE(shp[0] == pk->m && shp[2] == pk->n_pub, "og_split_prove_batch_d: the key is not for this split-statement shape");
+  return records_prove_batch(ctx, pk, depth, (size_t)(9 + depth) * 32, split_records_ok, split_witness, inputs_d, n, rs, proofs, pub_out);
+}
+
+// join records -> proofs of the join statement (witness.hip, tests/join_spec.py; two lanes per request in the witness launch).  The
+// prover's row check is what answers OG_ERR_UNSATISFIED for two notes under different roots: the witness carries note a's root in wire 1
+int join_shape_query(int, uint64_t out[3]);
+int join_records_ok(og_ctx*, int, const uint8_t*, size_t, size_t);
+int join_witness(og_ctx*, int, const uint8_t*, size_t, uint8_t*);
+int join_prove_batch(og_ctx* ctx, const og_pk* pk, int depth, const uint8_t* inputs_d, size_t n, const uint8_t* rs, uint8_t* proofs,
+                     uint8_t* pub_out) {
+  uint64_t shp[3];
+  OG_TRY(join_shape_query(depth, shp));
+  OG_REQUIRE(shp[0] == pk->m && shp[2] == pk->n_pub, "og_join_prove_batch_d: the key is not for this join-statement shape");
+  return records_prove_batch(ctx, pk, depth, (size_t)(11 + 2 * depth) * 32, join_records_ok, join_witness, inputs_d, n, rs, proofs, pub_out);
 }
 
 // ---- window-sharded proving: the two halves (WinShard above) -------------------------------------------------------------------

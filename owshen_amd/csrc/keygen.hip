@@ -8,8 +8,8 @@
 //
 //   og_withdraw_r1cs   constraint rows of the depth-D MiMC7 Merkle withdraw circuit (+ synthetic padding gates, + the two
 //                      optional density rows), CSR, canonical 32-byte coefficients
-//   og_deposit_r1cs / og_split_r1cs   the deposit and the split statement, with the same builder (oracle/py/deposit.py,
-//                      tests/split_spec.py)
+//   og_deposit_r1cs / og_split_r1cs / og_join_r1cs   the deposit, the split and the join statement, with the same builder
+//                      (oracle/py/deposit.py, tests/split_spec.py, tests/join_spec.py)
 //   og_r1cs_from_csr   any R1CS the caller built
 //   og_setup           Groth16 key generation from (tau, alpha, beta, gamma, delta): Lagrange evaluations, the three
 //                      transposed sparse products, the query scalars and ~3 m + d fixed-base multiplications, all on the
@@ -253,6 +253,57 @@ int split_r1cs_build(const uint8_t* mimc_consts, int depth, og_r1cs* r) {
   return OG_OK;
 }
 
+// the join statement (tests/join_spec.py; witness.hip k_join_core): two notes under one root into one note worth their sum
+int join_shape_query(int depth, uint64_t out[3]);
+int join_r1cs_build(const uint8_t* mimc_consts, int depth, og_r1cs* r) {
+  uint64_t shp[3];
+  OG_TRY(join_shape_query(depth, shp));
+  r->n_wires = shp[0];
+  r->n_pub = shp[2];
+  for (int k = 0; k < 3; k++) r->ptr[k].assign(1, 0u);
+  R1csBuilder b{r, 0, mimc_consts};
+  const HFr m1 = hfr_neg_one();
+  constexpr uint32_t JW_ROOT = 1, JW_NH_A = 2, JW_NH_B = 3, JW_CHAIN = 4, JW_OUT_LEAF = 5, JW_NOTE_A = 6, JW_NOTE_B = 9, JW_TOKEN = 12,
+                     JW_OUT_COMMITMENT = 13, JW_SUM = 14, JW_NH_DIFF_INV = 15;  // a note: nullifier, secret, amount
+  OG_REQUIRE(r->n_pub == 5, "og_join_r1cs: the statement has five public inputs");
+  b.alloc(1 + 5 + 10);
+  const uint32_t w_sib = b.alloc(2 * depth), w_bit = b.alloc(2 * depth), w_csq = b.alloc();
+  const uint32_t w_bits = b.alloc(3 * 128);
+  b.enforce(R1csBuilder::one(JW_CHAIN), R1csBuilder::one(JW_CHAIN), R1csBuilder::one(w_csq));
+  b.enforce(LC{{JW_NOTE_A + 2, hfr_u64(1)}, {JW_NOTE_B + 2, hfr_u64(1)}}, R1csBuilder::one(0), R1csBuilder::one(JW_SUM));  // amount_a + amount_b = sum
+  b.enforce(LC{{JW_NH_A, hfr_u64(1)}, {JW_NH_B, m1}}, R1csBuilder::one(JW_NH_DIFF_INV), R1csBuilder::one(0));  // two different notes
+  for (int v = 0; v < 3; v++) {  // amount_a, amount_b, sum: 128 boolean rows and the recomposition, so that each is < 2^128
+    const uint32_t bits = w_bits + 128 * v;
+    LC sum;
+    for (uint32_t i = 0; i < 128; i++) {
+      b.enforce(R1csBuilder::one(bits + i), LC{{bits + i, hfr_u64(1)}, {0u, m1}}, LC{});
+      HFr p2 = {{0, 0, 0, 0}};
+      p2.v[i >> 6] = 1ull << (i & 63);
+      sum.push_back({bits + i, p2});
+    }
+    b.enforce(sum, R1csBuilder::one(0), R1csBuilder::one(v == 0 ? JW_NOTE_A + 2 : v == 1 ? JW_NOTE_B + 2 : JW_SUM));
+  }
+  for (int x = 0; x < 2; x++) {  // the walk of note a, then of note b: both end in wire 1
+    const uint32_t nt = x ? JW_NOTE_B : JW_NOTE_A;
+    const uint32_t inner = b.hash2(R1csBuilder::one(nt), R1csBuilder::one(nt + 1));
+    const uint32_t asset = b.hash2(R1csBuilder::one(nt + 2), R1csBuilder::one(JW_TOKEN));
+    uint32_t cur = b.hash2(R1csBuilder::one(inner), R1csBuilder::one(asset));
+    b.hash2(R1csBuilder::one(nt), LC{}, (int)(x ? JW_NH_B : JW_NH_A));
+    for (int l = 0; l < depth; l++) {
+      const uint32_t bit = w_bit + x * depth + l, s = w_sib + x * depth + l;
+      b.enforce(R1csBuilder::one(bit), LC{{bit, hfr_u64(1)}, {0u, m1}}, LC{});              // bit (bit - 1) = 0
+      const uint32_t left = b.alloc();
+      b.enforce(R1csBuilder::one(bit), LC{{s, hfr_u64(1)}, {cur, m1}}, LC{{left, hfr_u64(1)}, {cur, m1}});  // left = cur + bit (s - cur)
+      const LC right{{s, hfr_u64(1)}, {cur, hfr_u64(1)}, {left, m1}};
+      cur = b.hash2(R1csBuilder::one(left), right, l == depth - 1 ? (int)JW_ROOT : -1);
+    }
+  }
+  const uint32_t out_asset = b.hash2(R1csBuilder::one(JW_SUM), R1csBuilder::one(JW_TOKEN));
+  b.hash2(R1csBuilder::one(JW_OUT_COMMITMENT), R1csBuilder::one(out_asset), (int)JW_OUT_LEAF);
+  OG_REQUIRE(b.next == r->n_wires && r->n_constraints == shp[1], "og_join_r1cs: internal shape mismatch");
+  return OG_OK;
+}
+
 // ---- setup kernels ---------------------------------------------------------------------------------------------
 // toxic: tau | alpha | beta | gamma | delta (canonical).  out: 0 zt = tau^d - 1, 1 1/gamma, 2 1/delta, 3 zt/delta
 __global__ void k_setup_scalars(const uint8_t* __restrict__ toxic, int log_d, uint8_t* __restrict__ out) {
@@ -485,6 +536,21 @@ int og_split_r1cs(og_ctx* ctx, int depth, og_r1cs** out) {
     *out = nullptr;
     og_r1cs* r = new og_r1cs();
     int rc = split_r1cs_build(ctx->mimc_consts_canon, depth, r);
+    if (rc != OG_OK) {
+      delete r;
+      return rc;
+    }
+    *out = r;
+    return OG_OK;
+  });
+}
+
+int og_join_r1cs(og_ctx* ctx, int depth, og_r1cs** out) {
+  return guarded([&]() -> int {
+    OG_REQUIRE(ctx != nullptr && out != nullptr, "og_join_r1cs: null argument");
+    *out = nullptr;
+    og_r1cs* r = new og_r1cs();
+    int rc = join_r1cs_build(ctx->mimc_consts_canon, depth, r);
     if (rc != OG_OK) {
       delete r;
       return rc;

@@ -8,6 +8,7 @@
 //                    intermediate power (t^2, t^4, t^6, t^7 per round), the Merkle selectors
 //   k_withdraw_pad   one lane per padding unit (a 3-wire gate or a 64-gate chained segment)
 //   k_deposit_witness / k_split_core   the deposit and the split statement (further down), one lane per request
+//   k_join_core      the join statement (at the end): two lanes per request, one per note
 //
 // Input record per proof, (8 + depth) x 32 B canonical LE:
 //   nullifier | secret | amount | recipient | pad_seed | index (u64 in the low bytes) | token | chain_id | siblings[depth]
@@ -1096,6 +1097,261 @@ int split_witness(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, uin
   ProfScope ps(ctx, PROF_WITNESS, (double)n);
   hipLaunchKernelGGL(k_split_core, dim3(grid_for(n, 64)), dim3(64), 0, ctx->stream, (const uint32_t*)ctx->mimc_consts_d, inputs_d, depth,
                      (size_t)s.n_wires, (uint32_t)s.first_bit_wire, n, out_d);
+  OG_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_wires_from_mont, dim3(grid_for(s.n_wires, 256), (unsigned)n), dim3(256), 0, ctx->stream, out_d, (size_t)s.n_wires,
+                     (uint32_t)s.n_wires, 1u);
+  OG_HIP(hipGetLastError());
+  return OG_OK;
+}
+
+// ---- the join statement: merge two notes into one -----------------------------------------------------------------------------------
+// Spec: tests/join_spec.py.  public: root, nullifier_hash_a, nullifier_hash_b, chain_id, out_leaf (n_pub = 5); private: per note
+// nullifier, secret, amount and a path; token (ONE wire for all three asset hashes: nothing is paid out), out_commitment, sum,
+// nh_diff_inv.  For x in {a, b}: leaf_x = H(H(nullifier_x, secret_x), H(amount_x, token)) lies under root at index_x and
+// nullifier_hash_x = H(nullifier_x, 0); the last level of BOTH walks has wire 1 as its output wire, which is what says "the same
+// root"; amount_a + amount_b = sum with all three below 2^128 (a 128-bit decomposition each); (nullifier_hash_a - nullifier_hash_b)
+// nh_diff_inv = 1, so the same note cannot be counted twice; out_leaf = H(out_commitment, H(sum, token)), a leaf of the deposit shape,
+// which og_mimc7_append_d appends.  No reference counterpart (the snapshot has no circuit).
+// Input record per request, (11 + 2 depth) x 32 B canonical LE:
+//   nullifier_a | secret_a | amount_a | index_a (u64 in the low bytes) | nullifier_b | secret_b | amount_b | index_b | token | chain_id
+//   | out_commitment | siblings_a[depth] | siblings_b[depth]
+// Wires:
+//   0 one | 1 root | 2 nullifier_hash_a | 3 nullifier_hash_b | 4 chain_id | 5 out_leaf
+//   6 nullifier_a | 7 secret_a | 8 amount_a | 9 nullifier_b | 10 secret_b | 11 amount_b | 12 token | 13 out_commitment | 14 sum
+//   | 15 nh_diff_inv | 16.. siblings_a[D] | siblings_b[D] | index bits a[D] | index bits b[D] | chain_id^2 | amount_a bits[128] (LSB
+//   first) | amount_b bits[128] | sum bits[128] | the gadgets of note a: inner, asset, leaf, nullifier_hash (out = wire 2), level
+//   0..D-1 (the last one's out = wire 1) | the same gadgets of note b (outs = wire 3 and wire 1) | out_asset = H(sum, token),
+//   out_leaf = H(out_commitment, out_asset) (out = wire 5)
+// NOT built for this statement (as for split): the t^4 | t^3 lane-pair round, the wave-per-request walk, the w9 form, host chains.
+constexpr int J_PUB = 5;
+constexpr int J_REC = 11;  // fields of a join record before the siblings
+constexpr int J_BITS = 128;
+
+struct JoinShape {
+  uint64_t n_wires, n_constraints, first_bit_wire, note_gadget_wires;
+};
+
+static JoinShape join_shape(int depth) {
+  JoinShape s;
+  const uint64_t hashes = 10 + 2 * (uint64_t)depth;
+  s.first_bit_wire = 1 + J_PUB + 10 + 4 * (uint64_t)depth + 1;
+  s.note_gadget_wires = (4 + (uint64_t)depth) * 730 + depth - 2;  // a `left` per level; nullifier_hash and root are public wires
+  s.n_wires = s.first_bit_wire + 3 * J_BITS + 2 * s.note_gadget_wires + 2 * 730 - 1;
+  s.n_constraints = 3 + 3 * (J_BITS + 1) + 4 * (uint64_t)depth + hashes * 730;
+  return s;
+}
+
+// TWO lanes per request: lane 2g walks note a, lane 2g + 1 note b, through the ONE rolled permutation body of k_split_core -- the same
+// instruction stream, uniform trip counts, no device-function calls -- so the two walks cost the wave what one costs and the
+// dependent chain is 6 + depth gadgets deep (4 + depth of a walk, then the two output gadgets) instead of 10 + 2 depth.  Each lane
+// stores its own note's input wires and gadget wires at its own cursor; the even lane alone stores the public and shared wires,
+// chain_id^2, the 384 bit wires (from the record's integer words: the records are checked first, amount_a + amount_b < 2^128), wire 1
+// from note a's walk, the two output gadgets (the odd lane runs them beside it on its own values and stores nothing) and
+// nh_diff_inv, for which it gets nullifier_hash_b from its neighbour (pair_swap) -- one fe_inv, ~380 products behind a chain of
+// ~27 000, not worth spreading.  Every wire is stored by exactly one lane, as a Montgomery value; k_wires_from_mont converts afterwards.
+// A pair never straddles a wave or the end of the batch: both lanes of a pair leave together.
+__global__ void __launch_bounds__(64) k_join_core(const uint32_t* __restrict__ consts, const uint8_t* __restrict__ inputs, int depth,
+                                                 size_t n_wires, uint32_t first_bit_wire, uint32_t note_gadget_wires, size_t n,
+                                                 uint8_t* __restrict__ out) {
+  OG_FILLER_PRIO();
+  const size_t lane = (size_t)blockIdx.x * blockDim.x + threadIdx.x, g = lane >> 1;
+  if (g >= n) return;
+  const bool odd = threadIdx.x & 1, even = !odd;
+  const uint32_t b = odd ? 1u : 0u;
+  const uint8_t* in = inputs + g * (size_t)(J_REC + 2 * depth) * 32;
+  const uint8_t* note = in + (size_t)b * 128;                               // nullifier | secret | amount | index of this lane's note
+  const uint8_t* sibs = in + (size_t)(J_REC + b * (uint32_t)depth) * 32;    // its siblings
+  const uint32_t first_gadget_wire = first_bit_wire + 3 * J_BITS;
+  WireWriterT<false> ww{out + g * n_wires * 32, first_gadget_wire + b * note_gadget_wires};
+  const Fr nullifier = fe_to_mont(fe_load<FrParams>(note));
+  const Fr secret = fe_to_mont(fe_load<FrParams>(note + 32));
+  const Fr amount = fe_to_mont(fe_load<FrParams>(note + 64));
+  const uint64_t index = *reinterpret_cast<const uint64_t*>(note + 96);
+  const Fr token = fe_to_mont(fe_load<FrParams>(in + 256));
+  const Fr out_commitment = fe_to_mont(fe_load<FrParams>(in + 320));
+  // sum = amount_a + amount_b on the integer words
+  const uint64_t a_lo = *reinterpret_cast<const uint64_t*>(in + 64), a_hi = *reinterpret_cast<const uint64_t*>(in + 72);
+  const uint64_t b_lo = *reinterpret_cast<const uint64_t*>(in + 192), b_hi = *reinterpret_cast<const uint64_t*>(in + 200);
+  const uint64_t s_lo = a_lo + b_lo, s_hi = a_hi + b_hi + (s_lo < a_lo ? 1u : 0u);
+  const uint32_t sw[8] = {(uint32_t)s_lo, (uint32_t)(s_lo >> 32), (uint32_t)s_hi, (uint32_t)(s_hi >> 32), 0u, 0u, 0u, 0u};
+  const Fr sum = fe_to_mont(fe_from_words<FrParams>(sw));
+  ww.put(6 + 3 * b, nullifier);
+  ww.put(7 + 3 * b, secret);
+  ww.put(8 + 3 * b, amount);
+  for (int l = 0; l < depth; l++) {
+    ww.put(16 + b * (uint32_t)depth + l, fe_to_mont(fe_load<FrParams>(sibs + (size_t)l * 32)));
+    ww.put(16 + (2 + b) * (uint32_t)depth + l, ((index >> l) & 1) ? Fr::one() : Fr::zero());
+  }
+  if (even) {
+    const Fr chain_id = fe_to_mont(fe_load<FrParams>(in + 288));
+    ww.put(0, Fr::one());
+    ww.put(4, chain_id);
+    ww.put(12, token);
+    ww.put(13, out_commitment);
+    ww.put(14, sum);
+    ww.put(16 + 4 * depth, fe_sqr(chain_id));
+    uint32_t w = first_bit_wire;
+#pragma unroll 1
+    for (int v = 0; v < 3; v++) {  // the bits of amount_a, amount_b, sum, LSB first
+      const uint64_t lo = v == 0 ? a_lo : v == 1 ? b_lo : s_lo, hi = v == 0 ? a_hi : v == 1 ? b_hi : s_hi;
+#pragma unroll 1
+      for (int i = 0; i < J_BITS; i++) ww.put(w++, (((i < 64 ? lo : hi) >> (i & 63)) & 1) ? Fr::one() : Fr::zero());
+    }
+  }
+  // gadget 0: inner = H(nullifier, secret); 1: asset = H(amount, token); 2: leaf = H(inner, asset); 3: nullifier_hash =
+  // H(nullifier, 0) -> wire 2 | 3; 4 + l: level l of this lane's path (the last one's output is the root: wire 1, stored by the even
+  // lane); then, stored by the even lane alone, 4 + depth: out_asset = H(sum, token); 5 + depth: out_leaf = H(out_commitment,
+  // out_asset) -> wire 5
+  Fr cur = Fr::zero(), inner = Fr::zero(), nh = Fr::zero();
+#pragma unroll 1
+  for (int h = 0; h < 6 + depth; h++) {
+    Fr l_in, r_in;
+    int out_wire = -1;
+    bool mine = true, mine_out = true;  // does this lane store the gadget's wires / its output
+    if (h == 0) {
+      l_in = nullifier; r_in = secret;
+    } else if (h == 1) {
+      l_in = amount; r_in = token;
+    } else if (h == 2) {
+      l_in = inner; r_in = cur;
+    } else if (h == 3) {
+      l_in = nullifier; r_in = Fr::zero(); out_wire = 2 + (int)b;
+    } else if (h < 4 + depth) {
+      const int lvl = h - 4;
+      const Fr sib = fe_to_mont(fe_load<FrParams>(sibs + (size_t)lvl * 32));
+      const bool right_child = (index >> lvl) & 1;
+      l_in = right_child ? sib : cur;
+      r_in = right_child ? cur : sib;
+      ww.push(l_in);  // the `left` selector wire
+      if (lvl == depth - 1) { out_wire = 1; mine_out = even; }
+    } else if (h == 4 + depth) {
+      l_in = sum; r_in = token; mine = mine_out = even;
+      ww.w = first_gadget_wire + 2 * note_gadget_wires;
+    } else {
+      l_in = out_commitment; r_in = cur; out_wire = 5; mine = mine_out = even;
+    }
+    // MultiMiMC7([l, r], key 0): k1 = l + E_0(l); out = 2 k1 + r + E_k1(r), with E_k(x) = x_91 + k
+    Fr k = Fr::zero(), x = l_in, k1 = Fr::zero();
+#pragma unroll 1
+    for (int p = 0; p < 2; p++) {
+#pragma unroll 1
+      for (int i = 0; i < MIMC7_ROUNDS; i++) {
+        const Fr t = fe_add3_weak(x, k, mimc7_const(consts, i));  // < 5N, only ever multiplied
+        const Fr t2 = fe_sqr(t);
+        const Fr t4 = fe_sqr(t2);
+        const Fr t6 = fe_mul(t4, t2);
+        x = fe_mul(t6, t);
+        ww.push_if(mine, t2);
+        ww.push_if(mine, t4);
+        ww.push_if(mine, t6);
+        ww.push_if(mine, x);
+      }
+      if (p == 0) {
+        k1 = fe_add(l_in, x);
+        ww.push_if(mine, k1);
+        k = k1;
+        x = r_in;
+      }
+    }
+    const Fr hout = fe_add(fe_add(fe_dbl(k1), r_in), x);
+    if (out_wire < 0) ww.push_if(mine_out, hout); else ww.put_if(mine_out, (uint32_t)out_wire, hout);
+    if (h == 0) inner = hout;
+    if (h == 3) nh = hout; else cur = hout;
+  }
+  // nh_diff_inv = 1 / (nullifier_hash_a - nullifier_hash_b): both lanes of the pair are here (the swap needs them); the operands are
+  // SELECTED so that both lanes form a - b, never b - a, and the even one stores
+  const Fr nh_other = pair_swap(nh);
+  const Fr inv = fe_inv(fe_sub(pair_select(odd, nh_other, nh), pair_select(odd, nh, nh_other)));
+  ww.put_if(even, 15, inv);
+}
+
+// Boundary check of the join records, one lane per field as k_check_split_records: every field canonical (< r), both indices inside
+// the tree (fields 3, 7), amount_a < 2^128 (field 2), amount_b < 2^128 and amount_a + amount_b < 2^128 (field 6) -- compared on the
+// integer words, not in the field --, and nullifier_b != nullifier_a (field 4: nh_diff_inv would not exist).  bad[g] = lowest
+// offending field of record g (the caller initialises it to 0xffffffff): 0 nullifier_a, 1 secret_a, 2 amount_a, 3 index_a,
+// 4 nullifier_b, 5 secret_b, 6 amount_b, 7 index_b, 8 token, 9 chain_id, 10 out_commitment, 11 + l sibling a of level l,
+// 11 + depth + l sibling b of level l.
+__global__ void __launch_bounds__(64) k_check_join_records(const uint8_t* __restrict__ inputs, int depth, size_t n, uint32_t* __restrict__ bad) {
+  OG_FILLER_PRIO();
+  const size_t g = blockIdx.y;
+  const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= n || f >= (uint32_t)(J_REC + 2 * depth)) return;
+  const uint8_t* rec = inputs + g * (size_t)(J_REC + 2 * depth) * 32;
+  const uint8_t* p = rec + (size_t)f * 32;
+  bool ok = fe_lt_modulus(fe_load<FrParams>(p));
+  const uint32_t* w = reinterpret_cast<const uint32_t*>(p);
+  if (f == 2 || f == 6) ok = ok && (w[4] | w[5] | w[6] | w[7]) == 0;
+  if (f == 6) {  // amount_a + amount_b < 2^128 as integers: no carry into word 4 or out of word 7
+    const uint32_t* a = reinterpret_cast<const uint32_t*>(rec + 64);
+    uint64_t carry = 0;
+    uint32_t high = 0;
+    for (int i = 0; i < 8; i++) {
+      carry += (uint64_t)a[i] + w[i];
+      if (i >= 4) high |= (uint32_t)carry;
+      carry >>= 32;
+    }
+    ok = ok && high == 0 && carry == 0;
+  }
+  if (f == 4) {  // nullifier_b != nullifier_a
+    const uint32_t* a = reinterpret_cast<const uint32_t*>(rec);
+    uint32_t diff = 0;
+    for (int i = 0; i < 8; i++) diff |= a[i] ^ w[i];
+    ok = ok && diff != 0;
+  }
+  if (f == 3 || f == 7) {  // an index
+    ok = ok && (w[2] | w[3] | w[4] | w[5] | w[6] | w[7]) == 0;
+    const uint64_t idx = (uint64_t)w[0] | ((uint64_t)w[1] << 32);
+    ok = ok && (depth >= 64 || (idx >> depth) == 0);
+  }
+  if (!ok) atomicMin(&bad[g], f);
+}
+
+int join_shape_query(int depth, uint64_t out[3]) {
+  OG_REQUIRE(depth >= 1 && depth <= 64, "join: depth must be 1..64");
+  const JoinShape s = join_shape(depth);
+  out[0] = s.n_wires; out[1] = s.n_constraints; out[2] = J_PUB;
+  return OG_OK;
+}
+
+// OG_ERR_INVALID names the first malformed record and its lowest offending field (`base` = index of record 0 in the caller's
+// batch); blocking
+int join_records_ok(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, size_t base) {
+  OG_REQUIRE(depth >= 1 && depth <= 64, "join: depth must be 1..64");
+  OG_REQUIRE(n <= 65535, "join: at most 65535 records per call");  // (the record index is grid.y)
+  if (n == 0) return OG_OK;
+  uint32_t* bad_d = nullptr;
+  OG_TRY(arena_get(ctx, "jn.bad", n * 4, (void**)&bad_d));
+  OG_HIP(hipMemsetAsync(bad_d, 0xff, n * 4, ctx->stream));
+  hipLaunchKernelGGL(k_check_join_records, dim3(grid_for(J_REC + 2 * depth, 64), (unsigned)n), dim3(64), 0, ctx->stream, inputs_d, depth, n, bad_d);
+  OG_HIP(hipGetLastError());
+  std::vector<uint32_t> bad(n);
+  OG_HIP(hipMemcpyAsync(bad.data(), bad_d, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+  OG_HIP(hipStreamSynchronize(ctx->stream));
+  static const char* names[J_REC] = {"nullifier_a", "secret_a", "amount_a", "index_a", "nullifier_b", "secret_b", "amount_b", "index_b",
+                                     "token", "chain_id", "out_commitment"};
+  for (size_t g = 0; g < n; g++)
+    if (bad[g] != 0xffffffffu) {
+      const uint32_t f = bad[g];
+      const std::string name = f < (uint32_t)J_REC ? std::string(names[f])
+                               : f < (uint32_t)(J_REC + depth) ? "sibling a " + std::to_string(f - J_REC)
+                                                               : "sibling b " + std::to_string(f - J_REC - depth);
+      set_error("og_join: input record " + std::to_string(base + g) + ": field " + std::to_string(f) + " (" + name +
+                ") is not a valid value (>= r, an index outside the tree, an amount >= 2^128, amount_a + amount_b >= 2^128, or "
+                "nullifier_b = nullifier_a)");
+      return OG_ERR_INVALID;
+    }
+  return OG_OK;
+}
+
+// records (checked: join_records_ok) -> n x n_wires x 32 B canonical; two lanes per request
+int join_witness(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, uint8_t* out_d) {
+  OG_REQUIRE(depth >= 1 && depth <= 64, "join: depth must be 1..64");
+  OG_REQUIRE(n <= 65535, "join: at most 65535 witnesses per call");
+  if (n == 0) return OG_OK;
+  const JoinShape s = join_shape(depth);
+  ProfScope ps(ctx, PROF_WITNESS, (double)n);
+  hipLaunchKernelGGL(k_join_core, dim3(grid_for(2 * n, 64)), dim3(64), 0, ctx->stream, (const uint32_t*)ctx->mimc_consts_d, inputs_d, depth,
+                     (size_t)s.n_wires, (uint32_t)s.first_bit_wire, (uint32_t)s.note_gadget_wires, n, out_d);
   OG_HIP(hipGetLastError());
   hipLaunchKernelGGL(k_wires_from_mont, dim3(grid_for(s.n_wires, 256), (unsigned)n), dim3(256), 0, ctx->stream, out_d, (size_t)s.n_wires,
                      (uint32_t)s.n_wires, 1u);
