@@ -428,6 +428,46 @@ int og_join_witness_d(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n,
 int og_join_prove_batch_d(og_ctx* ctx, const og_pk* pk, int depth, const uint8_t* inputs_d, size_t n, const uint8_t* rs,
                           uint8_t* proofs_out, uint8_t* public_out);
 
+/* ---- transfer statement: pay part of a note to somebody else INSIDE the pool, keep the rest ---------------------------------------
+ * "I know a note under `root` worth `amount` of `token`.  It is spent.  `pay_amount` of it goes into the new leaf `pay_leaf`.  The
+ * rest, change = amount - pay_amount, goes into the new leaf `change_leaf`."  Nothing leaves the pool.  With it the set closes: any
+ * in-pool payment is zero or more joins followed by one transfer.  (No reference counterpart: the snapshot has no circuit.)
+ * public (n_pub = 5, verifier order): root, nullifier_hash, chain_id, pay_leaf, change_leaf
+ * private: nullifier, secret, amount, token, pay_commitment, pay_amount, change_commitment, change, a depth-`depth` MiMC7 Merkle path.
+ * `token` is ONE wire shared by all three asset hashes, private as in join: nothing is paid out.  With H = MultiMiMC7 2-to-1:
+ *   leaf = H(H(nullifier, secret), H(amount, token)) is under root at `index`;  nullifier_hash = H(nullifier, 0);
+ *   pay_amount + change = amount with pay_amount < 2^128 and change < 2^128 (a 128-bit decomposition each: the sum stays below
+ *   2^129 < r and cannot wrap -- this is what makes it impossible to create value);
+ *   pay_leaf = H(pay_commitment, H(pay_amount, token));  change_leaf = H(change_commitment, H(change, token)) -- both have the leaf
+ *   shape of a deposit, so either note is later spent by withdraw, split, join or transfer like any other;  chain_id is bound by
+ *   its square.
+ * pay_commitment and change_commitment are unconstrained private inputs, each a c' = H(nullifier', secret') formed off-circuit; the
+ * payee hands over the first one (a c' nobody can open harms only the prover: the argument of the split statement).
+ * pay_amount = 0 and pay_amount = amount are both allowed.  The ledger's part: og_verify the proof, check that root is known and
+ * nullifier_hash unspent (and mark it), append pay_leaf, then change_leaf (og_mimc7_append_d).
+ * Wire and row order: tests/transfer_spec.py (the spec), og_transfer_r1cs / owshen_amd/circuit.py transfer_r1cs (the R1CS):
+ *   n_wires = 267 + 3 depth + (8 + depth) 730, n_constraints = 260 + 2 depth + (8 + depth) 730 (29 563 / 29 524 at depth 32:
+ *   domain 2^15).  depth 1..64; n <= 65 535 per og_transfer_witness_d call.  shape[0..2] = n_wires, n_constraints, n_pub.
+ * inputs_d: n records of (9 + depth) x 32 B canonical little-endian:
+ *   nullifier | secret | amount | index (u64, low bytes) | token | chain_id | pay_commitment | pay_amount | change_commitment | siblings[depth]
+ * witness_out_d: n x n_wires x 32 B.  og_transfer_prove_batch_d: records -> proofs (rs: n x 64 B host, proofs_out: n x 256 B host,
+ * public_out (host, may be NULL): n x 5 x 32 B in verifier order -- root, nullifier_hash and both leaves are COMPUTED by the
+ * witness generator).  Same bytes as og_transfer_witness_d + og_prove_batch_d.  The key must have this shape's wire count and n_pub.
+ * OG_ERR_INVALID, before anything is proved: a malformed record; og_last_error names the record and its lowest offending field
+ * ("input record 3: field 7 (pay_amount)"; 0 nullifier, 1 secret, 2 amount, 3 index, 4 token, 5 chain_id, 6 pay_commitment,
+ * 7 pay_amount, 8 change_commitment, 9 + l sibling l): any field >= r; an index that does not fit the tree; field 2 if amount >=
+ * 2^128; field 7 if pay_amount >= 2^128 or pay_amount > amount (compared as integers).
+ * The witness generator has two walks with the same bytes: one lane per request for batches, and for calls of at most 512 requests
+ * the wave-wide form of the withdraw statement -- a permutation per wave in three launches, the eight permutations of the two
+ * output notes beside the dependent chain, which is as long as withdraw's.  Out of scope for this statement: the lane-pair round
+ * and the wave-per-request walk, host chains (og_set_host_chains does not change how its witnesses are generated), a submit / job
+ * form, a multi-GPU form and a window-sharded form of the call, and Rust and Solidity bindings (ffi/ and contracts/ are frozen).
+ * split and join have no wave-wide walk yet; this statement's three launches are the template for them. */
+int og_transfer_shape(int depth, uint64_t shape[3]);
+int og_transfer_witness_d(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, uint8_t* witness_out_d);
+int og_transfer_prove_batch_d(og_ctx* ctx, const og_pk* pk, int depth, const uint8_t* inputs_d, size_t n, const uint8_t* rs,
+                              uint8_t* proofs_out, uint8_t* public_out);
+
 /* The same call in two halves, for a host that keeps requests flowing (a sequencer proving batch after batch): submit
  * enqueues ALL the work of the batch on the ctx's streams and returns; og_job_wait blocks until it is done, fills
  * proofs_out / public_out (which, like rs, must stay valid until then) and frees the job.  At most two calls may be in
@@ -502,6 +542,8 @@ int og_deposit_r1cs(og_ctx* ctx, og_r1cs** out);
 int og_split_r1cs(og_ctx* ctx, int depth, og_r1cs** out);
 /* the statement of og_join_witness_d at this depth (wire and row order: tests/join_spec.py) */
 int og_join_r1cs(og_ctx* ctx, int depth, og_r1cs** out);
+/* the statement of og_transfer_witness_d at this depth (wire and row order: tests/transfer_spec.py) */
+int og_transfer_r1cs(og_ctx* ctx, int depth, og_r1cs** out);
 int og_r1cs_from_csr(uint64_t n_wires, uint64_t n_pub, uint64_t n_constraints, const uint32_t* const ptr[3],
                      const uint32_t* const col[3], const uint8_t* const val[3], og_r1cs** out);
 void og_r1cs_free(og_r1cs* r1cs);

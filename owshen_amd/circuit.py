@@ -20,8 +20,8 @@ points, Fr NTT 2^17"): n_wires = 2^18, domain 2^17.
 Only index arrays and constants are produced here (numpy); there is no host-side witness
 generator -- the witness comes from og_withdraw_witness_d.
 
-The deposit, the split and the join statement (oracle/py/deposit.py, tests/split_spec.py, tests/join_spec.py are their specs)
-follow further down, built with the same gadget builder.
+The deposit, the split, the join and the transfer statement (oracle/py/deposit.py, tests/split_spec.py, tests/join_spec.py,
+tests/transfer_spec.py are their specs) follow further down, built with the same gadget builder.
 """
 import ctypes as C
 
@@ -598,6 +598,115 @@ def join_out_leaf(out_commitment, total, token, ctx):
 
     leaf = ctx.mimc7_hash2(dev(out_commitment), ctx.mimc7_hash2(dev(total), dev(token)))
     return int.from_bytes(ctx.to_host(leaf).tobytes(), "little")
+
+
+# ---- the transfer statement (tests/transfer_spec.py is the spec; witness.hip k_transfer_core / k_tw9_* fill the wires) ---------------
+# public: root, nullifier_hash, chain_id, pay_leaf, change_leaf; private: nullifier, secret, amount, token, pay_commitment, pay_amount,
+# change_commitment, change, the path.  leaf = H(H(nullifier, secret), H(amount, token)) under root; pay_amount + change = amount, both
+# below 2^128 by a bit decomposition; pay_leaf = H(pay_commitment, H(pay_amount, token)), change_leaf = H(change_commitment,
+# H(change, token)).  One note is spent, two are created -- one for the payee, one for the payer -- and nothing leaves the pool.
+T_N_PUB, T_N_REC, T_N_BITS = 5, 9, 128
+(TW_ROOT, TW_NH, TW_CHAIN, TW_PAY_LEAF, TW_CHANGE_LEAF, TW_NULLIFIER, TW_SECRET, TW_AMOUNT, TW_TOKEN, TW_PAY_COMMITMENT, TW_PAY_AMOUNT,
+ TW_CHANGE_COMMITMENT, TW_CHANGE) = range(1, 14)
+
+
+def transfer_shape(depth):
+    """(n_wires, n_constraints): (29563, 29524) at depth 32"""
+    return 267 + 3 * depth + (8 + depth) * 730, 260 + 2 * depth + (8 + depth) * 730
+
+
+def transfer_r1cs(mimc7_constants, depth=32):
+    """the transfer statement as an R1CS (the same gadget builder as the withdraw circuit); no padding gates"""
+    assert depth >= 1 and len(mimc7_constants) == N_ROUNDS
+    n_wires, n_constraints = transfer_shape(depth)
+    bld = _Builder([int(c) for c in mimc7_constants])
+    bld.alloc(1 + T_N_PUB + 8)
+    w_sib = bld.alloc(depth)
+    w_bit = bld.alloc(depth)
+    w_csq = bld.alloc()
+    w_pbit = bld.alloc(T_N_BITS)
+    w_cbit = bld.alloc(T_N_BITS)
+    bld.enforce([(TW_CHAIN, 1)], [(TW_CHAIN, 1)], [(w_csq, 1)])
+    bld.enforce([(TW_PAY_AMOUNT, 1), (TW_CHANGE, 1)], [(0, 1)], [(TW_AMOUNT, 1)])
+    for value, bits in ((TW_PAY_AMOUNT, w_pbit), (TW_CHANGE, w_cbit)):   # value < 2^128: boolean bits, then the recomposition
+        for i in range(T_N_BITS):
+            bld.enforce([(bits + i, 1)], [(bits + i, 1), (0, R - 1)], [])
+        bld.enforce([(bits + i, 1 << i) for i in range(T_N_BITS)], [(0, 1)], [(value, 1)])
+    inner = bld.hash2([(TW_NULLIFIER, 1)], [(TW_SECRET, 1)])
+    asset = bld.hash2([(TW_AMOUNT, 1)], [(TW_TOKEN, 1)])
+    cur = bld.hash2([(inner, 1)], [(asset, 1)])
+    bld.hash2([(TW_NULLIFIER, 1)], [], out_wire=TW_NH)
+    for l in range(depth):
+        b, s = w_bit + l, w_sib + l
+        bld.enforce([(b, 1)], [(b, 1), (0, R - 1)], [])
+        left = bld.alloc()
+        bld.enforce([(b, 1)], [(s, 1), (cur, R - 1)], [(left, 1), (cur, R - 1)])
+        right = [(s, 1), (cur, 1), (left, R - 1)]
+        cur = bld.hash2([(left, 1)], right, out_wire=TW_ROOT if l == depth - 1 else None)
+    pay_asset = bld.hash2([(TW_PAY_AMOUNT, 1)], [(TW_TOKEN, 1)])
+    bld.hash2([(TW_PAY_COMMITMENT, 1)], [(pay_asset, 1)], out_wire=TW_PAY_LEAF)
+    change_asset = bld.hash2([(TW_CHANGE, 1)], [(TW_TOKEN, 1)])
+    bld.hash2([(TW_CHANGE_COMMITMENT, 1)], [(change_asset, 1)], out_wire=TW_CHANGE_LEAF)
+    assert bld.next == n_wires
+    none = np.zeros(0, dtype=np.int64)
+    pad = (none, none, none)
+    r1cs = R1CS(n_wires, T_N_PUB, _csr(bld.a, *pad, n_wires), _csr(bld.b, *pad, n_wires), _csr(bld.c, *pad, n_wires))
+    assert r1cs.n_constraints == n_constraints
+    return r1cs
+
+
+def transfer_r1cs_native(ctx, depth=32):
+    """the same statement built by the library (og_transfer_r1cs: what a Rust host calls)"""
+    h = C.c_void_p()
+    ctx._check(ctx._lib.og_transfer_r1cs(ctx._h, depth, C.byref(h)))
+    return _r1cs_from_handle(ctx, h)
+
+
+def pack_transfer_inputs(nullifier, secret, amount, index, siblings, token=0, chain_id=0, pay_commitment=0, pay_amount=0, change_commitment=0):
+    """one transfer record: (9 + depth) x 32 B (include/owshen_gpu.h):
+    nullifier | secret | amount | index | token | chain_id | pay_commitment | pay_amount | change_commitment | siblings[depth]"""
+    vals = [nullifier, secret, amount, index, token, chain_id, pay_commitment, pay_amount, change_commitment] + list(siblings)
+    return np.frombuffer(b"".join(int(v).to_bytes(32, "little") for v in vals), dtype=np.uint8).reshape(-1, 32).copy()
+
+
+def transfer_witness(ctx, depth, inputs_d):
+    """inputs_d: device uint8 [n, 9 + depth, 32] -> device uint8 [n, n_wires, 32] (og_transfer_witness_d)"""
+    n = inputs_d.shape[0]
+    assert tuple(inputs_d.shape[1:]) == (T_N_REC + depth, 32)
+    shp = (C.c_uint64 * 3)()
+    ctx._check(ctx._lib.og_transfer_shape(depth, shp))
+    assert (int(shp[0]), int(shp[1]), int(shp[2])) == (*transfer_shape(depth), T_N_PUB), "circuit.py and witness.hip disagree on the transfer shape"
+    out = ctx.empty(n, int(shp[0]), 32)
+    ctx._pre()
+    ctx._check(ctx._lib.og_transfer_witness_d(ctx._h, depth, ctx.ptr(inputs_d), n, ctx.ptr(out)))
+    return out
+
+
+def transfer_prove(ctx, pk, depth, inputs_d, rs, return_public=False):
+    """inputs_d: device uint8 [n, 9 + depth, 32]; rs: (r, s) pairs or uint8 [n, 64] -> np.uint8 [n, 256] (og_transfer_prove_batch_d);
+    return_public: also (root, nullifier_hash, chain_id, pay_leaf, change_leaf) of every proof, np.uint8 [n, 5, 32]"""
+    n = inputs_d.shape[0]
+    assert tuple(inputs_d.shape[1:]) == (T_N_REC + depth, 32)
+    rsb = pk._rs_bytes(rs)
+    assert rsb.shape[0] == n
+    out = np.zeros((n, 256), dtype=np.uint8)
+    pub = np.zeros((n, T_N_PUB, 32), dtype=np.uint8) if return_public else None
+    ctx._pre()
+    ctx._check(ctx._lib.og_transfer_prove_batch_d(ctx._h, pk._h, depth, ctx.ptr(inputs_d), n, rsb.ctypes.data_as(C.c_void_p),
+                                                  out.ctypes.data_as(C.c_void_p), pub.ctypes.data_as(C.c_void_p) if return_public else None))
+    return (out, pub) if return_public else out
+
+
+def transfer_leaves(pay_commitment, pay_amount, change_commitment, change, token, ctx):
+    """the ledger's and the payee's side of a transfer: (pay_leaf, change_leaf) = (H(pay_commitment, H(pay_amount, token)),
+    H(change_commitment, H(change, token))) through og_mimc7_hash2_d -- the values of public inputs 4 and 5, what og_mimc7_append_d
+    appends, in this order.  Returns two ints."""
+    def dev(*vs):
+        return ctx.to_device(np.frombuffer(b"".join(int(v).to_bytes(32, "little") for v in vs), dtype=np.uint8).reshape(len(vs), 32).copy())
+
+    tok = dev(token, token)
+    leaves = ctx.mimc7_hash2(dev(pay_commitment, change_commitment), ctx.mimc7_hash2(dev(pay_amount, change), tok))
+    return tuple(int.from_bytes(row.tobytes(), "little") for row in ctx.to_host(leaves))
 
 
 class ProveJob:

@@ -63,6 +63,10 @@ int join_shape_query(int, uint64_t*);
 int join_records_ok(og_ctx*, int, const uint8_t*, size_t, size_t);
 int join_witness(og_ctx*, int, const uint8_t*, size_t, uint8_t*);
 int join_prove_batch(og_ctx*, const og_pk*, int, const uint8_t*, size_t, const uint8_t*, uint8_t*, uint8_t*);
+int transfer_shape_query(int, uint64_t*);
+int transfer_records_ok(og_ctx*, int, const uint8_t*, size_t, size_t);
+int transfer_witness(og_ctx*, int, const uint8_t*, size_t, uint8_t*);
+int transfer_prove_batch(og_ctx*, const og_pk*, int, const uint8_t*, size_t, const uint8_t*, uint8_t*, uint8_t*);
 int job_wait(og_job*);
 int withdraw_prove_partials_enqueue(og_ctx*, const og_pk*, int, uint64_t, uint64_t, const uint8_t*, size_t, int, int, uint8_t*, uint8_t*, og_job**);
 int prove_partials_enqueue(og_ctx*, const og_pk*, const uint8_t*, size_t, int, int, uint8_t*, og_job**);
@@ -853,6 +857,38 @@ int og_join_prove_batch_d(og_ctx* ctx, const og_pk* pk, int depth, const uint8_t
     if (n == 0) return OG_OK;
     LOCKED(ctx);
     return join_prove_batch(ctx, pk, depth, inputs_d, n, rs, proofs_out, public_out);
+  });
+}
+
+int og_transfer_shape(int depth, uint64_t shape[3]) {
+  return guarded([&]() -> int {
+    OG_REQUIRE(shape != nullptr, "og_transfer_shape: null argument");
+    return transfer_shape_query(depth, shape);
+  });
+}
+
+int og_transfer_witness_d(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, uint8_t* witness_out_d) {
+  return guarded([&]() -> int {
+    CTX_OK(ctx);
+    OG_REQUIRE(n <= 65535, "og_transfer_witness_d: at most 65535 witnesses per call");  // (before any scratch is grown or any kernel launched)
+    OG_REQUIRE(n == 0 || (inputs_d && witness_out_d), "og_transfer_witness_d: null argument");
+    LOCKED(ctx);
+    OG_TRY(transfer_records_ok(ctx, depth, inputs_d, n, 0));
+    OG_TRY(transfer_witness(ctx, depth, inputs_d, n, witness_out_d));
+    OG_HIP(hipStreamSynchronize(ctx->stream));
+    return OG_OK;
+  });
+}
+
+int og_transfer_prove_batch_d(og_ctx* ctx, const og_pk* pk, int depth, const uint8_t* inputs_d, size_t n, const uint8_t* rs,
+                              uint8_t* proofs_out, uint8_t* public_out) {
+  return guarded([&]() -> int {
+    CTX_OK(ctx);
+    OG_REQUIRE(pk != nullptr, "og_transfer_prove_batch_d: null key");
+    OG_REQUIRE(n == 0 || (inputs_d && rs && proofs_out), "og_transfer_prove_batch_d: null argument");
+    if (n == 0) return OG_OK;
+    LOCKED(ctx);
+    return transfer_prove_batch(ctx, pk, depth, inputs_d, n, rs, proofs_out, public_out);
   });
 }
 

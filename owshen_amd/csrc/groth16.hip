@@ -1483,7 +1483,7 @@ int deposit_prove_batch(og_ctx* ctx, const og_pk* pk, const uint8_t* inputs_d, s
   return OG_OK;
 }
 
-// records -> proofs for the statements whose witnesses depend on a depth alone (split, join): per slab -- sized as the small-circuit
+// records -> proofs for the statements whose witnesses depend on a depth alone (split, join, transfer): per slab -- sized as the small-circuit
 // branch of withdraw_prove_batch -- check the records, generate the witnesses in one launch, then the ordinary batched prover.
 // `rec`: bytes per record; records_ok / witness: the statement's boundary check and its witness launch (witness.hip)
 typedef int (*records_ok_fn)(og_ctx*, int, const uint8_t*, size_t, size_t);
@@ -1531,6 +1531,19 @@ int join_prove_batch(og_ctx* ctx, const og_pk* pk, int depth, const uint8_t* inp
   OG_TRY(join_shape_query(depth, shp));
   OG_REQUIRE(shp[0] == pk->m && shp[2] == pk->n_pub, "og_join_prove_batch_d: the key is not for this join-statement shape");
   return records_prove_batch(ctx, pk, depth, (size_t)(11 + 2 * depth) * 32, join_records_ok, join_witness, inputs_d, n, rs, proofs, pub_out);
+}
+
+// transfer records -> proofs of the transfer statement (witness.hip, tests/transfer_spec.py): the third user of the slab loop; a call
+// of at most 512 requests walks wave-wide (k_tw9_*), a batch lane-local (k_transfer_core)
+int transfer_shape_query(int, uint64_t out[3]);
+int transfer_records_ok(og_ctx*, int, const uint8_t*, size_t, size_t);
+int transfer_witness(og_ctx*, int, const uint8_t*, size_t, uint8_t*);
+int transfer_prove_batch(og_ctx* ctx, const og_pk* pk, int depth, const uint8_t* inputs_d, size_t n, const uint8_t* rs, uint8_t* proofs,
+                         uint8_t* pub_out) {
+  uint64_t shp[3];
+  OG_TRY(transfer_shape_query(depth, shp));
+  OG_REQUIRE(shp[0] == pk->m && shp[2] == pk->n_pub, "og_transfer_prove_batch_d: the key is not for this transfer-statement shape");
+  return records_prove_batch(ctx, pk, depth, (size_t)(9 + depth) * 32, transfer_records_ok, transfer_witness, inputs_d, n, rs, proofs, pub_out);
 }
 
 // ---- window-sharded proving: the two halves (WinShard above) -------------------------------------------------------------------

@@ -8,8 +8,8 @@
 //
 //   og_withdraw_r1cs   constraint rows of the depth-D MiMC7 Merkle withdraw circuit (+ synthetic padding gates, + the two
 //                      optional density rows), CSR, canonical 32-byte coefficients
-//   og_deposit_r1cs / og_split_r1cs / og_join_r1cs   the deposit, the split and the join statement, with the same builder
-//                      (oracle/py/deposit.py, tests/split_spec.py, tests/join_spec.py)
+//   og_deposit_r1cs / og_split_r1cs / og_join_r1cs / og_transfer_r1cs   the deposit, the split, the join and the transfer statement,
+//                      with the same builder (oracle/py/deposit.py, tests/split_spec.py, tests/join_spec.py, tests/transfer_spec.py)
 //   og_r1cs_from_csr   any R1CS the caller built
 //   og_setup           Groth16 key generation from (tau, alpha, beta, gamma, delta): Lagrange evaluations, the three
 //                      transposed sparse products, the query scalars and ~3 m + d fixed-base multiplications, all on the
@@ -304,6 +304,56 @@ int join_r1cs_build(const uint8_t* mimc_consts, int depth, og_r1cs* r) {
   return OG_OK;
 }
 
+// the transfer statement (tests/transfer_spec.py; witness.hip k_transfer_core / k_tw9_*): part of a note into a leaf for the payee,
+// the rest into a change leaf, nothing out of the pool
+int transfer_shape_query(int depth, uint64_t out[3]);
+int transfer_r1cs_build(const uint8_t* mimc_consts, int depth, og_r1cs* r) {
+  uint64_t shp[3];
+  OG_TRY(transfer_shape_query(depth, shp));
+  r->n_wires = shp[0];
+  r->n_pub = shp[2];
+  for (int k = 0; k < 3; k++) r->ptr[k].assign(1, 0u);
+  R1csBuilder b{r, 0, mimc_consts};
+  const HFr m1 = hfr_neg_one();
+  constexpr uint32_t TW_ROOT = 1, TW_NH = 2, TW_CHAIN = 3, TW_PAY_LEAF = 4, TW_CHANGE_LEAF = 5, TW_NULLIFIER = 6, TW_SECRET = 7, TW_AMOUNT = 8,
+                     TW_TOKEN = 9, TW_PAY_COMMITMENT = 10, TW_PAY_AMOUNT = 11, TW_CHANGE_COMMITMENT = 12, TW_CHANGE = 13;
+  OG_REQUIRE(r->n_pub == 5, "og_transfer_r1cs: the statement has five public inputs");
+  b.alloc(1 + 5 + 8);
+  const uint32_t w_sib = b.alloc(depth), w_bit = b.alloc(depth), w_csq = b.alloc();
+  const uint32_t w_pbit = b.alloc(128), w_cbit = b.alloc(128);
+  b.enforce(R1csBuilder::one(TW_CHAIN), R1csBuilder::one(TW_CHAIN), R1csBuilder::one(w_csq));
+  b.enforce(LC{{TW_PAY_AMOUNT, hfr_u64(1)}, {TW_CHANGE, hfr_u64(1)}}, R1csBuilder::one(0), R1csBuilder::one(TW_AMOUNT));  // pay_amount + change = amount
+  for (int v = 0; v < 2; v++) {  // pay_amount, then change: 128 boolean rows and the recomposition, so that each is < 2^128
+    const uint32_t bits = v ? w_cbit : w_pbit;
+    LC sum;
+    for (uint32_t i = 0; i < 128; i++) {
+      b.enforce(R1csBuilder::one(bits + i), LC{{bits + i, hfr_u64(1)}, {0u, m1}}, LC{});
+      HFr p2 = {{0, 0, 0, 0}};
+      p2.v[i >> 6] = 1ull << (i & 63);
+      sum.push_back({bits + i, p2});
+    }
+    b.enforce(sum, R1csBuilder::one(0), R1csBuilder::one(v ? TW_CHANGE : TW_PAY_AMOUNT));
+  }
+  const uint32_t inner = b.hash2(R1csBuilder::one(TW_NULLIFIER), R1csBuilder::one(TW_SECRET));
+  const uint32_t asset = b.hash2(R1csBuilder::one(TW_AMOUNT), R1csBuilder::one(TW_TOKEN));
+  uint32_t cur = b.hash2(R1csBuilder::one(inner), R1csBuilder::one(asset));
+  b.hash2(R1csBuilder::one(TW_NULLIFIER), LC{}, (int)TW_NH);
+  for (int l = 0; l < depth; l++) {
+    const uint32_t bit = w_bit + l, s = w_sib + l;
+    b.enforce(R1csBuilder::one(bit), LC{{bit, hfr_u64(1)}, {0u, m1}}, LC{});              // bit (bit - 1) = 0
+    const uint32_t left = b.alloc();
+    b.enforce(R1csBuilder::one(bit), LC{{s, hfr_u64(1)}, {cur, m1}}, LC{{left, hfr_u64(1)}, {cur, m1}});  // left = cur + bit (s - cur)
+    const LC right{{s, hfr_u64(1)}, {cur, hfr_u64(1)}, {left, m1}};
+    cur = b.hash2(R1csBuilder::one(left), right, l == depth - 1 ? (int)TW_ROOT : -1);
+  }
+  const uint32_t pay_asset = b.hash2(R1csBuilder::one(TW_PAY_AMOUNT), R1csBuilder::one(TW_TOKEN));
+  b.hash2(R1csBuilder::one(TW_PAY_COMMITMENT), R1csBuilder::one(pay_asset), (int)TW_PAY_LEAF);
+  const uint32_t change_asset = b.hash2(R1csBuilder::one(TW_CHANGE), R1csBuilder::one(TW_TOKEN));
+  b.hash2(R1csBuilder::one(TW_CHANGE_COMMITMENT), R1csBuilder::one(change_asset), (int)TW_CHANGE_LEAF);
+  OG_REQUIRE(b.next == r->n_wires && r->n_constraints == shp[1], "og_transfer_r1cs: internal shape mismatch");
+  return OG_OK;
+}
+
 // ---- setup kernels ---------------------------------------------------------------------------------------------
 // toxic: tau | alpha | beta | gamma | delta (canonical).  out: 0 zt = tau^d - 1, 1 1/gamma, 2 1/delta, 3 zt/delta
 __global__ void k_setup_scalars(const uint8_t* __restrict__ toxic, int log_d, uint8_t* __restrict__ out) {
@@ -551,6 +601,21 @@ int og_join_r1cs(og_ctx* ctx, int depth, og_r1cs** out) {
     *out = nullptr;
     og_r1cs* r = new og_r1cs();
     int rc = join_r1cs_build(ctx->mimc_consts_canon, depth, r);
+    if (rc != OG_OK) {
+      delete r;
+      return rc;
+    }
+    *out = r;
+    return OG_OK;
+  });
+}
+
+int og_transfer_r1cs(og_ctx* ctx, int depth, og_r1cs** out) {
+  return guarded([&]() -> int {
+    OG_REQUIRE(ctx != nullptr && out != nullptr, "og_transfer_r1cs: null argument");
+    *out = nullptr;
+    og_r1cs* r = new og_r1cs();
+    int rc = transfer_r1cs_build(ctx->mimc_consts_canon, depth, r);
     if (rc != OG_OK) {
       delete r;
       return rc;

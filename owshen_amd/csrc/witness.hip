@@ -8,7 +8,9 @@
 //                    intermediate power (t^2, t^4, t^6, t^7 per round), the Merkle selectors
 //   k_withdraw_pad   one lane per padding unit (a 3-wire gate or a 64-gate chained segment)
 //   k_deposit_witness / k_split_core   the deposit and the split statement (further down), one lane per request
-//   k_join_core      the join statement (at the end): two lanes per request, one per note
+//   k_join_core      the join statement: two lanes per request, one per note
+//   k_transfer_core / k_tw9_*   the transfer statement (at the end): one lane per request for batches, a permutation per wave in three
+//                    launches for calls of at most 512 requests
 //
 // Input record per proof, (8 + depth) x 32 B canonical LE:
 //   nullifier | secret | amount | recipient | pad_seed | index (u64 in the low bytes) | token | chain_id | siblings[depth]
@@ -888,6 +890,37 @@ int deposit_witness(og_ctx* ctx, const uint8_t* inputs_d, size_t n, uint8_t* out
   return OG_OK;
 }
 
+// The ONE rolled permutation body of the one-lane-per-request statement kernels (k_split_core, k_transfer_core): MultiMiMC7([l, r],
+// key 0) with every wire of the gadget but its output pushed at the writer's cursor -- k1 = l + E_0(l); out = 2 k1 + r + E_k1(r), with
+// E_k(x) = x_91 + k.  Inlined into the kernel's loop over gadgets (no device-function call).  Returns the gadget's output.
+// (k_join_core keeps the same loop in its own text, with a store predicate per lane of its pairs: routed through here it compiles
+// to one VGPR more, and the existing rows of the kernel-resource table stay what they are.)
+__device__ __forceinline__ Fr gadget_wires(const uint32_t* __restrict__ consts, WireWriterT<false>& ww, const Fr& l_in, const Fr& r_in) {
+  Fr k = Fr::zero(), x = l_in, k1 = Fr::zero();
+#pragma unroll 1
+  for (int p = 0; p < 2; p++) {
+#pragma unroll 1
+    for (int i = 0; i < MIMC7_ROUNDS; i++) {
+      const Fr t = fe_add3_weak(x, k, mimc7_const(consts, i));  // < 5N, only ever multiplied
+      const Fr t2 = fe_sqr(t);
+      const Fr t4 = fe_sqr(t2);
+      const Fr t6 = fe_mul(t4, t2);
+      x = fe_mul(t6, t);
+      ww.push(t2);
+      ww.push(t4);
+      ww.push(t6);
+      ww.push(x);
+    }
+    if (p == 0) {
+      k1 = fe_add(l_in, x);
+      ww.push(k1);
+      k = k1;
+      x = r_in;
+    }
+  }
+  return fe_add(fe_add(fe_dbl(k1), r_in), x);
+}
+
 // ---- the split statement: withdraw part of a note, keep the rest as a change note ---------------------------------------------------
 // Spec: tests/split_spec.py.  public: root, nullifier_hash, recipient, amount_out, token, chain_id, change_leaf (n_pub = 7); private:
 // nullifier, secret, amount, change_commitment, change, the path.  The note leaf = H(H(nullifier, secret), H(amount, token)) lies under
@@ -996,30 +1029,7 @@ __global__ void __launch_bounds__(64) k_split_core(const uint32_t* __restrict__ 
     } else {
       l_in = change_commitment; r_in = cur; out_wire = 7;
     }
-    // MultiMiMC7([l, r], key 0): k1 = l + E_0(l); out = 2 k1 + r + E_k1(r), with E_k(x) = x_91 + k
-    Fr k = Fr::zero(), x = l_in, k1 = Fr::zero();
-#pragma unroll 1
-    for (int p = 0; p < 2; p++) {
-#pragma unroll 1
-      for (int i = 0; i < MIMC7_ROUNDS; i++) {
-        const Fr t = fe_add3_weak(x, k, mimc7_const(consts, i));  // < 5N, only ever multiplied
-        const Fr t2 = fe_sqr(t);
-        const Fr t4 = fe_sqr(t2);
-        const Fr t6 = fe_mul(t4, t2);
-        x = fe_mul(t6, t);
-        ww.push(t2);
-        ww.push(t4);
-        ww.push(t6);
-        ww.push(x);
-      }
-      if (p == 0) {
-        k1 = fe_add(l_in, x);
-        ww.push(k1);
-        k = k1;
-        x = r_in;
-      }
-    }
-    const Fr hout = fe_add(fe_add(fe_dbl(k1), r_in), x);
+    const Fr hout = gadget_wires(consts, ww, l_in, r_in);
     if (out_wire < 0) ww.push(hout); else ww.put((uint32_t)out_wire, hout);
     if (h == 0) inner = hout;
     if (h != 3) cur = hout;
@@ -1352,6 +1362,402 @@ int join_witness(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, uint
   ProfScope ps(ctx, PROF_WITNESS, (double)n);
   hipLaunchKernelGGL(k_join_core, dim3(grid_for(2 * n, 64)), dim3(64), 0, ctx->stream, (const uint32_t*)ctx->mimc_consts_d, inputs_d, depth,
                      (size_t)s.n_wires, (uint32_t)s.first_bit_wire, (uint32_t)s.note_gadget_wires, n, out_d);
+  OG_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_wires_from_mont, dim3(grid_for(s.n_wires, 256), (unsigned)n), dim3(256), 0, ctx->stream, out_d, (size_t)s.n_wires,
+                     (uint32_t)s.n_wires, 1u);
+  OG_HIP(hipGetLastError());
+  return OG_OK;
+}
+
+// ---- the transfer statement: pay part of a note inside the pool, keep the rest ------------------------------------------------------
+// Spec: tests/transfer_spec.py.  public: root, nullifier_hash, chain_id, pay_leaf, change_leaf (n_pub = 5); private: nullifier, secret,
+// amount, token (ONE wire for all three asset hashes, private as in join: nothing is paid out), pay_commitment, pay_amount,
+// change_commitment, change, the path.  The note leaf = H(H(nullifier, secret), H(amount, token)) lies under root, nullifier_hash =
+// H(nullifier, 0), pay_amount + change = amount with both below 2^128 (a 128-bit decomposition each: the sum cannot wrap, which is what
+// makes it impossible to create value), pay_leaf = H(pay_commitment, H(pay_amount, token)) and change_leaf = H(change_commitment,
+// H(change, token)) -- two leaves of the deposit shape, which og_mimc7_append_d appends in that order.  Nothing leaves the pool.  No
+// reference counterpart (the snapshot has no circuit).
+// Input record per request, (9 + depth) x 32 B canonical LE:
+//   nullifier | secret | amount | index (u64 in the low bytes) | token | chain_id | pay_commitment | pay_amount | change_commitment | siblings[depth]
+// Wires:
+//   0 one | 1 root | 2 nullifier_hash | 3 chain_id | 4 pay_leaf | 5 change_leaf
+//   6 nullifier | 7 secret | 8 amount | 9 token | 10 pay_commitment | 11 pay_amount | 12 change_commitment | 13 change
+//   14.. siblings[D] | index bits[D] | chain_id^2 | pay_amount bits[128] (LSB first) | change bits[128] | the gadgets: inner, asset, leaf,
+//   nullifier_hash (out = wire 2), level 0..D-1 (the last one's out = wire 1), pay_asset = H(pay_amount, token), pay_leaf =
+//   H(pay_commitment, pay_asset) (out = wire 4), change_asset = H(change, token), change_leaf = H(change_commitment, change_asset) (out = wire 5)
+// Two walks: k_transfer_core (one lane per request, the form for batches) and k_tw9_* (a permutation per wave in three launches, for
+// calls of at most 512 requests: the rule of withdraw's k_w9_*).  NOT built for this statement: the t^4 | t^3 lane-pair round, the
+// wave-per-request walk, host chains.
+constexpr int T_PUB = 5;
+constexpr int T_REC = 9;  // fields of a transfer record before the siblings
+constexpr int T_BITS = 128;
+// byte offsets of the record's fields
+constexpr int T_NULLIFIER = 0, T_SECRET = 32, T_AMOUNT = 64, T_INDEX = 96, T_TOKEN = 128, T_CHAIN = 160, T_PAY_COMMITMENT = 192, T_PAY_AMOUNT = 224,
+              T_CHANGE_COMMITMENT = 256;
+
+struct TransferShape {
+  uint64_t n_wires, n_constraints, first_bit_wire, first_gadget_wire;
+};
+
+static TransferShape transfer_shape(int depth) {
+  TransferShape s;
+  const uint64_t hashes = 8 + (uint64_t)depth;
+  s.first_bit_wire = 1 + T_PUB + 8 + 2 * (uint64_t)depth + 1;
+  s.first_gadget_wire = s.first_bit_wire + 2 * T_BITS;
+  s.n_wires = s.first_gadget_wire + depth + hashes * 730 - 4;  // a `left` per level; nullifier_hash, root and the two leaves are public wires
+  s.n_constraints = 2 + 2 * (T_BITS + 1) + 2 * (uint64_t)depth + hashes * 730;
+  return s;
+}
+
+// change = amount - pay_amount on the record's integer words (the records are checked first: pay_amount <= amount < 2^128, so the
+// difference does not borrow): its two 64-bit halves, and the field element
+struct TransferChange {
+  uint64_t p_lo, p_hi, c_lo, c_hi;
+  __device__ __forceinline__ Fr value() const {
+    const uint32_t cw[8] = {(uint32_t)c_lo, (uint32_t)(c_lo >> 32), (uint32_t)c_hi, (uint32_t)(c_hi >> 32), 0u, 0u, 0u, 0u};
+    return fe_to_mont(fe_from_words<FrParams>(cw));
+  }
+};
+__device__ __forceinline__ TransferChange transfer_change(const uint8_t* in) {
+  const uint64_t a_lo = *reinterpret_cast<const uint64_t*>(in + T_AMOUNT), a_hi = *reinterpret_cast<const uint64_t*>(in + T_AMOUNT + 8);
+  TransferChange c;
+  c.p_lo = *reinterpret_cast<const uint64_t*>(in + T_PAY_AMOUNT);
+  c.p_hi = *reinterpret_cast<const uint64_t*>(in + T_PAY_AMOUNT + 8);
+  c.c_lo = a_lo - c.p_lo;
+  c.c_hi = a_hi - c.p_hi - (a_lo < c.p_lo ? 1u : 0u);
+  return c;
+}
+// bit i (0 .. 255) of pay_amount | change, as a wire
+__device__ __forceinline__ Fr transfer_bit_wire(const TransferChange& c, int i) {
+  const uint64_t word = i < 64 ? c.p_lo : i < 128 ? c.p_hi : i < 192 ? c.c_lo : c.c_hi;
+  return ((word >> (i & 63)) & 1) ? Fr::one() : Fr::zero();
+}
+
+// One lane per request, as k_split_core: the (8 + depth) MultiMiMC7 gadgets through the one rolled permutation body (gadget_wires), no
+// device-function calls; Montgomery values are stored and k_wires_from_mont converts them afterwards, in parallel.
+__global__ void __launch_bounds__(64) k_transfer_core(const uint32_t* __restrict__ consts, const uint8_t* __restrict__ inputs, int depth,
+                                                     size_t n_wires, uint32_t first_bit_wire, size_t n, uint8_t* __restrict__ out) {
+  OG_FILLER_PRIO();
+  const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= n) return;
+  const uint8_t* in = inputs + g * (size_t)(T_REC + depth) * 32;
+  WireWriterT<false> ww{out + g * n_wires * 32, first_bit_wire};
+  const Fr nullifier = fe_to_mont(fe_load<FrParams>(in + T_NULLIFIER));
+  const Fr secret = fe_to_mont(fe_load<FrParams>(in + T_SECRET));
+  const Fr amount = fe_to_mont(fe_load<FrParams>(in + T_AMOUNT));
+  const uint64_t index = *reinterpret_cast<const uint64_t*>(in + T_INDEX);
+  const Fr token = fe_to_mont(fe_load<FrParams>(in + T_TOKEN));
+  const Fr chain_id = fe_to_mont(fe_load<FrParams>(in + T_CHAIN));
+  const Fr pay_commitment = fe_to_mont(fe_load<FrParams>(in + T_PAY_COMMITMENT));
+  const Fr pay_amount = fe_to_mont(fe_load<FrParams>(in + T_PAY_AMOUNT));
+  const Fr change_commitment = fe_to_mont(fe_load<FrParams>(in + T_CHANGE_COMMITMENT));
+  const TransferChange chg = transfer_change(in);
+  const Fr change = chg.value();
+  ww.put(0, Fr::one());
+  ww.put(3, chain_id);
+  ww.put(6, nullifier);
+  ww.put(7, secret);
+  ww.put(8, amount);
+  ww.put(9, token);
+  ww.put(10, pay_commitment);
+  ww.put(11, pay_amount);
+  ww.put(12, change_commitment);
+  ww.put(13, change);
+  for (int l = 0; l < depth; l++) {
+    ww.put(14 + l, fe_to_mont(fe_load<FrParams>(in + (size_t)(T_REC + l) * 32)));
+    ww.put(14 + depth + l, ((index >> l) & 1) ? Fr::one() : Fr::zero());
+  }
+  ww.put(14 + 2 * depth, fe_sqr(chain_id));
+#pragma unroll 1
+  for (int i = 0; i < 2 * T_BITS; i++) ww.push(transfer_bit_wire(chg, i));  // the bits of pay_amount, then of change, LSB first
+  // gadget 0: inner = H(nullifier, secret); 1: asset = H(amount, token); 2: leaf = H(inner, asset); 3: nullifier_hash =
+  // H(nullifier, 0) -> wire 2; 4 + l: level l of the path (wire 1 = root for the last level); 4 + depth: pay_asset = H(pay_amount,
+  // token); 5 + depth: pay_leaf = H(pay_commitment, pay_asset) -> wire 4; 6 + depth: change_asset = H(change, token); 7 + depth:
+  // change_leaf = H(change_commitment, change_asset) -> wire 5
+  Fr cur = Fr::zero(), inner = Fr::zero();
+#pragma unroll 1
+  for (int h = 0; h < 8 + depth; h++) {
+    Fr l_in, r_in;
+    int out_wire = -1;
+    if (h == 0) {
+      l_in = nullifier; r_in = secret;
+    } else if (h == 1) {
+      l_in = amount; r_in = token;
+    } else if (h == 2) {
+      l_in = inner; r_in = cur;
+    } else if (h == 3) {
+      l_in = nullifier; r_in = Fr::zero(); out_wire = 2;
+    } else if (h < 4 + depth) {
+      const int lvl = h - 4;
+      const Fr sib = fe_to_mont(fe_load<FrParams>(in + (size_t)(T_REC + lvl) * 32));
+      const bool right_child = (index >> lvl) & 1;
+      l_in = right_child ? sib : cur;
+      r_in = right_child ? cur : sib;
+      ww.push(l_in);  // the `left` selector wire
+      if (lvl == depth - 1) out_wire = 1;
+    } else if (h == 4 + depth) {
+      l_in = pay_amount; r_in = token;
+    } else if (h == 5 + depth) {
+      l_in = pay_commitment; r_in = cur; out_wire = 4;
+    } else if (h == 6 + depth) {
+      l_in = change; r_in = token;
+    } else {
+      l_in = change_commitment; r_in = cur; out_wire = 5;
+    }
+    const Fr hout = gadget_wires(consts, ww, l_in, r_in);
+    if (out_wire < 0) ww.push(hout); else ww.put((uint32_t)out_wire, hout);
+    if (h == 0) inner = hout;
+    if (h != 3) cur = hout;
+  }
+}
+
+// The wave-wide form of the same walk (the header of k_w9_*: ONE permutation per one-wave workgroup, values between the launches as
+// nine lazy limbs in xch, wires as nine limbs in wl for k_wires_from_limbs, the bounds of mimc7.hip.h w9_mimc7_round -- every hash
+// output passes the strict product by one, w9_renorm, before it is anybody's input).  The two output notes do not depend on the
+// Merkle walk, so all eight of their permutations sit BESIDE the dependent chain, which is exactly as long as withdraw's:
+//   k_tw9_first   grid n x (7 + depth): E_0 of nullifier (wires of gadgets 0 and 3), amount, pay_amount, change, pay_commitment and
+//                 change_commitment; E_0(sibling_l) of every level whose path node is the RIGHT input; one workgroup for the wires
+//                 that are inputs, the square, the index bits and the 256 bit wires
+//   k_tw9_second  grid n x 5: the second permutations of inner, asset, nullifier_hash, pay_asset, change_asset
+//   k_tw9_chain   grid n x 3: block 0 is the chain (leaf, then the levels: k_w9_chain's work); blocks 1 and 2 are the second
+//                 permutations of pay_leaf and change_leaf
+// xch slots per request beyond the levels: [depth + 0] k1 of inner / nullifier_hash, [1] k1 of asset, [2] inner, [3] asset, [4] k1 of
+// pay_asset, [5] k1 of change_asset, [6] k1 of pay_leaf, [7] k1 of change_leaf, [8] pay_asset, [9] change_asset, [10 .. 13]: 36 words
+// nobody reads -- where the lanes without a limb store (w9_permute `dump`)
+constexpr int TW9_XCH = 14, TW9_DUMP = 10;
+// first wire of gadget h (for a level: of its hash, behind the `left` wire)
+__device__ __forceinline__ uint32_t tw9_gadget_base(uint32_t fgw, int depth, int h) {
+  if (h < 4) return fgw + (uint32_t)h * 730u;
+  if (h < 4 + depth) return w9_gadget_base(fgw, h) + 1u;
+  const uint32_t ob = fgw + 2918u + 731u * (uint32_t)depth;  // behind the levels (the last one's output is wire 1)
+  return ob + (h == 4 + depth ? 0u : h == 5 + depth ? 730u : h == 6 + depth ? 1459u : 2189u);  // (pay_leaf's output is wire 4)
+}
+// the rest of H(l, r) once k1 = l + E_0(l) is there: the second permutation's wires behind k1's, the output (below 2 N) at out_wire
+template <int FORM>
+__device__ __forceinline__ uint32_t tw9_second_half(const uint32_t* __restrict__ consts9, uint32_t r_in, uint32_t k1, uint32_t nj, int tid, int lane,
+                                                    uint32_t* __restrict__ wl, uint32_t base, uint32_t out_wire, uint32_t* __restrict__ dump) {
+  const uint32_t xr = w9_permute<FORM, false>(consts9, r_in, k1, nj, tid, lane, wl, base + 365, 0u, dump);
+  const uint32_t h = w9_renorm(2u * k1 + r_in + xr, nj, lane);
+  w9_store(wl, out_wire, h, tid);
+  return h;
+}
+
+template <int FORM>
+__global__ void __launch_bounds__(64) k_tw9_first(const uint32_t* __restrict__ consts9, const uint8_t* __restrict__ inputs, int depth, size_t n_wires,
+                                                 uint32_t fgw, uint32_t* __restrict__ wl_all, uint32_t* __restrict__ xch_all) {
+  OG_FILLER_PRIO();
+  const int jobs = 7 + depth, tid = threadIdx.x, lane = FORM ? w9_row_limb(tid) : tid;
+  const size_t g = blockIdx.x / jobs;
+  const int job = (int)(blockIdx.x % jobs);
+  const uint8_t* in = inputs + g * (size_t)(T_REC + depth) * 32;
+  uint32_t* wl = wl_all + g * n_wires * 9;
+  uint32_t* xch = xch_all + g * (size_t)(depth + TW9_XCH) * 9;
+  const uint64_t index = *reinterpret_cast<const uint64_t*>(in + T_INDEX);
+  if (job == 6 + depth) {  // the wires that are inputs, the square, the index bits and the 256 bit wires: lane-local values, a lane per wire
+    const int lane = tid;
+    const TransferChange chg = transfer_change(in);
+    const Fr chain_id = fe_to_mont(fe_load<FrParams>(in + T_CHAIN));
+    if (lane == 0) w9_put_fe(wl, 0, Fr::one());
+    if (lane == 1) w9_put_fe(wl, 3, chain_id);
+    if (lane == 2) w9_put_fe(wl, 6, fe_to_mont(fe_load<FrParams>(in + T_NULLIFIER)));
+    if (lane == 3) w9_put_fe(wl, 7, fe_to_mont(fe_load<FrParams>(in + T_SECRET)));
+    if (lane == 4) w9_put_fe(wl, 8, fe_to_mont(fe_load<FrParams>(in + T_AMOUNT)));
+    if (lane == 5) w9_put_fe(wl, 9, fe_to_mont(fe_load<FrParams>(in + T_TOKEN)));
+    if (lane == 6) w9_put_fe(wl, 10, fe_to_mont(fe_load<FrParams>(in + T_PAY_COMMITMENT)));
+    if (lane == 7) w9_put_fe(wl, 11, fe_to_mont(fe_load<FrParams>(in + T_PAY_AMOUNT)));
+    if (lane == 8) w9_put_fe(wl, 12, fe_to_mont(fe_load<FrParams>(in + T_CHANGE_COMMITMENT)));
+    if (lane == 9) w9_put_fe(wl, 13, chg.value());
+    if (lane == 10) w9_put_fe(wl, 14 + 2 * depth, fe_sqr(chain_id));
+    for (int l = lane; l < depth; l += 64) {
+      w9_put_fe(wl, 14 + l, fe_to_mont(fe_load<FrParams>(in + (size_t)(T_REC + l) * 32)));
+      w9_put_fe(wl, 14 + depth + l, ((index >> l) & 1) ? Fr::one() : Fr::zero());
+    }
+    for (int i = lane; i < 2 * T_BITS; i += 64) w9_put_fe(wl, 15 + 2 * depth + i, transfer_bit_wire(chg, i));
+    return;
+  }
+  const uint32_t nj = w9_modulus_limb<FrParams>(lane);
+  // job 0 nullifier (gadget 0, the same wires again in gadget 3), 1 amount, 2 pay_amount, 3 change, 4 pay_commitment, 5 change_commitment
+  Fr l_fe;
+  uint32_t wbase, dup = 0;
+  int slot;
+  if (job >= 6) {
+    const int lvl = job - 6;
+    if (!((index >> lvl) & 1)) return;  // the path node is the LEFT input of this level: its first permutation is the chain's
+    l_fe = fe_to_mont(fe_load<FrParams>(in + (size_t)(T_REC + lvl) * 32));
+    wbase = tw9_gadget_base(fgw, depth, 4 + lvl);
+    slot = lvl;
+  } else {
+    const int gadget = job < 2 ? job : job == 2 ? 4 + depth : job == 3 ? 6 + depth : job == 4 ? 5 + depth : 7 + depth;
+    const int off = job == 0 ? T_NULLIFIER : job == 1 ? T_AMOUNT : job == 2 ? T_PAY_AMOUNT : job == 4 ? T_PAY_COMMITMENT : T_CHANGE_COMMITMENT;
+    l_fe = job == 3 ? transfer_change(in).value() : fe_to_mont(fe_load<FrParams>(in + off));
+    wbase = tw9_gadget_base(fgw, depth, gadget);
+    if (job == 0) dup = tw9_gadget_base(fgw, depth, 3);
+    slot = depth + (job < 2 ? job : job + 2);
+  }
+  const uint32_t l_in = w9_spread(l_fe, lane);
+  if (job >= 6) w9_store(wl, wbase - 1, l_in, tid);  // the level's `left` selector wire: the sibling
+  uint32_t* dump = xch + (size_t)(depth + TW9_DUMP) * 9;
+  const uint32_t k1 = l_in + (dup ? w9_permute<FORM, true>(consts9, l_in, 0u, nj, tid, lane, wl, wbase, dup, dump)
+                                  : w9_permute<FORM, false>(consts9, l_in, 0u, nj, tid, lane, wl, wbase, 0u, dump));  // l + E_0(l): < 4 N, lazy limbs
+  w9_store(wl, wbase + 364, k1, tid);
+  if (dup) w9_store(wl, dup + 364, k1, tid);
+  if (tid < 9) xch[(size_t)slot * 9 + lane] = k1;
+}
+
+template <int FORM>
+__global__ void __launch_bounds__(64) k_tw9_second(const uint32_t* __restrict__ consts9, const uint8_t* __restrict__ inputs, int depth, size_t n_wires,
+                                                  uint32_t fgw, uint32_t* __restrict__ wl_all, uint32_t* __restrict__ xch_all) {
+  OG_FILLER_PRIO();
+  const int tid = threadIdx.x, lane = FORM ? w9_row_limb(tid) : tid;
+  const size_t g = blockIdx.x / 5;
+  const int job = (int)(blockIdx.x % 5);  // 0 inner, 1 asset, 2 nullifier_hash, 3 pay_asset, 4 change_asset
+  const uint8_t* in = inputs + g * (size_t)(T_REC + depth) * 32;
+  uint32_t* wl = wl_all + g * n_wires * 9;
+  uint32_t* xch = xch_all + g * (size_t)(depth + TW9_XCH) * 9;
+  const uint32_t nj = w9_modulus_limb<FrParams>(lane);
+  const uint32_t k1 = w9_load(xch + (size_t)(depth + (job == 0 || job == 2 ? 0 : job == 1 ? 1 : job + 1)) * 9, lane);
+  uint32_t r_in = 0;  // nullifier_hash = H(nullifier, 0)
+  if (job == 0) r_in = w9_spread(fe_to_mont(fe_load<FrParams>(in + T_SECRET)), lane);
+  if (job == 1 || job >= 3) r_in = w9_spread(fe_to_mont(fe_load<FrParams>(in + T_TOKEN)), lane);
+  const uint32_t base = tw9_gadget_base(fgw, depth, job == 0 ? 0 : job == 1 ? 1 : job == 2 ? 3 : job == 3 ? 4 + depth : 6 + depth);
+  const uint32_t hout = tw9_second_half<FORM>(consts9, r_in, k1, nj, tid, lane, wl, base, job == 2 ? 2u : base + 729, xch + (size_t)(depth + TW9_DUMP) * 9);
+  if (job == 2) return;  // nullifier_hash: a public wire, nobody's input
+  if (tid < 9) xch[(size_t)(depth + (job < 2 ? 2 + job : 5 + job)) * 9 + lane] = hout;
+}
+
+template <int FORM>
+__global__ void __launch_bounds__(64) k_tw9_chain(const uint32_t* __restrict__ consts9, const uint8_t* __restrict__ inputs, int depth, size_t n_wires,
+                                                 uint32_t fgw, uint32_t* __restrict__ wl_all, uint32_t* __restrict__ xch_all) {
+  OG_FILLER_PRIO();
+  const int tid = threadIdx.x, lane = FORM ? w9_row_limb(tid) : tid;
+  const size_t g = blockIdx.x / 3;
+  const int job = (int)(blockIdx.x % 3);  // 0 the chain, 1 pay_leaf, 2 change_leaf
+  const uint8_t* in = inputs + g * (size_t)(T_REC + depth) * 32;
+  uint32_t* wl = wl_all + g * n_wires * 9;
+  uint32_t* xch = xch_all + g * (size_t)(depth + TW9_XCH) * 9;
+  uint32_t* dump = xch + (size_t)(depth + TW9_DUMP) * 9;
+  const uint32_t nj = w9_modulus_limb<FrParams>(lane);
+  if (job) {  // H(commitment, asset): E_0(commitment) and k1 are k_tw9_first's, the asset is k_tw9_second's
+    const uint32_t base = tw9_gadget_base(fgw, depth, job == 1 ? 5 + depth : 7 + depth);
+    tw9_second_half<FORM>(consts9, w9_load(xch + (size_t)(depth + 7 + job) * 9, lane), w9_load(xch + (size_t)(depth + 5 + job) * 9, lane), nj, tid,
+                          lane, wl, base, 3u + (uint32_t)job, dump);
+    return;
+  }
+  const uint64_t index = *reinterpret_cast<const uint64_t*>(in + T_INDEX);
+  // H(l, r) with both permutations here (a level whose path node is the left input, and the leaf)
+  auto hash_both = [&](uint32_t l_in, uint32_t r_in, uint32_t base, uint32_t out_wire) -> uint32_t {
+    const uint32_t k1 = l_in + w9_permute<FORM, false>(consts9, l_in, 0u, nj, tid, lane, wl, base, 0u, dump);
+    w9_store(wl, base + 364, k1, tid);
+    return tw9_second_half<FORM>(consts9, r_in, k1, nj, tid, lane, wl, base, out_wire, dump);
+  };
+  const uint32_t leaf_base = tw9_gadget_base(fgw, depth, 2);
+  uint32_t cur = hash_both(w9_load(xch + (size_t)(depth + 2) * 9, lane), w9_load(xch + (size_t)(depth + 3) * 9, lane), leaf_base, leaf_base + 729);
+#pragma unroll 1
+  for (int l = 0; l < depth; l++) {
+    const uint32_t base = tw9_gadget_base(fgw, depth, 4 + l);
+    const uint32_t out_wire = l == depth - 1 ? 1u : base + 729;
+    if ((index >> l) & 1) {  // the path node is the right input: E_0(sibling), k1 and the selector wire are k_tw9_first's
+      cur = tw9_second_half<FORM>(consts9, cur, w9_load(xch + (size_t)l * 9, lane), nj, tid, lane, wl, base, out_wire, dump);
+    } else {
+      w9_store(wl, base - 1, cur, tid);  // `left` selector wire: the path node
+      cur = hash_both(cur, w9_spread(fe_to_mont(fe_load<FrParams>(in + (size_t)(T_REC + l) * 32)), lane), base, out_wire);
+    }
+  }
+}
+
+// Boundary check of the transfer records, one lane per field as k_check_split_records: every field canonical (< r), the index inside
+// the tree, amount < 2^128 (field 2), pay_amount < 2^128 and pay_amount <= amount (field 7) -- compared on the integer words, not in
+// the field.  bad[g] = lowest offending field of record g (the caller initialises it to 0xffffffff): 0 nullifier, 1 secret, 2 amount,
+// 3 index, 4 token, 5 chain_id, 6 pay_commitment, 7 pay_amount, 8 change_commitment, 9 + l sibling l.
+__global__ void __launch_bounds__(64) k_check_transfer_records(const uint8_t* __restrict__ inputs, int depth, size_t n, uint32_t* __restrict__ bad) {
+  OG_FILLER_PRIO();
+  const size_t g = blockIdx.y;
+  const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= n || f >= (uint32_t)(T_REC + depth)) return;
+  const uint8_t* rec = inputs + g * (size_t)(T_REC + depth) * 32;
+  const uint8_t* p = rec + (size_t)f * 32;
+  bool ok = fe_lt_modulus(fe_load<FrParams>(p));
+  const uint32_t* w = reinterpret_cast<const uint32_t*>(p);
+  if (f == 2 || f == 7) ok = ok && (w[4] | w[5] | w[6] | w[7]) == 0;
+  if (f == 7) {  // pay_amount <= amount, most significant word first
+    const uint32_t* a = reinterpret_cast<const uint32_t*>(rec + T_AMOUNT);
+    bool gt = false, decided = false;
+    for (int i = 7; i >= 0; i--) {
+      if (!decided && w[i] != a[i]) { gt = w[i] > a[i]; decided = true; }
+    }
+    ok = ok && !gt;
+  }
+  if (f == 3) {  // index
+    ok = ok && (w[2] | w[3] | w[4] | w[5] | w[6] | w[7]) == 0;
+    const uint64_t idx = (uint64_t)w[0] | ((uint64_t)w[1] << 32);
+    ok = ok && (depth >= 64 || (idx >> depth) == 0);
+  }
+  if (!ok) atomicMin(&bad[g], f);
+}
+
+int transfer_shape_query(int depth, uint64_t out[3]) {
+  OG_REQUIRE(depth >= 1 && depth <= 64, "transfer: depth must be 1..64");
+  const TransferShape s = transfer_shape(depth);
+  out[0] = s.n_wires; out[1] = s.n_constraints; out[2] = T_PUB;
+  return OG_OK;
+}
+
+// OG_ERR_INVALID names the first malformed record and its lowest offending field (`base` = index of record 0 in the caller's
+// batch); blocking
+int transfer_records_ok(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, size_t base) {
+  OG_REQUIRE(depth >= 1 && depth <= 64, "transfer: depth must be 1..64");
+  OG_REQUIRE(n <= 65535, "transfer: at most 65535 records per call");  // (the record index is grid.y)
+  if (n == 0) return OG_OK;
+  uint32_t* bad_d = nullptr;
+  OG_TRY(arena_get(ctx, "tr.bad", n * 4, (void**)&bad_d));
+  OG_HIP(hipMemsetAsync(bad_d, 0xff, n * 4, ctx->stream));
+  hipLaunchKernelGGL(k_check_transfer_records, dim3(grid_for(T_REC + depth, 64), (unsigned)n), dim3(64), 0, ctx->stream, inputs_d, depth, n, bad_d);
+  OG_HIP(hipGetLastError());
+  std::vector<uint32_t> bad(n);
+  OG_HIP(hipMemcpyAsync(bad.data(), bad_d, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+  OG_HIP(hipStreamSynchronize(ctx->stream));
+  static const char* names[T_REC] = {"nullifier", "secret", "amount", "index", "token", "chain_id", "pay_commitment", "pay_amount", "change_commitment"};
+  for (size_t g = 0; g < n; g++)
+    if (bad[g] != 0xffffffffu) {
+      const std::string name = bad[g] < (uint32_t)T_REC ? std::string(names[bad[g]]) : "sibling " + std::to_string(bad[g] - T_REC);
+      set_error("og_transfer: input record " + std::to_string(base + g) + ": field " + std::to_string(bad[g]) + " (" + name +
+                ") is not a valid value (>= r, an index outside the tree, an amount >= 2^128, or pay_amount > amount)");
+      return OG_ERR_INVALID;
+    }
+  return OG_OK;
+}
+
+// records (checked: transfer_records_ok) -> n x n_wires x 32 B canonical.  The wave-wide walk for calls of at most 512 requests -- the
+// rule and the hooks of withdraw_witness (OG_WITNESS_W9 = 0 | 1 forces either way, OG_WITNESS_W9_MAX moves the bound, OG_W9_ROWS picks
+// the round's form; hooks builds only) --, the lane-local kernel for batches: there a wave per permutation would be paid out of the
+// prover's accumulations
+int transfer_witness(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, uint8_t* out_d) {
+  OG_REQUIRE(depth >= 1 && depth <= 64, "transfer: depth must be 1..64");
+  OG_REQUIRE(n <= 65535, "transfer: at most 65535 witnesses per call");
+  if (n == 0) return OG_OK;
+  const TransferShape s = transfer_shape(depth);
+  ProfScope ps(ctx, PROF_WITNESS, (double)n);
+  const bool w9 = OG_HOOK_SET("OG_WITNESS_W9") ? OG_HOOK_INT("OG_WITNESS_W9", 1) != 0
+                                               : std::max(n, ctx->call_requests) <= (size_t)OG_HOOK_INT("OG_WITNESS_W9_MAX", 512);
+  if (w9) {
+    uint32_t *wl = nullptr, *xch = nullptr;
+    OG_TRY(arena_get(ctx, "wit.w9.limbs", n * (size_t)s.n_wires * 36, (void**)&wl));
+    OG_TRY(arena_get(ctx, "wit.w9.xch", n * (size_t)(depth + TW9_XCH) * 36, (void**)&xch));
+    const uint32_t* c9 = (const uint32_t*)ctx->mimc_consts9_d;
+    OG_W9_LAUNCH(k_tw9_first, w9_rows(), dim3((unsigned)(n * (size_t)(7 + depth))), dim3(64), 0, ctx->stream, c9, inputs_d, depth, (size_t)s.n_wires,
+                 (uint32_t)s.first_gadget_wire, wl, xch);
+    OG_W9_LAUNCH(k_tw9_second, w9_rows(), dim3((unsigned)(n * 5)), dim3(64), 0, ctx->stream, c9, inputs_d, depth, (size_t)s.n_wires,
+                 (uint32_t)s.first_gadget_wire, wl, xch);
+    OG_W9_LAUNCH(k_tw9_chain, w9_rows(), dim3((unsigned)(n * 3)), dim3(64), 0, ctx->stream, c9, inputs_d, depth, (size_t)s.n_wires,
+                 (uint32_t)s.first_gadget_wire, wl, xch);
+    OG_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_wires_from_limbs, dim3(grid_for(s.n_wires, 256), (unsigned)n), dim3(256), 0, ctx->stream, (const uint32_t*)wl, out_d,
+                       (size_t)s.n_wires, (uint32_t)s.n_wires);
+    OG_HIP(hipGetLastError());
+    return OG_OK;
+  }
+  hipLaunchKernelGGL(k_transfer_core, dim3(grid_for(n, 64)), dim3(64), 0, ctx->stream, (const uint32_t*)ctx->mimc_consts_d, inputs_d, depth,
+                     (size_t)s.n_wires, (uint32_t)s.first_bit_wire, n, out_d);
   OG_HIP(hipGetLastError());
   hipLaunchKernelGGL(k_wires_from_mont, dim3(grid_for(s.n_wires, 256), (unsigned)n), dim3(256), 0, ctx->stream, out_d, (size_t)s.n_wires,
                      (uint32_t)s.n_wires, 1u);
