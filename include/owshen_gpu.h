@@ -379,9 +379,11 @@ int og_deposit_prove_batch_d(og_ctx* ctx, const og_pk* pk, const uint8_t* inputs
  * OG_ERR_INVALID, before anything is proved: a malformed record; og_last_error names the record and its lowest offending field
  * ("input record 3: field 4 (amount_out)"; 0 nullifier, 1 secret, 2 amount, 3 recipient, 4 amount_out, 5 index, 6 token,
  * 7 chain_id, 8 change_commitment, 9 + l sibling l): any field >= r; an index that does not fit the tree; field 2 if amount >=
- * 2^128; field 4 if amount_out >= 2^128 or amount_out > amount (compared as integers).  There is no submit / job form, no
- * multi-GPU form and no window-sharded form of this statement, and og_set_host_chains does not change how its witnesses are
- * generated. */
+ * 2^128; field 4 if amount_out >= 2^128 or amount_out > amount (compared as integers).
+ * The witness generator has two walks with the same bytes: one lane per request for batches, and for calls of at most 512 requests
+ * the wave-wide form of the withdraw statement -- a permutation per wave in three launches, the four permutations of the change
+ * note beside the dependent chain, which is as long as withdraw's.  There is no submit / job form, no multi-GPU form and no
+ * window-sharded form of this statement, and og_set_host_chains does not change how its witnesses are generated. */
 int og_split_shape(int depth, uint64_t shape[3]);
 int og_split_witness_d(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, uint8_t* witness_out_d);
 int og_split_prove_batch_d(og_ctx* ctx, const og_pk* pk, int depth, const uint8_t* inputs_d, size_t n, const uint8_t* rs,
@@ -419,10 +421,12 @@ int og_split_prove_batch_d(og_ctx* ctx, const og_pk* pk, int depth, const uint8_
  * amount_a + amount_b >= 2^128 (compared as integers); field 4 if nullifier_b == nullifier_a (nh_diff_inv would not exist).
  * Two notes whose walks end in DIFFERENT roots cannot be seen at that boundary: og_join_witness_d fills the root wire from note
  * a's walk, and og_join_prove_batch_d answers OG_ERR_UNSATISFIED through the prover's row check.
- * The witness generator gives every request two lanes, one per note, through one rolled permutation body.  Out of scope for this
- * statement: the lane-pair round (t^4 beside t^3), the wave-per-request walk, the wave-wide (w9) form and host chains
- * (og_set_host_chains does not change how its witnesses are generated); there is no submit / job form, no multi-GPU form and no
- * window-sharded form of the call. */
+ * The witness generator has two walks with the same bytes.  For batches every request gets two lanes, one per note, through one
+ * rolled permutation body.  For calls of at most 512 requests it is the wave-wide form of the withdraw statement -- a permutation
+ * per wave in three launches, the two notes' chains side by side (each as long as withdraw's), the joined note's four permutations
+ * and nh_diff_inv beside them; there too the root wire is note a's alone.  Out of scope for this statement: the lane-pair round
+ * (t^4 beside t^3), the wave-per-request walk and host chains (og_set_host_chains does not change how its witnesses are
+ * generated); there is no submit / job form, no multi-GPU form and no window-sharded form of the call. */
 int og_join_shape(int depth, uint64_t shape[3]);
 int og_join_witness_d(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, uint8_t* witness_out_d);
 int og_join_prove_batch_d(og_ctx* ctx, const og_pk* pk, int depth, const uint8_t* inputs_d, size_t n, const uint8_t* rs,
@@ -462,7 +466,7 @@ int og_join_prove_batch_d(og_ctx* ctx, const og_pk* pk, int depth, const uint8_t
  * output notes beside the dependent chain, which is as long as withdraw's.  Out of scope for this statement: the lane-pair round
  * and the wave-per-request walk, host chains (og_set_host_chains does not change how its witnesses are generated), a submit / job
  * form, a multi-GPU form and a window-sharded form of the call, and Rust and Solidity bindings (ffi/ and contracts/ are frozen).
- * split and join have no wave-wide walk yet; this statement's three launches are the template for them. */
+ * split and join take the same three launches for calls of the same size. */
 int og_transfer_shape(int depth, uint64_t shape[3]);
 int og_transfer_witness_d(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, uint8_t* witness_out_d);
 int og_transfer_prove_batch_d(og_ctx* ctx, const og_pk* pk, int depth, const uint8_t* inputs_d, size_t n, const uint8_t* rs,

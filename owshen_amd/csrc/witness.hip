@@ -9,8 +9,10 @@
 //   k_withdraw_pad   one lane per padding unit (a 3-wire gate or a 64-gate chained segment)
 //   k_deposit_witness / k_split_core   the deposit and the split statement (further down), one lane per request
 //   k_join_core      the join statement: two lanes per request, one per note
-//   k_transfer_core / k_tw9_*   the transfer statement (at the end): one lane per request for batches, a permutation per wave in three
+//   k_transfer_core / k_tw9_*   the transfer statement (near the end): one lane per request for batches, a permutation per wave in three
 //                    launches for calls of at most 512 requests
+//   k_sw9_* / k_jw9_*   the wave-wide walk of split and of join (at the end, behind transfer's, whose bodies they share): three launches
+//                    each, for calls of at most 512 requests; k_split_core / k_join_core stay the form for batches
 //
 // Input record per proof, (8 + depth) x 32 B canonical LE:
 //   nullifier | secret | amount | recipient | pad_seed | index (u64 in the low bytes) | token | chain_id | siblings[depth]
@@ -935,6 +937,9 @@ __device__ __forceinline__ Fr gadget_wires(const uint32_t* __restrict__ consts, 
 //   8 nullifier | 9 secret | 10 amount | 11 change_commitment | 12 change | 13.. siblings[D] | index bits[D] | recipient^2 | chain_id^2
 //   | amount_out bits[128] (LSB first) | change bits[128] | the gadgets: inner, asset, leaf, nullifier_hash (out = wire 2), level
 //   0..D-1 (the last one's out = wire 1), change_asset = H(change, token), change_leaf = H(change_commitment, change_asset) (out = wire 7)
+// Two walks: k_split_core (one lane per request, the form for batches) and k_sw9_* (a permutation per wave in three launches, for
+// calls of at most 512 requests: at the end of the file).  NOT built for this statement: the t^4 | t^3 lane-pair round, the
+// wave-per-request walk, host chains.
 constexpr int S_PUB = 7;
 constexpr int S_REC = 9;  // fields of a split record before the siblings
 constexpr int S_BITS = 128;
@@ -1098,13 +1103,21 @@ int split_records_ok(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, 
   return OG_OK;
 }
 
-// records (checked: split_records_ok) -> n x n_wires x 32 B canonical
+static int split_walk_w9(og_ctx* ctx, int depth, const SplitShape& s, const uint8_t* inputs_d, size_t n, uint8_t* out_d);  // k_sw9_*: at the end of the file
+
+// records (checked: split_records_ok) -> n x n_wires x 32 B canonical.  The wave-wide walk (k_sw9_*, beside transfer's k_tw9_* at the end
+// of the file) for calls of at most 512 requests -- the rule and the hooks of transfer_witness, verbatim (OG_WITNESS_W9 = 0 | 1 forces
+// either way, OG_WITNESS_W9_MAX moves the bound, OG_W9_ROWS picks the round's form; hooks builds only) --, the lane-local kernel for
+// batches.  The wave-wide walk's limb buffer is n x n_wires x 36 B from the arena: 0.52 GB at 512 depth-32 requests
 int split_witness(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, uint8_t* out_d) {
   OG_REQUIRE(depth >= 1 && depth <= 64, "split: depth must be 1..64");
   OG_REQUIRE(n <= 65535, "split: at most 65535 witnesses per call");
   if (n == 0) return OG_OK;
   const SplitShape s = split_shape(depth);
   ProfScope ps(ctx, PROF_WITNESS, (double)n);
+  const bool w9 = OG_HOOK_SET("OG_WITNESS_W9") ? OG_HOOK_INT("OG_WITNESS_W9", 1) != 0
+                                               : std::max(n, ctx->call_requests) <= (size_t)OG_HOOK_INT("OG_WITNESS_W9_MAX", 512);
+  if (w9) return split_walk_w9(ctx, depth, s, inputs_d, n, out_d);
   hipLaunchKernelGGL(k_split_core, dim3(grid_for(n, 64)), dim3(64), 0, ctx->stream, (const uint32_t*)ctx->mimc_consts_d, inputs_d, depth,
                      (size_t)s.n_wires, (uint32_t)s.first_bit_wire, n, out_d);
   OG_HIP(hipGetLastError());
@@ -1132,7 +1145,9 @@ int split_witness(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, uin
 //   first) | amount_b bits[128] | sum bits[128] | the gadgets of note a: inner, asset, leaf, nullifier_hash (out = wire 2), level
 //   0..D-1 (the last one's out = wire 1) | the same gadgets of note b (outs = wire 3 and wire 1) | out_asset = H(sum, token),
 //   out_leaf = H(out_commitment, out_asset) (out = wire 5)
-// NOT built for this statement (as for split): the t^4 | t^3 lane-pair round, the wave-per-request walk, the w9 form, host chains.
+// Two walks: k_join_core (two lanes per request, the form for batches) and k_jw9_* (a permutation per wave in three launches, for
+// calls of at most 512 requests: at the end of the file).  NOT built for this statement (as for split): the t^4 | t^3 lane-pair
+// round, the wave-per-request walk, host chains.
 constexpr int J_PUB = 5;
 constexpr int J_REC = 11;  // fields of a join record before the siblings
 constexpr int J_BITS = 128;
@@ -1353,13 +1368,20 @@ int join_records_ok(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, s
   return OG_OK;
 }
 
-// records (checked: join_records_ok) -> n x n_wires x 32 B canonical; two lanes per request
+static int join_walk_w9(og_ctx* ctx, int depth, const JoinShape& s, const uint8_t* inputs_d, size_t n, uint8_t* out_d);  // k_jw9_*: at the end of the file
+
+// records (checked: join_records_ok) -> n x n_wires x 32 B canonical.  The wave-wide walk (k_jw9_*, at the end of the file) for calls of
+// at most 512 requests -- the rule and the hooks of transfer_witness, verbatim --, two lanes per request (k_join_core) for batches.  The
+// wave-wide walk's limb buffer is n x n_wires x 36 B from the arena: 1.0 GB at 512 depth-32 requests
 int join_witness(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, uint8_t* out_d) {
   OG_REQUIRE(depth >= 1 && depth <= 64, "join: depth must be 1..64");
   OG_REQUIRE(n <= 65535, "join: at most 65535 witnesses per call");
   if (n == 0) return OG_OK;
   const JoinShape s = join_shape(depth);
   ProfScope ps(ctx, PROF_WITNESS, (double)n);
+  const bool w9 = OG_HOOK_SET("OG_WITNESS_W9") ? OG_HOOK_INT("OG_WITNESS_W9", 1) != 0
+                                               : std::max(n, ctx->call_requests) <= (size_t)OG_HOOK_INT("OG_WITNESS_W9_MAX", 512);
+  if (w9) return join_walk_w9(ctx, depth, s, inputs_d, n, out_d);
   hipLaunchKernelGGL(k_join_core, dim3(grid_for(2 * n, 64)), dim3(64), 0, ctx->stream, (const uint32_t*)ctx->mimc_consts_d, inputs_d, depth,
                      (size_t)s.n_wires, (uint32_t)s.first_bit_wire, (uint32_t)s.note_gadget_wires, n, out_d);
   OG_HIP(hipGetLastError());
@@ -1542,6 +1564,57 @@ __device__ __forceinline__ uint32_t tw9_second_half(const uint32_t* __restrict__
   return h;
 }
 
+// The chain block of split and of join (k_sw9_chain, k_jw9_chain: further down), k_tw9_chain's walk with the record and the note as
+// parameters: leaf = H(inner, asset) (xch slots vals[0], vals[1]), then per level two permutations (the path node is the left input)
+// or one (right: E_0(sibling), k1 and the selector wire came from the first launch, xch slot lvls[l]).  `fgw` is the first gadget
+// wire of the note, `sibs` its siblings.  root = false (join's note b): the last level's output is nobody's wire -- wire 1 is note
+// a's -- so its second permutation leaves its round wires and nothing else.  (k_tw9_chain keeps its own text: through here it
+// compiles to 41 VGPRs instead of 43, and the existing rows of the kernel-resource table stay what they are.)
+template <int FORM>
+__device__ __forceinline__ void w9_note_chain(const uint32_t* __restrict__ consts9, const uint8_t* __restrict__ sibs, uint64_t index, int depth,
+                                              uint32_t fgw, bool root, uint32_t* __restrict__ wl, const uint32_t* lvls, const uint32_t* vals,
+                                              uint32_t* dump, uint32_t nj, int tid, int lane) {
+  const uint32_t leaf_base = tw9_gadget_base(fgw, depth, 2);
+  const uint32_t inner = w9_load(vals, lane);
+  const uint32_t leaf_k1 = inner + w9_permute<FORM, false>(consts9, inner, 0u, nj, tid, lane, wl, leaf_base, 0u, dump);
+  w9_store(wl, leaf_base + 364, leaf_k1, tid);
+  uint32_t cur = tw9_second_half<FORM>(consts9, w9_load(vals + 9, lane), leaf_k1, nj, tid, lane, wl, leaf_base, leaf_base + 729, dump);
+  // a level's second permutation, once per branch below as in k_tw9_chain: a k1 that was LOADED is waited for inside the round loop
+  // (vmcnt(0) at its top, i.e. for the round's own stores too), and shared text would make the levels with a computed k1 pay that as well
+  auto level_rest = [&](uint32_t r_in, uint32_t k1, uint32_t base, int l) -> uint32_t {
+    if (l == depth - 1 && !root) return w9_permute<FORM, false>(consts9, r_in, k1, nj, tid, lane, wl, base + 365, 0u, dump);
+    return tw9_second_half<FORM>(consts9, r_in, k1, nj, tid, lane, wl, base, l == depth - 1 ? 1u : base + 729, dump);
+  };
+#pragma unroll 1
+  for (int l = 0; l < depth; l++) {
+    const uint32_t base = tw9_gadget_base(fgw, depth, 4 + l);
+    if ((index >> l) & 1) {  // the path node is the right input
+      cur = level_rest(cur, w9_load(lvls + (size_t)l * 9, lane), base, l);
+    } else {
+      w9_store(wl, base - 1, cur, tid);  // `left` selector wire: the path node
+      const uint32_t k1 = cur + w9_permute<FORM, false>(consts9, cur, 0u, nj, tid, lane, wl, base, 0u, dump);
+      w9_store(wl, base + 364, k1, tid);
+      cur = level_rest(w9_spread(fe_to_mont(fe_load<FrParams>(sibs + (size_t)l * 32)), lane), k1, base, l);
+    }
+  }
+}
+
+// the first permutation of a gadget whose left input is known before the walk (k_tw9_first, k_sw9_first, k_jw9_first): k1 = l + E_0(l)
+// (< 4 N, lazy limbs) with its round wires at wbase (and at dup, if non-zero: a nullifier's, which is the left input of two gadgets),
+// k1 into xch slot `slot`; selector: l is a level's sibling, which is also that level's `left` wire
+template <int FORM>
+__device__ __forceinline__ void w9_first_half(const uint32_t* __restrict__ consts9, const Fr& l_fe, uint32_t nj, int tid, int lane,
+                                              uint32_t* __restrict__ wl, uint32_t wbase, uint32_t dup, bool selector, uint32_t* __restrict__ slot,
+                                              uint32_t* __restrict__ dump) {
+  const uint32_t l_in = w9_spread(l_fe, lane);
+  if (selector) w9_store(wl, wbase - 1, l_in, tid);  // a level's `left` selector wire: the sibling
+  const uint32_t k1 = l_in + (dup ? w9_permute<FORM, true>(consts9, l_in, 0u, nj, tid, lane, wl, wbase, dup, dump)
+                                  : w9_permute<FORM, false>(consts9, l_in, 0u, nj, tid, lane, wl, wbase, 0u, dump));
+  w9_store(wl, wbase + 364, k1, tid);
+  if (dup) w9_store(wl, dup + 364, k1, tid);
+  if (tid < 9) slot[lane] = k1;
+}
+
 template <int FORM>
 __global__ void __launch_bounds__(64) k_tw9_first(const uint32_t* __restrict__ consts9, const uint8_t* __restrict__ inputs, int depth, size_t n_wires,
                                                  uint32_t fgw, uint32_t* __restrict__ wl_all, uint32_t* __restrict__ xch_all) {
@@ -1594,14 +1667,7 @@ __global__ void __launch_bounds__(64) k_tw9_first(const uint32_t* __restrict__ c
     if (job == 0) dup = tw9_gadget_base(fgw, depth, 3);
     slot = depth + (job < 2 ? job : job + 2);
   }
-  const uint32_t l_in = w9_spread(l_fe, lane);
-  if (job >= 6) w9_store(wl, wbase - 1, l_in, tid);  // the level's `left` selector wire: the sibling
-  uint32_t* dump = xch + (size_t)(depth + TW9_DUMP) * 9;
-  const uint32_t k1 = l_in + (dup ? w9_permute<FORM, true>(consts9, l_in, 0u, nj, tid, lane, wl, wbase, dup, dump)
-                                  : w9_permute<FORM, false>(consts9, l_in, 0u, nj, tid, lane, wl, wbase, 0u, dump));  // l + E_0(l): < 4 N, lazy limbs
-  w9_store(wl, wbase + 364, k1, tid);
-  if (dup) w9_store(wl, dup + 364, k1, tid);
-  if (tid < 9) xch[(size_t)slot * 9 + lane] = k1;
+  w9_first_half<FORM>(consts9, l_fe, nj, tid, lane, wl, wbase, dup, job >= 6, xch + (size_t)slot * 9, xch + (size_t)(depth + TW9_DUMP) * 9);
 }
 
 template <int FORM>
@@ -1761,6 +1827,346 @@ int transfer_witness(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, 
   OG_HIP(hipGetLastError());
   hipLaunchKernelGGL(k_wires_from_mont, dim3(grid_for(s.n_wires, 256), (unsigned)n), dim3(256), 0, ctx->stream, out_d, (size_t)s.n_wires,
                      (uint32_t)s.n_wires, 1u);
+  OG_HIP(hipGetLastError());
+  return OG_OK;
+}
+
+// ---- the wave-wide walk of the split and the join statement ---------------------------------------------------------------------------
+// The same decomposition as k_tw9_* (its header: ONE permutation per one-wave workgroup, three launches, values between them as nine
+// lazy limbs in xch, wires as nine limbs in wl for k_wires_from_limbs, every hash output through w9_renorm before it is anybody's
+// input, unconditional stores with a dump slot for the lanes without a limb).  split's gadgets lie exactly where transfer's first
+// 6 + depth lie (change_asset, change_leaf where pay_asset, pay_leaf are), so tw9_gadget_base serves it as it is; a join note's
+// gadgets are a transfer's first 4 + depth from the note's own first wire, and the two output gadgets follow note b's levels as
+// gadgets 4 + depth and 5 + depth of note b would.  The bodies the three statements share are above k_tw9_first: tw9_second_half,
+// w9_first_half, w9_note_chain.
+//
+// split:
+//   k_sw9_first   grid n x (5 + depth): E_0 of nullifier (wires of gadgets 0 and 3), amount, change (from the record's integer words,
+//                 as k_split_core) and change_commitment; E_0(sibling_l) of every level whose path node is the RIGHT input; one
+//                 workgroup for the wires that are inputs, the two squares, the index bits and the 256 bit wires
+//   k_sw9_second  grid n x 4: the second permutations of inner, asset, nullifier_hash (-> wire 2), change_asset
+//   k_sw9_chain   grid n x 2: block 0 is the chain (leaf, then the levels: k_w9_chain's work, exactly as long as withdraw's); block 1
+//                 is the second permutation of change_leaf (-> wire 7)
+// xch slots per request beyond the levels: [depth + 0] k1 of inner / nullifier_hash, [1] k1 of asset, [2] inner, [3] asset, [4] k1 of
+// change_asset, [5] k1 of change_leaf, [6] change_asset, [7 .. 10]: 36 words nobody reads -- where the lanes without a limb store
+// (w9_permute `dump`)
+constexpr int SW9_XCH = 11, SW9_DUMP = 7;
+constexpr int S_NULLIFIER = 0, S_SECRET = 32, S_AMOUNT = 64, S_RECIPIENT = 96, S_AMOUNT_OUT = 128, S_INDEX = 160, S_TOKEN = 192, S_CHAIN = 224,
+              S_CHANGE_COMMITMENT = 256;
+// amount_out and change = amount - amount_out as 64-bit halves (transfer's pair: p is what leaves the note, c what stays)
+__device__ __forceinline__ TransferChange split_change(const uint8_t* in) {
+  const uint64_t a_lo = *reinterpret_cast<const uint64_t*>(in + S_AMOUNT), a_hi = *reinterpret_cast<const uint64_t*>(in + S_AMOUNT + 8);
+  TransferChange c;
+  c.p_lo = *reinterpret_cast<const uint64_t*>(in + S_AMOUNT_OUT);
+  c.p_hi = *reinterpret_cast<const uint64_t*>(in + S_AMOUNT_OUT + 8);
+  c.c_lo = a_lo - c.p_lo;
+  c.c_hi = a_hi - c.p_hi - (a_lo < c.p_lo ? 1u : 0u);
+  return c;
+}
+
+template <int FORM>
+__global__ void __launch_bounds__(64) k_sw9_first(const uint32_t* __restrict__ consts9, const uint8_t* __restrict__ inputs, int depth, size_t n_wires,
+                                                 uint32_t fgw, uint32_t* __restrict__ wl_all, uint32_t* __restrict__ xch_all) {
+  OG_FILLER_PRIO();
+  const int jobs = 5 + depth, tid = threadIdx.x, lane = FORM ? w9_row_limb(tid) : tid;
+  const size_t g = blockIdx.x / jobs;
+  const int job = (int)(blockIdx.x % jobs);
+  const uint8_t* in = inputs + g * (size_t)(S_REC + depth) * 32;
+  uint32_t* wl = wl_all + g * n_wires * 9;
+  uint32_t* xch = xch_all + g * (size_t)(depth + SW9_XCH) * 9;
+  const uint64_t index = *reinterpret_cast<const uint64_t*>(in + S_INDEX);
+  if (job == 4 + depth) {  // the wires that are inputs, the squares, the index bits and the 256 bit wires: lane-local values, a lane per wire
+    const int lane = tid;
+    const TransferChange chg = split_change(in);
+    const Fr recipient = fe_to_mont(fe_load<FrParams>(in + S_RECIPIENT)), chain_id = fe_to_mont(fe_load<FrParams>(in + S_CHAIN));
+    if (lane == 0) w9_put_fe(wl, 0, Fr::one());
+    if (lane == 1) w9_put_fe(wl, 3, recipient);
+    if (lane == 2) w9_put_fe(wl, 4, fe_to_mont(fe_load<FrParams>(in + S_AMOUNT_OUT)));
+    if (lane == 3) w9_put_fe(wl, 5, fe_to_mont(fe_load<FrParams>(in + S_TOKEN)));
+    if (lane == 4) w9_put_fe(wl, 6, chain_id);
+    if (lane == 5) w9_put_fe(wl, 8, fe_to_mont(fe_load<FrParams>(in + S_NULLIFIER)));
+    if (lane == 6) w9_put_fe(wl, 9, fe_to_mont(fe_load<FrParams>(in + S_SECRET)));
+    if (lane == 7) w9_put_fe(wl, 10, fe_to_mont(fe_load<FrParams>(in + S_AMOUNT)));
+    if (lane == 8) w9_put_fe(wl, 11, fe_to_mont(fe_load<FrParams>(in + S_CHANGE_COMMITMENT)));
+    if (lane == 9) w9_put_fe(wl, 12, chg.value());
+    if (lane == 10) w9_put_fe(wl, 13 + 2 * depth, fe_sqr(recipient));
+    if (lane == 11) w9_put_fe(wl, 14 + 2 * depth, fe_sqr(chain_id));
+    for (int l = lane; l < depth; l += 64) {
+      w9_put_fe(wl, 13 + l, fe_to_mont(fe_load<FrParams>(in + (size_t)(S_REC + l) * 32)));
+      w9_put_fe(wl, 13 + depth + l, ((index >> l) & 1) ? Fr::one() : Fr::zero());
+    }
+    for (int i = lane; i < 2 * S_BITS; i += 64) w9_put_fe(wl, 15 + 2 * depth + i, transfer_bit_wire(chg, i));  // amount_out, then change
+    return;
+  }
+  const uint32_t nj = w9_modulus_limb<FrParams>(lane);
+  // job 0 nullifier (gadget 0, the same wires again in gadget 3), 1 amount, 2 change, 3 change_commitment, 4 + l sibling l
+  Fr l_fe;
+  uint32_t wbase, dup = 0;
+  int slot;
+  if (job >= 4) {
+    const int lvl = job - 4;
+    if (!((index >> lvl) & 1)) return;  // the path node is the LEFT input of this level: its first permutation is the chain's
+    l_fe = fe_to_mont(fe_load<FrParams>(in + (size_t)(S_REC + lvl) * 32));
+    wbase = tw9_gadget_base(fgw, depth, 4 + lvl);
+    slot = lvl;
+  } else {
+    l_fe = job == 2 ? split_change(in).value() : fe_to_mont(fe_load<FrParams>(in + (job == 0 ? S_NULLIFIER : job == 1 ? S_AMOUNT : S_CHANGE_COMMITMENT)));
+    wbase = tw9_gadget_base(fgw, depth, job < 2 ? job : 2 + depth + job);
+    if (job == 0) dup = tw9_gadget_base(fgw, depth, 3);
+    slot = depth + (job < 2 ? job : job + 2);
+  }
+  w9_first_half<FORM>(consts9, l_fe, nj, tid, lane, wl, wbase, dup, job >= 4, xch + (size_t)slot * 9, xch + (size_t)(depth + SW9_DUMP) * 9);
+}
+
+template <int FORM>
+__global__ void __launch_bounds__(64) k_sw9_second(const uint32_t* __restrict__ consts9, const uint8_t* __restrict__ inputs, int depth, size_t n_wires,
+                                                  uint32_t fgw, uint32_t* __restrict__ wl_all, uint32_t* __restrict__ xch_all) {
+  OG_FILLER_PRIO();
+  const int tid = threadIdx.x, lane = FORM ? w9_row_limb(tid) : tid;
+  const size_t g = blockIdx.x / 4;
+  const int job = (int)(blockIdx.x % 4);  // 0 inner, 1 asset, 2 nullifier_hash, 3 change_asset
+  const uint8_t* in = inputs + g * (size_t)(S_REC + depth) * 32;
+  uint32_t* wl = wl_all + g * n_wires * 9;
+  uint32_t* xch = xch_all + g * (size_t)(depth + SW9_XCH) * 9;
+  const uint32_t nj = w9_modulus_limb<FrParams>(lane);
+  const uint32_t k1 = w9_load(xch + (size_t)(depth + (job == 1 ? 1 : job == 3 ? 4 : 0)) * 9, lane);
+  uint32_t r_in = 0;  // nullifier_hash = H(nullifier, 0)
+  if (job == 0) r_in = w9_spread(fe_to_mont(fe_load<FrParams>(in + S_SECRET)), lane);
+  if (job == 1 || job == 3) r_in = w9_spread(fe_to_mont(fe_load<FrParams>(in + S_TOKEN)), lane);
+  const uint32_t base = tw9_gadget_base(fgw, depth, job == 2 ? 3 : job == 3 ? 4 + depth : job);
+  const uint32_t hout = tw9_second_half<FORM>(consts9, r_in, k1, nj, tid, lane, wl, base, job == 2 ? 2u : base + 729, xch + (size_t)(depth + SW9_DUMP) * 9);
+  if (job == 2) return;  // nullifier_hash: a public wire, nobody's input
+  if (tid < 9) xch[(size_t)(depth + (job < 2 ? 2 + job : 6)) * 9 + lane] = hout;
+}
+
+template <int FORM>
+__global__ void __launch_bounds__(64) k_sw9_chain(const uint32_t* __restrict__ consts9, const uint8_t* __restrict__ inputs, int depth, size_t n_wires,
+                                                 uint32_t fgw, uint32_t* __restrict__ wl_all, uint32_t* __restrict__ xch_all) {
+  OG_FILLER_PRIO();
+  const int tid = threadIdx.x, lane = FORM ? w9_row_limb(tid) : tid;
+  const size_t g = blockIdx.x / 2;
+  const uint8_t* in = inputs + g * (size_t)(S_REC + depth) * 32;
+  uint32_t* wl = wl_all + g * n_wires * 9;
+  uint32_t* xch = xch_all + g * (size_t)(depth + SW9_XCH) * 9;
+  uint32_t* dump = xch + (size_t)(depth + SW9_DUMP) * 9;
+  const uint32_t nj = w9_modulus_limb<FrParams>(lane);
+  if (blockIdx.x & 1) {  // change_leaf = H(change_commitment, change_asset): k1 is k_sw9_first's, the asset is k_sw9_second's
+    tw9_second_half<FORM>(consts9, w9_load(xch + (size_t)(depth + 6) * 9, lane), w9_load(xch + (size_t)(depth + 5) * 9, lane), nj, tid, lane, wl,
+                          tw9_gadget_base(fgw, depth, 5 + depth), 7u, dump);
+    return;
+  }
+  w9_note_chain<FORM>(consts9, in + (size_t)S_REC * 32, *reinterpret_cast<const uint64_t*>(in + S_INDEX), depth, fgw, true, wl, xch,
+                      xch + (size_t)(depth + 2) * 9, dump, nj, tid, lane);
+}
+
+// The wave-wide walk of n split requests (split_witness decides when).  wl is n x n_wires x 36 B from the arena: 0.52 GB for 512
+// depth-32 requests (28 104 wires each), the largest call that takes this walk by default.
+static int split_walk_w9(og_ctx* ctx, int depth, const SplitShape& s, const uint8_t* inputs_d, size_t n, uint8_t* out_d) {
+  uint32_t *wl = nullptr, *xch = nullptr;
+  OG_TRY(arena_get(ctx, "wit.w9.limbs", n * (size_t)s.n_wires * 36, (void**)&wl));
+  OG_TRY(arena_get(ctx, "wit.w9.xch", n * (size_t)(depth + SW9_XCH) * 36, (void**)&xch));
+  const uint32_t* c9 = (const uint32_t*)ctx->mimc_consts9_d;
+  const uint32_t fgw = (uint32_t)s.first_bit_wire + 2 * S_BITS;
+  OG_W9_LAUNCH(k_sw9_first, w9_rows(), dim3((unsigned)(n * (size_t)(5 + depth))), dim3(64), 0, ctx->stream, c9, inputs_d, depth, (size_t)s.n_wires, fgw,
+               wl, xch);
+  OG_W9_LAUNCH(k_sw9_second, w9_rows(), dim3((unsigned)(n * 4)), dim3(64), 0, ctx->stream, c9, inputs_d, depth, (size_t)s.n_wires, fgw, wl, xch);
+  OG_W9_LAUNCH(k_sw9_chain, w9_rows(), dim3((unsigned)(n * 2)), dim3(64), 0, ctx->stream, c9, inputs_d, depth, (size_t)s.n_wires, fgw, wl, xch);
+  OG_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_wires_from_limbs, dim3(grid_for(s.n_wires, 256), (unsigned)n), dim3(256), 0, ctx->stream, (const uint32_t*)wl, out_d,
+                     (size_t)s.n_wires, (uint32_t)s.n_wires);
+  OG_HIP(hipGetLastError());
+  return OG_OK;
+}
+
+// join:
+//   k_jw9_first   grid n x (7 + 2 depth): E_0 of nullifier_a and nullifier_b (each into its note's gadgets 0 and 3), amount_a, amount_b,
+//                 sum (from the record's integer words, as k_join_core) and out_commitment; E_0(sibling) of every level of either
+//                 walk whose path node is the RIGHT input; one workgroup for the wires that are inputs, chain_id^2, the index bits
+//                 and the 384 bit wires
+//   k_jw9_second  grid n x 7: the second permutations of inner, asset and nullifier_hash of note a (-> wire 2) and of note b (-> wire
+//                 3), and of out_asset.  Both nullifier hashes go into xch as well: they are the inputs of nh_diff_inv
+//   k_jw9_chain   grid n x 4: block 0 is note a's chain, block 1 note b's -- side by side, each as long as withdraw's; wire 1 comes from
+//                 note a's walk ALONE (note b's last level stores its round wires and no output), so a record whose two paths do
+//                 not meet carries note a's root and the prover's row check refuses it (tests/join_cases.py case_different_roots);
+//                 block 2 is the second permutation of out_leaf (-> wire 5); block 3 is nh_diff_inv = 1 / (nullifier_hash_a -
+//                 nullifier_hash_b) -> wire 15, ONE lane-local fe_inv on one lane: ~380 products beside a chain of ~19 000, not
+//                 worth spreading (k_join_core says the same of its own)
+// xch slots per request: [0 .. depth) k1 of note a's levels, [depth .. 2 depth) of note b's; beyond them [2 depth + 0] k1 of inner_a /
+// nullifier_hash_a, [1] k1 of asset_a, [2] inner_a, [3] asset_a, [4] nullifier_hash_a, [5 .. 9] the same five of note b, [10] k1 of
+// out_asset, [11] k1 of out_leaf, [12] out_asset, [13 .. 16]: 36 words nobody reads -- where the lanes without a limb store
+// (w9_permute `dump`)
+constexpr int JW9_XCH = 17, JW9_NOTE = 5, JW9_OUT = 10, JW9_DUMP = 13;
+constexpr int J_NOTE_BYTES = 128, J_NULLIFIER = 0, J_SECRET = 32, J_AMOUNT = 64, J_INDEX = 96;  // a note's fields, from the note's first byte
+constexpr int J_TOKEN = 256, J_CHAIN = 288, J_OUT_COMMITMENT = 320;
+// amount_a, amount_b and sum = amount_a + amount_b on the record's integer words (the records are checked first: the sum is below
+// 2^128), as 64-bit words: a_lo a_hi b_lo b_hi s_lo s_hi
+struct JoinSum {
+  uint64_t w[6];
+  __device__ __forceinline__ Fr value() const {
+    const uint32_t sw[8] = {(uint32_t)w[4], (uint32_t)(w[4] >> 32), (uint32_t)w[5], (uint32_t)(w[5] >> 32), 0u, 0u, 0u, 0u};
+    return fe_to_mont(fe_from_words<FrParams>(sw));
+  }
+  // bit i (0 .. 383) of amount_a | amount_b | sum, as a wire
+  __device__ __forceinline__ Fr bit_wire(int i) const {
+    uint64_t word = 0;
+#pragma unroll
+    for (int k = 0; k < 6; k++) word = (i >> 6) == k ? w[k] : word;
+    return ((word >> (i & 63)) & 1) ? Fr::one() : Fr::zero();
+  }
+};
+__device__ __forceinline__ JoinSum join_sum(const uint8_t* in) {
+  JoinSum s;
+  s.w[0] = *reinterpret_cast<const uint64_t*>(in + J_AMOUNT);
+  s.w[1] = *reinterpret_cast<const uint64_t*>(in + J_AMOUNT + 8);
+  s.w[2] = *reinterpret_cast<const uint64_t*>(in + J_NOTE_BYTES + J_AMOUNT);
+  s.w[3] = *reinterpret_cast<const uint64_t*>(in + J_NOTE_BYTES + J_AMOUNT + 8);
+  s.w[4] = s.w[0] + s.w[2];
+  s.w[5] = s.w[1] + s.w[3] + (s.w[4] < s.w[0] ? 1u : 0u);
+  return s;
+}
+
+template <int FORM>
+__global__ void __launch_bounds__(64) k_jw9_first(const uint32_t* __restrict__ consts9, const uint8_t* __restrict__ inputs, int depth, size_t n_wires,
+                                                 uint32_t fgw, uint32_t ngw, uint32_t* __restrict__ wl_all, uint32_t* __restrict__ xch_all) {
+  OG_FILLER_PRIO();
+  const int jobs = 7 + 2 * depth, tid = threadIdx.x, lane = FORM ? w9_row_limb(tid) : tid;
+  const size_t g = blockIdx.x / jobs;
+  const int job = (int)(blockIdx.x % jobs);
+  const uint8_t* in = inputs + g * (size_t)(J_REC + 2 * depth) * 32;
+  uint32_t* wl = wl_all + g * n_wires * 9;
+  uint32_t* xch = xch_all + g * (size_t)(2 * depth + JW9_XCH) * 9;
+  if (job == 6 + 2 * depth) {  // the wires that are inputs, the square, the index bits and the 384 bit wires: lane-local values, a lane per wire
+    const int lane = tid;
+    const JoinSum sum = join_sum(in);
+    const Fr chain_id = fe_to_mont(fe_load<FrParams>(in + J_CHAIN));
+    if (lane == 0) w9_put_fe(wl, 0, Fr::one());
+    if (lane == 1) w9_put_fe(wl, 4, chain_id);
+    if (lane >= 2 && lane < 8) {  // 6 nullifier_a | 7 secret_a | 8 amount_a | 9 nullifier_b | 10 secret_b | 11 amount_b
+      const int f = lane - 2;
+      w9_put_fe(wl, 4 + lane, fe_to_mont(fe_load<FrParams>(in + (size_t)(f / 3) * J_NOTE_BYTES + (size_t)(f % 3) * 32)));
+    }
+    if (lane == 8) w9_put_fe(wl, 12, fe_to_mont(fe_load<FrParams>(in + J_TOKEN)));
+    if (lane == 9) w9_put_fe(wl, 13, fe_to_mont(fe_load<FrParams>(in + J_OUT_COMMITMENT)));
+    if (lane == 10) w9_put_fe(wl, 14, sum.value());
+    if (lane == 11) w9_put_fe(wl, 16 + 4 * depth, fe_sqr(chain_id));
+    for (int l = lane; l < 2 * depth; l += 64) {  // siblings_a | siblings_b, then the index bits of a | b
+      const int b = l >= depth ? 1 : 0, lvl = l - b * depth;
+      const uint64_t index = *reinterpret_cast<const uint64_t*>(in + (size_t)b * J_NOTE_BYTES + J_INDEX);
+      w9_put_fe(wl, 16 + l, fe_to_mont(fe_load<FrParams>(in + (size_t)(J_REC + l) * 32)));
+      w9_put_fe(wl, 16 + 2 * depth + l, ((index >> lvl) & 1) ? Fr::one() : Fr::zero());
+    }
+    for (int i = lane; i < 3 * J_BITS; i += 64) w9_put_fe(wl, 17 + 4 * depth + i, sum.bit_wire(i));
+    return;
+  }
+  const uint32_t nj = w9_modulus_limb<FrParams>(lane);
+  // job 0 nullifier_a (gadget 0 of note a, the same wires again in its gadget 3), 1 amount_a, 2 nullifier_b, 3 amount_b, 4 sum (out_asset),
+  // 5 out_commitment (out_leaf), 6 + l sibling l of note a, 6 + depth + l sibling l of note b
+  Fr l_fe;
+  uint32_t wbase, dup = 0;
+  int slot;
+  if (job >= 6) {
+    const int b = job - 6 >= depth ? 1 : 0, lvl = job - 6 - b * depth;
+    const uint64_t index = *reinterpret_cast<const uint64_t*>(in + (size_t)b * J_NOTE_BYTES + J_INDEX);
+    if (!((index >> lvl) & 1)) return;  // the path node is the LEFT input of this level: its first permutation is the chain's
+    l_fe = fe_to_mont(fe_load<FrParams>(in + (size_t)(J_REC + b * depth + lvl) * 32));
+    wbase = tw9_gadget_base(fgw + (uint32_t)b * ngw, depth, 4 + lvl);
+    slot = b * depth + lvl;
+  } else if (job >= 4) {
+    l_fe = job == 4 ? join_sum(in).value() : fe_to_mont(fe_load<FrParams>(in + J_OUT_COMMITMENT));
+    wbase = tw9_gadget_base(fgw + ngw, depth, depth + job);  // behind note b's levels: gadgets 4 + depth and 5 + depth from note b's first wire
+    slot = 2 * depth + JW9_OUT + (job - 4);
+  } else {
+    const int b = job >> 1, f = job & 1;  // f = 0 the nullifier, 1 the amount
+    l_fe = fe_to_mont(fe_load<FrParams>(in + (size_t)b * J_NOTE_BYTES + (f ? J_AMOUNT : J_NULLIFIER)));
+    wbase = tw9_gadget_base(fgw + (uint32_t)b * ngw, depth, f);
+    if (!f) dup = tw9_gadget_base(fgw + (uint32_t)b * ngw, depth, 3);
+    slot = 2 * depth + b * JW9_NOTE + f;
+  }
+  w9_first_half<FORM>(consts9, l_fe, nj, tid, lane, wl, wbase, dup, job >= 6, xch + (size_t)slot * 9, xch + (size_t)(2 * depth + JW9_DUMP) * 9);
+}
+
+template <int FORM>
+__global__ void __launch_bounds__(64) k_jw9_second(const uint32_t* __restrict__ consts9, const uint8_t* __restrict__ inputs, int depth, size_t n_wires,
+                                                  uint32_t fgw, uint32_t ngw, uint32_t* __restrict__ wl_all, uint32_t* __restrict__ xch_all) {
+  OG_FILLER_PRIO();
+  const int tid = threadIdx.x, lane = FORM ? w9_row_limb(tid) : tid;
+  const size_t g = blockIdx.x / 7;
+  const int job = (int)(blockIdx.x % 7);  // 0 inner_a, 1 asset_a, 2 nullifier_hash_a, 3 .. 5 the same of note b, 6 out_asset
+  const uint8_t* in = inputs + g * (size_t)(J_REC + 2 * depth) * 32;
+  uint32_t* wl = wl_all + g * n_wires * 9;
+  uint32_t* xch = xch_all + g * (size_t)(2 * depth + JW9_XCH) * 9;
+  uint32_t* vals = xch + (size_t)(2 * depth) * 9;
+  const uint32_t nj = w9_modulus_limb<FrParams>(lane);
+  const Fr token = fe_to_mont(fe_load<FrParams>(in + J_TOKEN));
+  if (job == 6) {  // out_asset = H(sum, token)
+    const uint32_t base = tw9_gadget_base(fgw + ngw, depth, 4 + depth);
+    const uint32_t hout = tw9_second_half<FORM>(consts9, w9_spread(token, lane), w9_load(vals + (size_t)JW9_OUT * 9, lane), nj, tid, lane, wl, base,
+                                                base + 729, vals + (size_t)JW9_DUMP * 9);
+    if (tid < 9) vals[(size_t)(JW9_OUT + 2) * 9 + lane] = hout;
+    return;
+  }
+  const int b = job >= 3 ? 1 : 0, h = job - 3 * b;  // 0 inner, 1 asset, 2 nullifier_hash of note b
+  uint32_t* note = vals + (size_t)(b * JW9_NOTE) * 9;
+  const uint32_t k1 = w9_load(note + (size_t)(h == 1 ? 1 : 0) * 9, lane);
+  uint32_t r_in = 0;  // nullifier_hash = H(nullifier, 0)
+  if (h == 0) r_in = w9_spread(fe_to_mont(fe_load<FrParams>(in + (size_t)b * J_NOTE_BYTES + J_SECRET)), lane);
+  if (h == 1) r_in = w9_spread(token, lane);
+  const uint32_t base = tw9_gadget_base(fgw + (uint32_t)b * ngw, depth, h == 2 ? 3 : h);
+  const uint32_t hout = tw9_second_half<FORM>(consts9, r_in, k1, nj, tid, lane, wl, base, h == 2 ? 2u + (uint32_t)b : base + 729,
+                                              vals + (size_t)JW9_DUMP * 9);
+  if (tid < 9) note[(size_t)(2 + h) * 9 + lane] = hout;  // (the nullifier hash too: nh_diff_inv reads it)
+}
+
+template <int FORM>
+__global__ void __launch_bounds__(64) k_jw9_chain(const uint32_t* __restrict__ consts9, const uint8_t* __restrict__ inputs, int depth, size_t n_wires,
+                                                 uint32_t fgw, uint32_t ngw, uint32_t* __restrict__ wl_all, uint32_t* __restrict__ xch_all) {
+  OG_FILLER_PRIO();
+  const int tid = threadIdx.x, lane = FORM ? w9_row_limb(tid) : tid;
+  const size_t g = blockIdx.x / 4;
+  const int job = (int)(blockIdx.x % 4);  // 0 note a's chain, 1 note b's, 2 out_leaf, 3 nh_diff_inv
+  const uint8_t* in = inputs + g * (size_t)(J_REC + 2 * depth) * 32;
+  uint32_t* wl = wl_all + g * n_wires * 9;
+  uint32_t* xch = xch_all + g * (size_t)(2 * depth + JW9_XCH) * 9;
+  uint32_t* vals = xch + (size_t)(2 * depth) * 9;
+  uint32_t* dump = vals + (size_t)JW9_DUMP * 9;
+  if (job == 3) {  // lane-local, one lane: both hashes are below 2 N with limbs < 2^29 + 32 (w9_renorm); fe_sub wants normalized limbs
+    if (tid) return;
+    uint32_t ta[9], tb[9];
+#pragma unroll
+    for (int i = 0; i < 9; i++) {
+      ta[i] = vals[(size_t)4 * 9 + i];
+      tb[i] = vals[(size_t)(JW9_NOTE + 4) * 9 + i];
+    }
+    w9_put_fe(wl, 15, fe_inv(fe_sub(fe_from_lazy_limbs<FrParams>(ta), fe_from_lazy_limbs<FrParams>(tb))));  // a - b, never b - a
+    return;
+  }
+  const uint32_t nj = w9_modulus_limb<FrParams>(lane);
+  if (job == 2) {  // out_leaf = H(out_commitment, out_asset): k1 is k_jw9_first's, the asset is k_jw9_second's
+    tw9_second_half<FORM>(consts9, w9_load(vals + (size_t)(JW9_OUT + 2) * 9, lane), w9_load(vals + (size_t)(JW9_OUT + 1) * 9, lane), nj, tid, lane, wl,
+                          tw9_gadget_base(fgw + ngw, depth, 5 + depth), 5u, dump);
+    return;
+  }
+  const uint8_t* note = in + (size_t)job * J_NOTE_BYTES;
+  w9_note_chain<FORM>(consts9, in + (size_t)(J_REC + job * depth) * 32, *reinterpret_cast<const uint64_t*>(note + J_INDEX), depth,
+                      fgw + (uint32_t)job * ngw, job == 0, wl, xch + (size_t)(job * depth) * 9, vals + (size_t)(job * JW9_NOTE + 2) * 9, dump, nj, tid,
+                      lane);
+}
+
+// The wave-wide walk of n join requests (join_witness decides when).  wl is n x n_wires x 36 B from the arena: 1.0 GB for 512
+// depth-32 requests (54 608 wires each), the largest call that takes this walk by default.
+static int join_walk_w9(og_ctx* ctx, int depth, const JoinShape& s, const uint8_t* inputs_d, size_t n, uint8_t* out_d) {
+  uint32_t *wl = nullptr, *xch = nullptr;
+  OG_TRY(arena_get(ctx, "wit.w9.limbs", n * (size_t)s.n_wires * 36, (void**)&wl));
+  OG_TRY(arena_get(ctx, "wit.w9.xch", n * (size_t)(2 * depth + JW9_XCH) * 36, (void**)&xch));
+  const uint32_t* c9 = (const uint32_t*)ctx->mimc_consts9_d;
+  const uint32_t fgw = (uint32_t)s.first_bit_wire + 3 * J_BITS, ngw = (uint32_t)s.note_gadget_wires;
+  OG_W9_LAUNCH(k_jw9_first, w9_rows(), dim3((unsigned)(n * (size_t)(7 + 2 * depth))), dim3(64), 0, ctx->stream, c9, inputs_d, depth, (size_t)s.n_wires,
+               fgw, ngw, wl, xch);
+  OG_W9_LAUNCH(k_jw9_second, w9_rows(), dim3((unsigned)(n * 7)), dim3(64), 0, ctx->stream, c9, inputs_d, depth, (size_t)s.n_wires, fgw, ngw, wl, xch);
+  OG_W9_LAUNCH(k_jw9_chain, w9_rows(), dim3((unsigned)(n * 4)), dim3(64), 0, ctx->stream, c9, inputs_d, depth, (size_t)s.n_wires, fgw, ngw, wl, xch);
+  OG_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_wires_from_limbs, dim3(grid_for(s.n_wires, 256), (unsigned)n), dim3(256), 0, ctx->stream, (const uint32_t*)wl, out_d,
+                     (size_t)s.n_wires, (uint32_t)s.n_wires);
   OG_HIP(hipGetLastError());
   return OG_OK;
 }
