@@ -94,7 +94,8 @@ OG_HD Fq2 f_mul_minus_y(const Fq2& y, bool neg, const Fq2& z, const Fq2& x) {
   return {fe_mul_add_plus(a0, z.c0, s1, z.c1, fe_neg_lazy4(x.c0)), fe_mul_add_plus(a0, z.c1, a1, z.c0, fe_neg_lazy4(x.c1))};
 }
 
-// a a - c d with one reduction per component (for X3 = R^2 - PP (P + 2 X1))
+// a a - c d with one reduction per component: X3 = R^2 - PP (P + 2 X1) as rounds 1-6 computed it.  The group law below takes
+// X3 through f_sqr_rider now; this form stays for the raw-field hooks and the interpreter's op tables, which drive it alone.
 // Bounds (multiples of N): a < 6, c < 2, d < 10.  Fq: 36 + 4 * 10 = 76 N^2.  Fq2: re 36 + 8*6 + 4*10 + 2*10 = 144,
 // im 36 + 36 + 40 + 40 = 152, all < 169 (field.hip.h) -- which is why c is negated against 4N, not 8N.
 OG_HD Fq f_sqr_sub(const Fq& a, const Fq& c, const Fq& d) { return fe_sqr_add(a, fe_neg_lazy4(c), d); }
@@ -103,6 +104,40 @@ OG_HD Fq2 f_sqr_sub(const Fq2& a, const Fq2& c, const Fq2& d) {
   const Fq na1 = fe_neg_lazy(a.c1), nc0 = fe_neg_lazy4(c.c0), nc1 = fe_neg_lazy4(c.c1);
   return {fe_sqr_add3(a.c0, na1, a.c1, nc0, d.c0, c.c1, d.c1), fe_mul_add3(fe_dbl_lazy(a.c0), a.c1, nc0, d.c1, nc1, d.c0)};
 }
+
+// ---- the weak X coordinate (xyzz_madd_signed_w / xyzz_add_w) ------------------------------------------------------------
+// Inside a chain of additions the running X (each Fq2 component of it) has normalized limbs and a value below 5.5N instead of
+// 2N; Y, ZZ and ZZZ stay below 2N.  The forms below are the ones that meet it.
+// a b - x + 6N for a weak x (fe_neg_lazy6), one reduction: in (0.5N, 7.2N).  In Fq2 the lazily negated operand is a's (a.c1 < 2N).
+OG_HD Fq f_mul_minus6(const Fq& a, const Fq& b, const Fq& x) { return fe_mul_plus(a, b, fe_neg_lazy6(x)); }
+OG_HD Fq2 f_mul_minus6(const Fq2& a, const Fq2& b, const Fq2& x) {
+  return {fe_mul_add_plus(a.c0, b.c0, fe_neg_lazy(a.c1), b.c1, fe_neg_lazy6(x.c0)), fe_mul_add_plus(a.c0, b.c1, a.c1, b.c0, fe_neg_lazy6(x.c1))};
+}
+// a b for a < 2N and a weak or wide b (< 7.2N): the lazily negated operand of the Fq2 product is a's, against 4N (not 8N), which
+// keeps PP P and PP X1 near N: (2 + 4) 7.2 = 43 N^2
+OG_HD Fq f_mul_n4(const Fq& a, const Fq& b) { return fe_mul(a, b); }
+OG_HD Fq2 f_mul_n4(const Fq2& a, const Fq2& b) {
+  return {fe_mul_add(a.c0, b.c0, fe_neg_lazy4(a.c1), b.c1), fe_mul_add(a.c0, b.c1, a.c1, b.c0)};
+}
+// X3 = r^2 - (ppp + 2q) + 4N with one reduction per component: the subtrahend rides in the high columns (fe_rider4, limbs
+// < 2^31), so X3 is the reduced square plus at most 4N -- weak.  r < 6N: Fq 36 N^2; Fq2 re 36 + 8 * 6 = 84, im 2 * 36 = 72.
+OG_HD Fq f_sqr_rider(const Fq& r, const Fq& ppp, const Fq& q) { return fe_sqr_plus(r, fe_rider4(ppp, q)); }
+OG_HD Fq2 f_sqr_rider(const Fq2& r, const Fq2& ppp, const Fq2& q) {
+  return {fe_sqr_add_plus(r.c0, fe_neg_lazy(r.c1), r.c1, fe_rider4(ppp.c0, q.c0)), fe_mul_plus(fe_dbl_lazy(r.c0), r.c1, fe_rider4(ppp.c1, q.c1))};
+}
+// D = q - x + 6N for a weak x, as the operand of R D.  Fq: limb-wise, no carry pass (limbs < 2^29 + 2^30; the columns of
+// R D + (8N - Y1) PPP hold 9 (1.5 + 1) 2^59 + 9 2^58 < 2^64).  Fq2: R D - Y1 PPP is four products, two of them with a lazy
+// operand already (15.75 x 2^60 of the 2^64), so there D pays one carry pass per component.
+OG_HD Fq f_q_minus(const Fq& q, const Fq& x) { return fe_add_lazy(q, fe_neg_lazy6(x)); }
+OG_HD Fq2 f_q_minus(const Fq2& q, const Fq2& x) {
+  Fq2 r;
+  normalize29u(r.c0.l, fe_add_lazy(q.c0, fe_neg_lazy6(x.c0)).l);
+  normalize29u(r.c1.l, fe_add_lazy(q.c1, fe_neg_lazy6(x.c1)).l);
+  return r;
+}
+// weak X -> [0, 2N): where a point is stored or handed to code that assumes the invariant of field.hip.h
+OG_HD Fq f_norm_weak(const Fq& a) { return fe_norm_weak(a); }
+OG_HD Fq2 f_norm_weak(const Fq2& a) { return {fe_norm_weak(a.c0), fe_norm_weak(a.c1)}; }
 
 template <class T> struct FieldIO;
 template <> struct FieldIO<Fq> {
@@ -196,30 +231,52 @@ OG_HD XYZZ<T> xyzz_dbl(const XYZZ<T>& p) {
 }
 
 // acc + (neg ? -q : q), q affine (madd-2008-s); complete: handles acc = inf, q = inf, q = +-acc.
-// Inside, differences are "weak" (bounds in the comments, in multiples of N):
-//   * P = U2 - X1, R = S2 - Y1 and D = Q - X3 come straight out of the Montgomery reduction of the product they follow
-//     (f_mul_minus: the subtrahend rides in the high columns) -- no separate subtraction, no carry pass;
-//   * X3 = R^2 - PPP - 2Q is the fused R R - PP (P + 2 X1), Y3 = R D - Y1 PPP one reduction per component;
+// Q = X1 PP is multiplied out ONCE: X3 = R^2 - PPP - 2Q takes PPP + 2Q as an addend of its reduction (f_sqr_rider) and
+// D = Q - X3 is limb-wise (f_q_minus), where rounds 1-6 had R R - PP (P + 2 X1) and a second X1 PP inside D.  The price is
+// that X3 leaves its reduction with up to 4N on top: a.x may be WEAK (normalized limbs, < 5.5N per component) and so is the
+// result's x; y, zz, zzz are < 2N as everywhere.  Callers run chains of these and normalise x once (xyzz_norm), where the
+// point is stored; xyzz_madd_signed below is the form that keeps the 2N contract per call.
+//   * P = U2 - X1, R = S2 - Y1 come straight out of the Montgomery reduction of the product they follow (the subtrahend
+//     rides in the high columns) -- no separate subtraction, no carry pass;
 //   * the sign of a signed-digit entry negates q.y lazily (4N - y limb-wise, a multiplication operand); only the two rare
-//     branches that need y itself negate it properly.
-// 8 product sets + 2 squarings with 9 reductions, 1 carry pass.  Outputs are < 2N again.
+//     branches that need y itself negate it properly;
+//   * q = +-acc is seen on PP (< 2N: exactly 0 or N iff P = 0 mod N), not on P, which now spans seven multiples of N.
+// Bounds (multiples of N, Fq | per Fq2 component; a product routine returns < 1 + sum / 169.28):
+//   X1 < 5.5       P = [x2 ZZ1] + 6N - X1: (0.5, 7.03 | 7.12)      R = [+-y2 ZZZ1] + 4N - Y1: (2, 5.05 | 5.15)
+//   PP: 49.4 | 50.7 + 8 * 7.12 = 107.7 N^2 -> < 1.30 | 1.64        PPP = PP P: 9.2 | (1.64 + 4) 7.12 = 40.2 -> < 1.06 | 1.24
+//   Q = PP X1: 7.2 | (1.64 + 4) 5.5 = 31.1 -> < 1.05 | 1.19        PPP + 2Q < 3.16 | 3.62 < 4N - 2^234 (fe_rider4)
+//   X3 < [R^2] + 4N: 36 | 84 -> < 5.22 | 5.50: the invariant closes   D = Q + 6N - X3 < 7.05 | 7.19
+//   Y3 = R D - Y1 PPP: 6 * 7.05 + 8 * 1.06 = 51 | 6 * 7.19 + 8 * 7.19 + 8 * 1.24 + 2 * 1.24 = 113 -> < 2
+// 8 product sets + 2 squarings with 9 reductions and no carry pass (Fq2: two, in D).
 template <class T>
-OG_HD XYZZ<T> xyzz_madd_signed(const XYZZ<T>& a, const Affine<T>& q, bool neg) {
+OG_HD XYZZ<T> xyzz_madd_signed_w(const XYZZ<T>& a, const Affine<T>& q, bool neg) {
   if (q.is_inf()) return a;
   if (a.is_inf()) return XYZZ<T>::from_affine(neg ? affine_neg(q) : q);
-  T P = f_mul_minus(q.x, a.zz, a.x);       // U2 - X1 + 4N: (2, 6)
+  T P = f_mul_minus6(q.x, a.zz, a.x);         // U2 - X1 + 6N
   T R = f_mul_minus_y(q.y, neg, a.zzz, a.y);  // S2 - Y1 + 4N: (2, 6)   (operands <= 8N x 2N: far below 169 N^2)
-  if (f_weak_diff_is_zero(P)) {
+  T PP = f_sqr(P);
+  if (PP.is_zero()) {
     if (f_weak_diff_is_zero(R)) return xyzz_dbl_affine(neg ? affine_neg(q) : q);
     return XYZZ<T>::inf();
   }
-  T PP = f_sqr(P);                         // Fq2 worst case 36 + 8 * 6 = 84 N^2 -> < 2
-  T PPP = f_mul(PP, P);                    // the lazily negated operand inside an Fq2 product is PP's, not P's
-  T W = f_add2_weak(P, a.x);               // P + 2 X1: < 10
-  T X3 = f_sqr_sub(R, PP, W);              // R^2 - PP W: <= 152 N^2 -> < 2
-  T D = f_mul_minus(a.x, PP, X3);          // Q - X3 + 4N: < 6
-  T Y3 = f_mul_sub(R, D, a.y, PPP);        // R D - Y1 PPP: <= 36 + 48 + 16 + 4 = 104 N^2 -> < 2
+  T PPP = f_mul_n4(PP, P);
+  T Q = f_mul_n4(PP, a.x);
+  T X3 = f_sqr_rider(R, PPP, Q);              // R^2 - PPP - 2Q + 4N: weak
+  T D = f_q_minus(Q, X3);                     // Q - X3 + 6N
+  T Y3 = f_mul_sub(R, D, a.y, PPP);           // R D - Y1 PPP
   return {X3, Y3, f_mul(a.zz, PP), f_mul(a.zzz, PPP)};
+}
+
+// the point with its weak x brought below 2N: before a store, and before code that assumes the invariant of field.hip.h
+template <class T>
+OG_HD XYZZ<T> xyzz_norm(const XYZZ<T>& p) {
+  return {f_norm_weak(p.x), p.y, p.zz, p.zzz};
+}
+
+// the same with every coordinate of the result < 2N (a.x may still be weak)
+template <class T>
+OG_HD XYZZ<T> xyzz_madd_signed(const XYZZ<T>& a, const Affine<T>& q, bool neg) {
+  return xyzz_norm(xyzz_madd_signed_w(a, q, neg));
 }
 
 template <class T>
@@ -227,9 +284,11 @@ OG_HD XYZZ<T> xyzz_madd(const XYZZ<T>& a, const Affine<T>& q) {
   return xyzz_madd_signed(a, q, false);
 }
 
-// a + b (add-2008-s); complete.  Same structure as xyzz_madd_signed: the three differences come out of reductions.
+// a + b (add-2008-s); complete.  Same structure as xyzz_madd_signed_w with U1 = X1 ZZ2 in the place of X1: a.x and b.x may
+// be weak (they only meet products), the result's x is weak.  U1, S1 < 2, so P and R are the (2, 6) differences against 4N
+// and every bound above holds with room (Fq2: PP 84 N^2 -> < 1.5, PPP (1.5 + 4) 6 = 33, Q (1.5 + 4) 2 = 11, X3 < 5.5).
 template <class T>
-OG_HD XYZZ<T> xyzz_add(const XYZZ<T>& a, const XYZZ<T>& b) {
+OG_HD XYZZ<T> xyzz_add_w(const XYZZ<T>& a, const XYZZ<T>& b) {
   if (b.is_inf()) return a;
   if (a.is_inf()) return b;
   T U1 = f_mul(a.x, b.zz);
@@ -241,12 +300,18 @@ OG_HD XYZZ<T> xyzz_add(const XYZZ<T>& a, const XYZZ<T>& b) {
     return XYZZ<T>::inf();
   }
   T PP = f_sqr(P);
-  T PPP = f_mul(PP, P);
-  T W = f_add2_weak(P, U1);
-  T X3 = f_sqr_sub(R, PP, W);
-  T D = f_mul_minus(U1, PP, X3);           // Q - X3 + 4N: < 6
+  T PPP = f_mul_n4(PP, P);
+  T Q = f_mul_n4(PP, U1);
+  T X3 = f_sqr_rider(R, PPP, Q);
+  T D = f_q_minus(Q, X3);                  // Q - X3 + 6N
   T Y3 = f_mul_sub(R, D, S1, PPP);
   return {X3, Y3, f_mul(f_mul(a.zz, b.zz), PP), f_mul(f_mul(a.zzz, b.zzz), PPP)};
+}
+
+// the same with every coordinate of the result < 2N
+template <class T>
+OG_HD XYZZ<T> xyzz_add(const XYZZ<T>& a, const XYZZ<T>& b) {
+  return xyzz_norm(xyzz_add_w(a, b));
 }
 
 template <class T>

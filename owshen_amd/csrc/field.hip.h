@@ -48,6 +48,8 @@ struct FqParams {
   static constexpr uint32_t N3[9] = {0x0976f7d5u, 0x030d2224u, 0x1557e9edu, 0x087f6872u, 0x00918c68u, 0x0891c242u, 0x01f4a3c3u, 0x0b14729cu, 0x00912cebu};
   static constexpr uint32_t N4[9] = {0x01f3f51cu, 0x041182dbu, 0x11ca8d3cu, 0x0b548b43u, 0x161765e0u, 0x0b6d0302u, 0x029b8504u, 0x197098d0u, 0x00c19139u};
   static constexpr uint32_t N5[9] = {0x1a70f263u, 0x0515e391u, 0x0e3d308bu, 0x0e29ae14u, 0x0b9d3f58u, 0x0e4843c3u, 0x03426645u, 0x07ccbf04u, 0x00f1f588u};
+  // 6 N inflated like NEG4 / NEG8 (fe_neg_lazy6)
+  static constexpr uint32_t NEG6[9] = {0x32edefaau, 0x261a4447u, 0x2aafd3d9u, 0x30fed0e4u, 0x212318cfu, 0x31238483u, 0x23e94785u, 0x3628e537u, 0x012259d5u};
 };
 
 struct FrParams {
@@ -68,6 +70,8 @@ struct FrParams {
   static constexpr uint32_t N3[9] = {0x10000003u, 0x1d2f05deu, 0x0b146cf2u, 0x1771b2dau, 0x00917789u, 0x0891c242u, 0x01f4a3c3u, 0x0b14729cu, 0x00912cebu};
   static constexpr uint32_t N4[9] = {0x00000004u, 0x1c3eb27eu, 0x19709143u, 0x1f4243cdu, 0x16174a0cu, 0x0b6d0302u, 0x029b8504u, 0x197098d0u, 0x00c19139u};
   static constexpr uint32_t N5[9] = {0x10000005u, 0x1b4e5f1du, 0x07ccb594u, 0x0712d4c1u, 0x0b9d1c90u, 0x0e4843c3u, 0x03426645u, 0x07ccbf04u, 0x00f1f588u};
+  // 6 N inflated like NEG4 / NEG8 (fe_neg_lazy6)
+  static constexpr uint32_t NEG6[9] = {0x20000006u, 0x3a5e0bbcu, 0x3628d9e4u, 0x2ee365b3u, 0x2122ef12u, 0x31238483u, 0x23e94785u, 0x3628e537u, 0x012259d5u};
 };
 
 template <class M>
@@ -390,6 +394,47 @@ OG_HD Fe<M> fe_neg_lazy4(const Fe<M>& a) {
   return r;
 }
 
+// 6N - a for a normalized a < 6N - 2^232, i.e. a.l[8] <= NEG6[8]: the lazy negation of the accumulator's weak X (< 5.5N,
+// ec.hip.h), where 8N would cost the sums of products that follow too much of their 169 N^2
+template <class M>
+OG_HD Fe<M> fe_neg_lazy6(const Fe<M>& a) {
+  Fe<M> r;
+#pragma unroll
+  for (int i = 0; i < 9; i++) r.l[i] = M::NEG6[i] - a.l[i];
+  return r;
+}
+// 4N - a - 2b limb-wise for normalized a, b with a + 2b < 4N - 2^234 (top limbs: a.l[8] + 2 b.l[8] <= NEG4[8] - 2): 4N with
+// every limb below the top inflated by 3 x 2^29 (NEG4's 2^29 and 2^30 more, each borrowed from the next limb), so that no
+// limb goes negative.  Limbs < 2^31, value in (0, 4N].  NOT an operand of a product: only the addend of the `plus` routines
+// below, which take it into the 64-bit columns (the group law's X3 = R^2 + (4N - (PPP + 2Q)))
+template <class M>
+OG_HD Fe<M> fe_rider4(const Fe<M>& a, const Fe<M>& b) {
+  Fe<M> r;
+#pragma unroll
+  for (int i = 0; i < 9; i++) r.l[i] = M::NEG4[i] + (i < 8 ? (1u << 30) : 0u) - (i > 0 ? 2u : 0u) - a.l[i] - (b.l[i] << 1);
+  return r;
+}
+// a < 6N with normalized limbs ("weak") -> the same residue in [0, 2N): subtract 4N, then 2N, where they fit.  This is the
+// ONE place a weak value becomes storable again (the group law's running X, normalised where a bucket is stored)
+template <class M>
+OG_HD Fe<M> fe_norm_weak(const Fe<M>& a) {
+  Fe<M> x = a;
+#pragma unroll
+  for (int pass = 0; pass < 2; pass++) {
+    uint32_t u[9];
+    int32_t c = 0;
+#pragma unroll
+    for (int i = 0; i < 9; i++) {
+      const int32_t v = (int32_t)x.l[i] - (int32_t)(pass ? M::N2[i] : M::N4[i]) + c;
+      u[i] = (uint32_t)v & MASK29;
+      c = v >> 29;
+    }
+#pragma unroll
+    for (int i = 0; i < 9; i++) x.l[i] = c ? x.l[i] : u[i];  // c = -1: below the subtrahend, keep
+  }
+  return x;
+}
+
 // ---- weak (carry-only) forms for the inside of the group-law formulas -------------------------
 // They skip the conditional subtraction: results have normalized limbs but are only bounded by a small multiple
 // of N (every product routine gives a result < 2N as long as its sum of products is < 169 N^2 = N 2^261).  Results must not be stored
@@ -517,6 +562,53 @@ OG_HD Fe<M> fe_mul_add_plus(const Fe<M>& a, const Fe<M>& b, const Fe<M>& d, cons
     x.template close<OG_COL(kc)>();
   });
   x.r.l[8] = (uint32_t)x.t + c.l[8];
+  return x.r;
+#endif
+}
+
+// a^2 2^-261 + p with ONE reduction and the 45-product squaring: fe_sqr(a) + p limb-for-limb after normalisation.  a
+// normalized (a < 13N: a^2 < 169 N^2); p any addend with limbs < 2^31 (fe_rider4): value < 2N + bound(p), normalized limbs.
+// Column bound: 9 x 2^58 (squaring) + 9 x 2^58 (reduction) + 2^31 + carry, far below 2^64.
+template <class M>
+OG_HD Fe<M> fe_sqr_plus(const Fe<M>& a, const Fe<M>& p) {
+#if OG_MONT_DEVICE
+  Fe<M> r;
+  uint32_t ad[8];
+  fe_doubled(ad, a);
+  asm(OG_MONT_ASM_SQR_PLUS : OG_MONT_OUT(r) : OG_MONT_MOD(M), OG_FE_V(a, a), OG_FE_V(p, p), OG_FE_DBL(a, ad) : OG_MONT_CLOBBER);
+  return r;
+#else
+  MontCols<M> x;
+  x.t = 0;
+  for_columns<0>([&](auto kc) {
+    if constexpr (OG_COL(kc) >= 9) x.t += p.l[OG_COL(kc) - 9];
+    x.template sqr<OG_COL(kc)>(a);
+    x.template close<OG_COL(kc)>();
+  });
+  x.r.l[8] = (uint32_t)x.t + p.l[8];
+  return x.r;
+#endif
+}
+// (a^2 + c d) 2^-261 + p, one reduction: the real part a0^2 + (8N - a1) a1 + p of the Fq2 form of the same (c may be lazy:
+// 9 x 2^58 + 9 x 2^59 + 9 x 2^58 + 2^31 + carry < 2^64)
+template <class M>
+OG_HD Fe<M> fe_sqr_add_plus(const Fe<M>& a, const Fe<M>& c, const Fe<M>& d, const Fe<M>& p) {
+#if OG_MONT_DEVICE
+  Fe<M> r;
+  uint32_t ad[8];
+  fe_doubled(ad, a);
+  asm(OG_MONT_ASM_SQR_ADD_PLUS : OG_MONT_OUT(r) : OG_MONT_MOD(M), OG_FE_V(a, a), OG_FE_V(c, c), OG_FE_V(d, d), OG_FE_V(p, p), OG_FE_DBL(a, ad) : OG_MONT_CLOBBER);
+  return r;
+#else
+  MontCols<M> x;
+  x.t = 0;
+  for_columns<0>([&](auto kc) {
+    if constexpr (OG_COL(kc) >= 9) x.t += p.l[OG_COL(kc) - 9];
+    x.template sqr<OG_COL(kc)>(a);
+    x.template mul<OG_COL(kc)>(c, d);
+    x.template close<OG_COL(kc)>();
+  });
+  x.r.l[8] = (uint32_t)x.t + p.l[8];
   return x.r;
 #endif
 }

@@ -133,7 +133,8 @@ int field_mulchain_lat(og_ctx* ctx, int field, int form, uint8_t* x, const uint8
 // lazy and weak operand bounds the routines document (limbs up to 2^30 / 2^31, values up to 42 N) reach the asm statements of
 // mont_gfx950.inc on the hardware, and returns the routine's limbs untouched (tests/field_raw_cases.py holds the cases and the
 // big-integer reference).  One kernel instantiation per (field, op): every asm statement gets a register allocation of its
-// own.  Op numbers 0..8, 12, 13 are those of emu_fe_op and 64 + k those of emu_fq2_op (tests/hipemu/stubs.cpp).
+// own.  Op numbers 0..8, 12, 13 are those of emu_fe_op and 64..70 those of emu_fq2_op (tests/hipemu/stubs.cpp); 37..41 and 71..74 are
+// the forms of the single-Q addition (tests/field_rider_cases.py).
 #include "ec.hip.h"
 #include <mutex>
 
@@ -155,10 +156,15 @@ constexpr int raw_arity(int op) {
     case 26: return 7;                                                      // sqr_add3
     case 27: case 29: case 30: case 31: case 33: case 34: case 35: case 36: return 1;  // dbl neg_lazy neg_lazy4 dbl_lazy weak_diff_is_zero canon lt_modulus to_mont
     case 32: return 3;                                                      // add3_weak
+    case 37: case 40: return 2;                                             // sqr_plus(a, p)  rider4(a, b)
+    case 38: return 4;                                                      // sqr_add_plus(a, c, d, p)
+    case 39: case 41: return 1;                                             // neg_lazy6  norm_weak
     case 64: return 4;                                                      // Fq2 f_mul(a, b)
     case 65: return 2;                                                      // Fq2 f_sqr(a)
     case 66: return 8;                                                      // Fq2 f_mul_sub(a, b, c, d)
     case 67: case 68: case 69: case 70: return 6;                           // Fq2 f_sqr_sub(a, c, d)  f_mul_minus(a, b, x)  f_mul_minus_y(y, neg = 0 | 1, z, x)
+    case 71: case 73: return 6;                                             // Fq2 f_mul_minus6(a, b, x)  f_sqr_rider(r, ppp, q)
+    case 72: case 74: return 4;                                             // Fq2 f_mul_n4(a, b)  f_q_minus(q, x)
     default: return 0;
   }
 }
@@ -210,6 +216,11 @@ OG_HD void fe_raw_apply(const Fe<M>* x, Fe<M>* o) {
   else if constexpr (OP == 34) o[0] = fe_canon(x[0]);
   else if constexpr (OP == 35) o[0] = raw_flag<M>(fe_lt_modulus(x[0]));
   else if constexpr (OP == 36) o[0] = fe_to_mont(x[0]);
+  else if constexpr (OP == 37) o[0] = fe_sqr_plus(x[0], x[1]);
+  else if constexpr (OP == 38) o[0] = fe_sqr_add_plus(x[0], x[1], x[2], x[3]);
+  else if constexpr (OP == 39) o[0] = fe_neg_lazy6(x[0]);
+  else if constexpr (OP == 40) o[0] = fe_rider4(x[0], x[1]);
+  else if constexpr (OP == 41) o[0] = fe_norm_weak(x[0]);
   else if constexpr (OP >= 64 && std::is_same<M, FqParams>::value) {
     const Fq2 a = {x[0], x[1]};
     Fq2 r;
@@ -218,7 +229,11 @@ OG_HD void fe_raw_apply(const Fe<M>* x, Fe<M>* o) {
     else if constexpr (OP == 66) r = f_mul_sub(a, Fq2{x[2], x[3]}, Fq2{x[4], x[5]}, Fq2{x[6], x[7]});
     else if constexpr (OP == 67) r = f_sqr_sub(a, Fq2{x[2], x[3]}, Fq2{x[4], x[5]});
     else if constexpr (OP == 68) r = f_mul_minus(a, Fq2{x[2], x[3]}, Fq2{x[4], x[5]});
-    else r = f_mul_minus_y(a, OP == 70, Fq2{x[2], x[3]}, Fq2{x[4], x[5]});
+    else if constexpr (OP == 69 || OP == 70) r = f_mul_minus_y(a, OP == 70, Fq2{x[2], x[3]}, Fq2{x[4], x[5]});
+    else if constexpr (OP == 71) r = f_mul_minus6(a, Fq2{x[2], x[3]}, Fq2{x[4], x[5]});
+    else if constexpr (OP == 72) r = f_mul_n4(a, Fq2{x[2], x[3]});
+    else if constexpr (OP == 73) r = f_sqr_rider(a, Fq2{x[2], x[3]}, Fq2{x[4], x[5]});
+    else r = f_q_minus(a, Fq2{x[2], x[3]});
     o[0] = r.c0;
     o[1] = r.c1;
   }
@@ -275,6 +290,77 @@ extern "C" int og_hook_fe_raw_d(og_ctx* ctx, int field, int op, const uint32_t* 
     std::lock_guard<std::mutex> lk(ctx->mu);
     OG_HIP(hipSetDevice(ctx->device));
     f(ctx->stream, operands_d, n, out_d);
+    OG_HIP(hipGetLastError());
+    OG_HIP(hipStreamSynchronize(ctx->stream));
+    return OG_OK;
+  });
+}
+// ---- the group law driven alone, on raw limbs ---------------------------------------------------------------------------------
+// og_hook_ec_chain_d walks one chain of additions per lane with NO normalisation in between and hands the accumulator back as
+// limbs, weak x included, so that a test can start it from a non-canonical x (x + j N, up to the 5.5N the weak invariant of
+// ec.hip.h allows) and see what the chain leaves.  acc: n x NC Fe (x, y, zz, zzz; NC = 4 for G1, 8 for G2) as 9 limbs each;
+// steps: n x n_steps records of 1 + 8 x 9 words: kind (0 / 1: xyzz_madd_signed_w with q = slots 0.. and neg = kind; 2: xyzz_add_w
+// with the XYZZ in slots 0..; 3: xyzz_norm), then the operand's Fe slots.  out: like acc.
+namespace og {
+
+constexpr int CHAIN_REC = 1 + 8 * 9;
+
+template <class T> struct ChainIO;
+template <> struct ChainIO<Fq> {
+  static constexpr int NF = 1;
+  OG_HD static Fq get(const uint32_t* p) {
+    Fq r;
+    for (int k = 0; k < 9; k++) r.l[k] = p[k];
+    return r;
+  }
+  OG_HD static void put(uint32_t* p, const Fq& v) {
+    for (int k = 0; k < 9; k++) p[k] = v.l[k];
+  }
+};
+template <> struct ChainIO<Fq2> {
+  static constexpr int NF = 2;
+  OG_HD static Fq2 get(const uint32_t* p) { return {ChainIO<Fq>::get(p), ChainIO<Fq>::get(p + 9)}; }
+  OG_HD static void put(uint32_t* p, const Fq2& v) {
+    ChainIO<Fq>::put(p, v.c0);
+    ChainIO<Fq>::put(p + 9, v.c1);
+  }
+};
+
+template <class T>
+__global__ void __launch_bounds__(64) k_ec_chain(const uint32_t* __restrict__ acc_in, const uint32_t* __restrict__ steps, size_t n, uint32_t n_steps,
+                                                uint32_t* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
+  if (i >= n) return;
+  typedef ChainIO<T> IO;
+  constexpr int W = IO::NF * 9;  // words per coordinate
+  const uint32_t* a = acc_in + i * 4 * W;
+  XYZZ<T> acc = {IO::get(a), IO::get(a + W), IO::get(a + 2 * W), IO::get(a + 3 * W)};
+#pragma unroll 1
+  for (uint32_t s = 0; s < n_steps; s++) {  // one inlined site per primitive (ec.hip.h)
+    const uint32_t* rec = steps + (i * n_steps + s) * CHAIN_REC;
+    const uint32_t kind = rec[0];
+    if (kind <= 1) acc = xyzz_madd_signed_w(acc, Affine<T>{IO::get(rec + 1), IO::get(rec + 1 + W)}, kind == 1);
+    else if (kind == 2) acc = xyzz_add_w(acc, XYZZ<T>{IO::get(rec + 1), IO::get(rec + 1 + W), IO::get(rec + 1 + 2 * W), IO::get(rec + 1 + 3 * W)});
+    else acc = xyzz_norm(acc);
+  }
+  uint32_t* o = out + i * 4 * W;
+  IO::put(o, acc.x);
+  IO::put(o + W, acc.y);
+  IO::put(o + 2 * W, acc.zz);
+  IO::put(o + 3 * W, acc.zzz);
+}
+
+}  // namespace og
+
+extern "C" int og_hook_ec_chain_d(og_ctx* ctx, int g2, const uint32_t* acc_d, const uint32_t* steps_d, size_t n, uint32_t n_steps, uint32_t* out_d) {
+  using namespace og;
+  return guarded([&]() -> int {
+    OG_REQUIRE(ctx && acc_d && steps_d && out_d && n >= 1 && n <= ((size_t)1 << 16) && n_steps <= (1u << 16) && (g2 == 0 || g2 == 1),
+               "og_hook_ec_chain_d: bad argument");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    OG_HIP(hipSetDevice(ctx->device));
+    if (g2) hipLaunchKernelGGL(k_ec_chain<Fq2>, dim3(grid_for(n, 64)), dim3(64), 0, ctx->stream, acc_d, steps_d, n, n_steps, out_d);
+    else hipLaunchKernelGGL(k_ec_chain<Fq>, dim3(grid_for(n, 64)), dim3(64), 0, ctx->stream, acc_d, steps_d, n, n_steps, out_d);
     OG_HIP(hipGetLastError());
     OG_HIP(hipStreamSynchronize(ctx->stream));
     return OG_OK;

@@ -117,9 +117,9 @@ __global__ void __launch_bounds__(64, MINW) k_accumulate_p(const uint8_t* __rest
 #pragma unroll 1
     for (uint32_t p = lo; p < hi; p++) {  // (a software prefetch of the next base was measured in round 3: 144 registers, same time)
       const uint32_t e = ent[p];
-      acc = xyzz_madd_signed(acc, gather_base<T>(tab, e), e & 1);
+      acc = xyzz_madd_signed_w(acc, gather_base<T>(tab, e), e & 1);  // x weak along the chain (ec.hip.h) ...
     }
-    if (live) acc.store(buckets + ((size_t)g * nkeys + key) * XYZZ<T>::BYTES);
+    if (live) xyzz_norm(acc).store(buckets + ((size_t)g * nkeys + key) * XYZZ<T>::BYTES);  // ... and < 2N in the bucket
   }
 }
 
@@ -172,9 +172,9 @@ __global__ void __launch_bounds__(64, MINW) k_accumulate_pieces(const uint8_t* _
 #pragma unroll 1
     for (uint32_t p = s0; p < s1; p++) {
       const uint32_t e = entries[p];
-      acc = xyzz_madd_signed(acc, gather_base<T>(tab, e), e & 1);
+      acc = xyzz_madd_signed_w(acc, gather_base<T>(tab, e), e & 1);
     }
-    if (live) acc.store(pieces + ((size_t)q * nkeys + key) * XYZZ<T>::BYTES);
+    if (live) xyzz_norm(acc).store(pieces + ((size_t)q * nkeys + key) * XYZZ<T>::BYTES);
   }
 }
 
@@ -282,8 +282,9 @@ __global__ void __launch_bounds__(HEAVY_BLOCK, MINW) k_accumulate_heavy(const ui
     XYZZ<T> acc = XYZZ<T>::inf();
     for (uint32_t p = s0 + threadIdx.x; p < s1; p += blockDim.x) {
       const uint32_t e = ent[p];
-      acc = xyzz_madd_signed(acc, gather_base<T>(tab, e), e & 1);
+      acc = xyzz_madd_signed_w(acc, gather_base<T>(tab, e), e & 1);
     }
+    acc = xyzz_norm(acc);  // the tree below stores it (32 bytes hold < 2^256 only) and adds with xyzz_add, which keeps x < 2N
 #pragma unroll 1
     for (int d = blockDim.x / 2; d >= 1; d >>= 1) {
       __syncthreads();
@@ -428,24 +429,24 @@ __global__ void __launch_bounds__(64, MINW) k_accumulate_g2_lds(const uint8_t* _
       inf = false;
       continue;
     }
-    const T P = f_mul_minus(q.x, coord(2), coord(0));          // U2 - X1 + 4N
+    // xyzz_madd_signed_w restated coordinate by coordinate (bounds there): X in LDS is weak, < 5.5N per component
+    const T P = f_mul_minus6(q.x, coord(2), coord(0));         // U2 - X1 + 6N
     const T R = f_mul_minus_y(q.y, neg, coord(3), coord(1));   // S2 - Y1 + 4N
-    if (f_weak_diff_is_zero(P)) {                              // q = +-acc: rare
+    const T PP = f_sqr(P);
+    if (PP.is_zero()) {                                        // q = +-acc: rare
       if (f_weak_diff_is_zero(R)) acc.put(0, xyzz_dbl_affine(neg ? affine_neg(q) : q)); else inf = true;
       continue;
     }
-    const T PP = f_sqr(P);
-    const T PPP = f_mul(PP, P);
+    const T PPP = f_mul_n4(PP, P);
     set(2, f_mul(coord(2), PP));                               // ZZ3
     set(3, f_mul(coord(3), PPP));                              // ZZZ3
-    const T X1 = coord(0);
-    const T X3 = f_sqr_sub(R, PP, f_add2_weak(P, X1));         // R^2 - PP (P + 2 X1)
-    const T D = f_mul_minus(X1, PP, X3);                       // Q - X3 + 4N
+    const T Q = f_mul_n4(PP, coord(0));                        // X1 PP, once
+    const T X3 = f_sqr_rider(R, PPP, Q);                       // R^2 - PPP - 2Q + 4N
     set(0, X3);
-    set(1, f_mul_sub(R, D, coord(1), PPP));                    // R D - Y1 PPP
+    set(1, f_mul_sub(R, f_q_minus(Q, X3), coord(1), PPP));     // R (Q - X3) - Y1 PPP
   }
   XYZZ<T> out = XYZZ<T>::inf();
-  if (!inf) out = acc.get(0);
+  if (!inf) out = xyzz_norm(acc.get(0));
   if (live) out.store(buckets + ((size_t)g * nkeys + key) * XYZZ<T>::BYTES);
   if constexpr (!PERSIST) return;
   }

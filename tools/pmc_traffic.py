@@ -11,8 +11,9 @@ Only the FULL-SIZE launches (the largest grid of each kernel = one whole sub-bat
 are averages over the query launches (A, B1, L, H for G1; B2 for G2), the same average bench.py's HIP-event timing takes.
 --points gives the per-proof point counts of the queries in launch order, from the bench line's config.n_dense.
 Instruction-issue figures use the cycle-calibrated og_ubench_cycles costs (profiles/<tag>_probe.json) and the multiply-add
-counts of one mixed addition from the generated field routines (owshen_amd/csrc/mont_gfx950.inc): G1 1572 v_mad_u64_u32
-(819 product + 729 reduction terms + 24 addend limbs) + 81 v_mul_lo_u32, G2 4836 + 162.
+counts of one mixed addition from the generated field routines (owshen_amd/csrc/mont_gfx950.inc): G1 1491 v_mad_u64_u32
+(738 product + 729 reduction terms + 24 addend limbs) + 81 v_mul_lo_u32, G2 4512 + 162 (the single-Q addition).
+MADS holds the counts of the formulation up to round 6 (1572 + 81, 4836 + 162), which the recorded r0x passes were made with.
 """
 import csv
 import glob
@@ -20,7 +21,8 @@ import json
 import os
 import sys
 
-MADS = {"accumulate_g1": (1572, 81), "accumulate_g2": (4836, 162)}
+MADS = {"accumulate_g1": (1572, 81), "accumulate_g2": (4836, 162)}           # rounds 1-6: X1 PP multiplied out twice
+MADS_SINGLE_Q = {"accumulate_g1": (1491, 81), "accumulate_g2": (4512, 162)}  # what the library runs now
 KERNELS = {"accumulate_g1": ("k_accumulate<og::Fe<og::FqParams>", "k_accumulate_p<og::Fe<og::FqParams>"),
            "accumulate_g2": ("k_accumulate<og::Fq2", "k_accumulate_p<og::Fq2", "k_accumulate_g2_lds")}
 N_SIMD, N_XCD, NWIN = 1024, 8, 16
@@ -98,7 +100,7 @@ def main():
             insts = sum(c["SQ_INSTS_VALU"]) / n                 # wave-instructions per launch
             cyc = sum(c["GRBM_GUI_ACTIVE"]) / n / N_XCD          # kernel duration in shader cycles
             madds = point_windows / 64                           # wave-level mixed additions per launch
-            mad, mul = MADS[key]
+            mad, mul = MADS_SINGLE_Q[key]
             entry.update(valu_insts_per_madd=round(insts / madds, 1), kernel_cycles=int(cyc),
                          effective_clock_GHz=round(cyc / (dur_ms * 1e6), 3),
                          valu_util=round(insts * 4 / (N_SIMD * cyc), 4),
