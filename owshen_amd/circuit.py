@@ -124,6 +124,32 @@ class _Builder:
         self.enforce(_lc_merge([(k1, 2)], r_lc, y91), [(0, 1)], [(out_wire, 1)])
         return out_wire
 
+    def range_check(self, value, bits, n_bits=128):
+        """value < 2^n_bits: boolean rows over the wires bits .. bits + n_bits - 1 (LSB first), then the recomposition row"""
+        for i in range(n_bits):
+            self.enforce([(bits + i, 1)], [(bits + i, 1), (0, R - 1)], [])
+        self.enforce([(bits + i, 1 << i) for i in range(n_bits)], [(0, 1)], [(value, 1)])
+
+    def merkle_walk(self, cur, w_sib, w_bit, depth, root):
+        """the path from `cur` up to the wire `root`, the output wire of the last level's hash: per level a boolean index bit, the
+        `left` selector wire (allocated here) and one hash"""
+        for l in range(depth):
+            b, s = w_bit + l, w_sib + l
+            self.enforce([(b, 1)], [(b, 1), (0, R - 1)], [])
+            left = self.alloc()
+            self.enforce([(b, 1)], [(s, 1), (cur, R - 1)], [(left, 1), (cur, R - 1)])
+            right = [(s, 1), (cur, 1), (left, R - 1)]
+            cur = self.hash2([(left, 1)], right, out_wire=root if l == depth - 1 else None)
+
+    def spend_note(self, nullifier, secret, amount, token, nh, w_sib, w_bit, depth, root):
+        """a note is spent: leaf = H(H(nullifier, secret), H(amount, token)), nullifier_hash = H(nullifier, 0) into the wire `nh`,
+        then the leaf's path up to `root`"""
+        inner = self.hash2([(nullifier, 1)], [(secret, 1)])
+        asset = self.hash2([(amount, 1)], [(token, 1)])
+        leaf = self.hash2([(inner, 1)], [(asset, 1)])
+        self.hash2([(nullifier, 1)], [], out_wire=nh)
+        self.merkle_walk(leaf, w_sib, w_bit, depth, root)
+
 
 def _csr(trip, pad_counts, pad_cols, pad_vals, n_wires):
     counts = np.concatenate([np.asarray(trip.counts, dtype=np.int64), pad_counts])
@@ -198,17 +224,7 @@ def withdraw_r1cs(mimc7_constants, depth=32, n_pad3=0, n_pad2=0, dense=False):
     w_csq = bld.alloc()
     bld.enforce([(W_RECIPIENT, 1)], [(W_RECIPIENT, 1)], [(w_rsq, 1)])
     bld.enforce([(W_CHAIN, 1)], [(W_CHAIN, 1)], [(w_csq, 1)])
-    inner = bld.hash2([(W_NULLIFIER, 1)], [(W_SECRET, 1)])
-    asset = bld.hash2([(W_AMOUNT, 1)], [(W_TOKEN, 1)])
-    cur = bld.hash2([(inner, 1)], [(asset, 1)])
-    bld.hash2([(W_NULLIFIER, 1)], [], out_wire=W_NH)
-    for l in range(depth):
-        b, s = w_bit + l, w_sib + l
-        bld.enforce([(b, 1)], [(b, 1), (0, R - 1)], [])
-        left = bld.alloc()
-        bld.enforce([(b, 1)], [(s, 1), (cur, R - 1)], [(left, 1), (cur, R - 1)])
-        right = [(s, 1), (cur, 1), (left, R - 1)]
-        cur = bld.hash2([(left, 1)], right, out_wire=W_ROOT if l == depth - 1 else None)
+    bld.spend_note(W_NULLIFIER, W_SECRET, W_AMOUNT, W_TOKEN, W_NH, w_sib, w_bit, depth, W_ROOT)
     pad_base = bld.next
     assert pad_base + 3 * n_pad3 + 2 * n_pad2 == n_wires
     pa, pb, pc = _pad_arrays(pad_base, n_pad3, n_pad2)
@@ -255,11 +271,59 @@ def _r1cs_from_handle(ctx, h):
     return R1CS(n_wires, n_pub, *mats)
 
 
+def _finish(bld, n_wires, n_pub, n_constraints):
+    """the R1CS of a statement without padding gates, from its finished builder"""
+    assert bld.next == n_wires
+    none = np.zeros(0, dtype=np.int64)
+    pad = (none, none, none)
+    r1cs = R1CS(n_wires, n_pub, _csr(bld.a, *pad, n_wires), _csr(bld.b, *pad, n_wires), _csr(bld.c, *pad, n_wires))
+    assert r1cs.n_constraints == n_constraints
+    return r1cs
+
+
+def _pack(vals):
+    """field elements -> uint8 [len, 32], canonical little-endian: one input record"""
+    return np.frombuffer(b"".join(int(v).to_bytes(32, "little") for v in vals), dtype=np.uint8).reshape(-1, 32).copy()
+
+
+def _dev(ctx, *values):
+    """field elements -> device uint8 [len, 32]"""
+    return ctx.to_device(_pack(values))
+
+
+def _records_witness(ctx, name, n_rec_fields, depth, inputs_d, shape, n_pub):
+    """og_<name>_witness_d of a record statement: inputs_d device uint8 [n, n_rec_fields, 32] -> device uint8 [n, n_wires, 32]; `shape`,
+    `n_pub`: what this module says of the statement, checked against og_<name>_shape"""
+    n = inputs_d.shape[0]
+    assert tuple(inputs_d.shape[1:]) == (n_rec_fields, 32)
+    shp = (C.c_uint64 * 3)()
+    ctx._check(getattr(ctx._lib, f"og_{name}_shape")(depth, shp))
+    assert (int(shp[0]), int(shp[1]), int(shp[2])) == (*shape, n_pub), f"circuit.py and witness.hip disagree on the {name} shape"
+    out = ctx.empty(n, int(shp[0]), 32)
+    ctx._pre()
+    ctx._check(getattr(ctx._lib, f"og_{name}_witness_d")(ctx._h, depth, ctx.ptr(inputs_d), n, ctx.ptr(out)))
+    return out
+
+
+def _records_prove(ctx, pk, name, n_rec_fields, n_pub, depth, inputs_d, rs, return_public):
+    """og_<name>_prove_batch_d of a record statement -> np.uint8 [n, 256], and the public inputs np.uint8 [n, n_pub, 32] when asked for"""
+    n = inputs_d.shape[0]
+    assert tuple(inputs_d.shape[1:]) == (n_rec_fields, 32)
+    rsb = pk._rs_bytes(rs)
+    assert rsb.shape[0] == n
+    out = np.zeros((n, 256), dtype=np.uint8)
+    pub = np.zeros((n, n_pub, 32), dtype=np.uint8) if return_public else None
+    ctx._pre()
+    ctx._check(getattr(ctx._lib, f"og_{name}_prove_batch_d")(ctx._h, pk._h, depth, ctx.ptr(inputs_d), n, rsb.ctypes.data_as(C.c_void_p),
+                                                            out.ctypes.data_as(C.c_void_p),
+                                                            pub.ctypes.data_as(C.c_void_p) if return_public else None))
+    return (out, pub) if return_public else out
+
+
 def pack_inputs(nullifier, secret, amount, recipient, pad_seed, index, siblings, token=0, chain_id=0):
     """one witness-generator input record: (8 + depth) x 32 B (include/owshen_gpu.h):
     nullifier | secret | amount | recipient | pad_seed | index | token | chain_id | siblings[depth]"""
-    vals = [nullifier, secret, amount, recipient, pad_seed, index, token, chain_id] + list(siblings)
-    return np.frombuffer(b"".join(int(v).to_bytes(32, "little") for v in vals), dtype=np.uint8).reshape(-1, 32).copy()
+    return _pack([nullifier, secret, amount, recipient, pad_seed, index, token, chain_id] + list(siblings))
 
 
 def witness(ctx, depth, inputs_d, n_pad3=0, n_pad2=0, out=None):
@@ -332,12 +396,7 @@ def deposit_r1cs(mimc7_constants):
     w_dsq = bld.alloc()
     bld.enforce([(DW_DEPOSITOR, 1)], [(DW_DEPOSITOR, 1)], [(w_dsq, 1)])
     bld.hash2([(DW_NULLIFIER, 1)], [(DW_SECRET, 1)], out_wire=DW_COMMITMENT)
-    assert bld.next == n_wires
-    none_i, none_c = np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
-    pad = (none_c, none_i, none_i)
-    r1cs = R1CS(n_wires, D_N_PUB, _csr(bld.a, *pad, n_wires), _csr(bld.b, *pad, n_wires), _csr(bld.c, *pad, n_wires))
-    assert r1cs.n_constraints == n_constraints
-    return r1cs
+    return _finish(bld, n_wires, D_N_PUB, n_constraints)
 
 
 def deposit_r1cs_native(ctx):
@@ -349,7 +408,7 @@ def deposit_r1cs_native(ctx):
 
 def pack_deposit_inputs(nullifier, secret, depositor):
     """one deposit record: 3 x 32 B, nullifier | secret | depositor (include/owshen_gpu.h)"""
-    return np.frombuffer(b"".join(int(v).to_bytes(32, "little") for v in (nullifier, secret, depositor)), dtype=np.uint8).reshape(3, 32).copy()
+    return _pack((nullifier, secret, depositor))
 
 
 def deposit_witness(ctx, inputs_d):
@@ -411,29 +470,12 @@ def split_r1cs(mimc7_constants, depth=32):
     bld.enforce([(SW_RECIPIENT, 1)], [(SW_RECIPIENT, 1)], [(w_rsq, 1)])
     bld.enforce([(SW_CHAIN, 1)], [(SW_CHAIN, 1)], [(w_csq, 1)])
     bld.enforce([(SW_AMOUNT_OUT, 1), (SW_CHANGE, 1)], [(0, 1)], [(SW_AMOUNT, 1)])
-    for value, bits in ((SW_AMOUNT_OUT, w_obit), (SW_CHANGE, w_cbit)):   # value < 2^128: boolean bits, then the recomposition
-        for i in range(S_N_BITS):
-            bld.enforce([(bits + i, 1)], [(bits + i, 1), (0, R - 1)], [])
-        bld.enforce([(bits + i, 1 << i) for i in range(S_N_BITS)], [(0, 1)], [(value, 1)])
-    inner = bld.hash2([(SW_NULLIFIER, 1)], [(SW_SECRET, 1)])
-    asset = bld.hash2([(SW_AMOUNT, 1)], [(SW_TOKEN, 1)])
-    cur = bld.hash2([(inner, 1)], [(asset, 1)])
-    bld.hash2([(SW_NULLIFIER, 1)], [], out_wire=SW_NH)
-    for l in range(depth):
-        b, s = w_bit + l, w_sib + l
-        bld.enforce([(b, 1)], [(b, 1), (0, R - 1)], [])
-        left = bld.alloc()
-        bld.enforce([(b, 1)], [(s, 1), (cur, R - 1)], [(left, 1), (cur, R - 1)])
-        right = [(s, 1), (cur, 1), (left, R - 1)]
-        cur = bld.hash2([(left, 1)], right, out_wire=SW_ROOT if l == depth - 1 else None)
+    bld.range_check(SW_AMOUNT_OUT, w_obit, S_N_BITS)
+    bld.range_check(SW_CHANGE, w_cbit, S_N_BITS)
+    bld.spend_note(SW_NULLIFIER, SW_SECRET, SW_AMOUNT, SW_TOKEN, SW_NH, w_sib, w_bit, depth, SW_ROOT)
     change_asset = bld.hash2([(SW_CHANGE, 1)], [(SW_TOKEN, 1)])
     bld.hash2([(SW_CHANGE_COMMITMENT, 1)], [(change_asset, 1)], out_wire=SW_CHANGE_LEAF)
-    assert bld.next == n_wires
-    none = np.zeros(0, dtype=np.int64)
-    pad = (none, none, none)
-    r1cs = R1CS(n_wires, S_N_PUB, _csr(bld.a, *pad, n_wires), _csr(bld.b, *pad, n_wires), _csr(bld.c, *pad, n_wires))
-    assert r1cs.n_constraints == n_constraints
-    return r1cs
+    return _finish(bld, n_wires, S_N_PUB, n_constraints)
 
 
 def split_r1cs_native(ctx, depth=32):
@@ -446,45 +488,24 @@ def split_r1cs_native(ctx, depth=32):
 def pack_split_inputs(nullifier, secret, amount, recipient, amount_out, index, siblings, token=0, chain_id=0, change_commitment=0):
     """one split record: (9 + depth) x 32 B (include/owshen_gpu.h):
     nullifier | secret | amount | recipient | amount_out | index | token | chain_id | change_commitment | siblings[depth]"""
-    vals = [nullifier, secret, amount, recipient, amount_out, index, token, chain_id, change_commitment] + list(siblings)
-    return np.frombuffer(b"".join(int(v).to_bytes(32, "little") for v in vals), dtype=np.uint8).reshape(-1, 32).copy()
+    return _pack([nullifier, secret, amount, recipient, amount_out, index, token, chain_id, change_commitment] + list(siblings))
 
 
 def split_witness(ctx, depth, inputs_d):
     """inputs_d: device uint8 [n, 9 + depth, 32] -> device uint8 [n, n_wires, 32] (og_split_witness_d)"""
-    n = inputs_d.shape[0]
-    assert tuple(inputs_d.shape[1:]) == (S_N_REC + depth, 32)
-    shp = (C.c_uint64 * 3)()
-    ctx._check(ctx._lib.og_split_shape(depth, shp))
-    assert (int(shp[0]), int(shp[1]), int(shp[2])) == (*split_shape(depth), S_N_PUB), "circuit.py and witness.hip disagree on the split shape"
-    out = ctx.empty(n, int(shp[0]), 32)
-    ctx._pre()
-    ctx._check(ctx._lib.og_split_witness_d(ctx._h, depth, ctx.ptr(inputs_d), n, ctx.ptr(out)))
-    return out
+    return _records_witness(ctx, "split", S_N_REC + depth, depth, inputs_d, split_shape(depth), S_N_PUB)
 
 
 def split_prove(ctx, pk, depth, inputs_d, rs, return_public=False):
     """inputs_d: device uint8 [n, 9 + depth, 32]; rs: (r, s) pairs or uint8 [n, 64] -> np.uint8 [n, 256] (og_split_prove_batch_d);
     return_public: also (root, nullifier_hash, recipient, amount_out, token, chain_id, change_leaf) of every proof, np.uint8 [n, 7, 32]"""
-    n = inputs_d.shape[0]
-    assert tuple(inputs_d.shape[1:]) == (S_N_REC + depth, 32)
-    rsb = pk._rs_bytes(rs)
-    assert rsb.shape[0] == n
-    out = np.zeros((n, 256), dtype=np.uint8)
-    pub = np.zeros((n, S_N_PUB, 32), dtype=np.uint8) if return_public else None
-    ctx._pre()
-    ctx._check(ctx._lib.og_split_prove_batch_d(ctx._h, pk._h, depth, ctx.ptr(inputs_d), n, rsb.ctypes.data_as(C.c_void_p),
-                                               out.ctypes.data_as(C.c_void_p), pub.ctypes.data_as(C.c_void_p) if return_public else None))
-    return (out, pub) if return_public else out
+    return _records_prove(ctx, pk, "split", S_N_REC + depth, S_N_PUB, depth, inputs_d, rs, return_public)
 
 
 def split_change_leaf(change_commitment, change, token, ctx):
     """the ledger's side of a split: the leaf of the change note, H(change_commitment, H(change, token)), through og_mimc7_hash2_d
     (the value of public input 7; what og_mimc7_append_d appends).  Returns an int."""
-    def dev(v):
-        return ctx.to_device(np.frombuffer(int(v).to_bytes(32, "little"), dtype=np.uint8).reshape(1, 32).copy())
-
-    leaf = ctx.mimc7_hash2(dev(change_commitment), ctx.mimc7_hash2(dev(change), dev(token)))
+    leaf = ctx.mimc7_hash2(_dev(ctx, change_commitment), ctx.mimc7_hash2(_dev(ctx, change), _dev(ctx, token)))
     return int.from_bytes(ctx.to_host(leaf).tobytes(), "little")
 
 
@@ -517,31 +538,13 @@ def join_r1cs(mimc7_constants, depth=32):
     bld.enforce([(JW_CHAIN, 1)], [(JW_CHAIN, 1)], [(w_csq, 1)])
     bld.enforce([(JW_NOTE_A + 2, 1), (JW_NOTE_B + 2, 1)], [(0, 1)], [(JW_SUM, 1)])
     bld.enforce([(JW_NH_A, 1), (JW_NH_B, R - 1)], [(JW_NH_DIFF_INV, 1)], [(0, 1)])      # two different notes
-    for v, value in enumerate((JW_NOTE_A + 2, JW_NOTE_B + 2, JW_SUM)):   # value < 2^128: boolean bits, then the recomposition
-        bits = w_bits + v * J_N_BITS
-        for i in range(J_N_BITS):
-            bld.enforce([(bits + i, 1)], [(bits + i, 1), (0, R - 1)], [])
-        bld.enforce([(bits + i, 1 << i) for i in range(J_N_BITS)], [(0, 1)], [(value, 1)])
+    for v, value in enumerate((JW_NOTE_A + 2, JW_NOTE_B + 2, JW_SUM)):
+        bld.range_check(value, w_bits + v * J_N_BITS, J_N_BITS)
     for x, (note, w_nh) in enumerate(((JW_NOTE_A, JW_NH_A), (JW_NOTE_B, JW_NH_B))):   # both walks end in wire 1
-        inner = bld.hash2([(note, 1)], [(note + 1, 1)])
-        asset = bld.hash2([(note + 2, 1)], [(JW_TOKEN, 1)])
-        cur = bld.hash2([(inner, 1)], [(asset, 1)])
-        bld.hash2([(note, 1)], [], out_wire=w_nh)
-        for l in range(depth):
-            b, s = w_bit + x * depth + l, w_sib + x * depth + l
-            bld.enforce([(b, 1)], [(b, 1), (0, R - 1)], [])
-            left = bld.alloc()
-            bld.enforce([(b, 1)], [(s, 1), (cur, R - 1)], [(left, 1), (cur, R - 1)])
-            right = [(s, 1), (cur, 1), (left, R - 1)]
-            cur = bld.hash2([(left, 1)], right, out_wire=JW_ROOT if l == depth - 1 else None)
+        bld.spend_note(note, note + 1, note + 2, JW_TOKEN, w_nh, w_sib + x * depth, w_bit + x * depth, depth, JW_ROOT)
     out_asset = bld.hash2([(JW_SUM, 1)], [(JW_TOKEN, 1)])
     bld.hash2([(JW_OUT_COMMITMENT, 1)], [(out_asset, 1)], out_wire=JW_OUT_LEAF)
-    assert bld.next == n_wires
-    none = np.zeros(0, dtype=np.int64)
-    pad = (none, none, none)
-    r1cs = R1CS(n_wires, J_N_PUB, _csr(bld.a, *pad, n_wires), _csr(bld.b, *pad, n_wires), _csr(bld.c, *pad, n_wires))
-    assert r1cs.n_constraints == n_constraints
-    return r1cs
+    return _finish(bld, n_wires, J_N_PUB, n_constraints)
 
 
 def join_r1cs_native(ctx, depth=32):
@@ -558,45 +561,24 @@ def pack_join_inputs(nullifier_a, secret_a, amount_a, index_a, siblings_a, nulli
     | siblings_a[depth] | siblings_b[depth]"""
     assert len(siblings_a) == len(siblings_b)
     vals = [nullifier_a, secret_a, amount_a, index_a, nullifier_b, secret_b, amount_b, index_b, token, chain_id, out_commitment]
-    vals += list(siblings_a) + list(siblings_b)
-    return np.frombuffer(b"".join(int(v).to_bytes(32, "little") for v in vals), dtype=np.uint8).reshape(-1, 32).copy()
+    return _pack(vals + list(siblings_a) + list(siblings_b))
 
 
 def join_witness(ctx, depth, inputs_d):
     """inputs_d: device uint8 [n, 11 + 2 depth, 32] -> device uint8 [n, n_wires, 32] (og_join_witness_d)"""
-    n = inputs_d.shape[0]
-    assert tuple(inputs_d.shape[1:]) == (J_N_REC + 2 * depth, 32)
-    shp = (C.c_uint64 * 3)()
-    ctx._check(ctx._lib.og_join_shape(depth, shp))
-    assert (int(shp[0]), int(shp[1]), int(shp[2])) == (*join_shape(depth), J_N_PUB), "circuit.py and witness.hip disagree on the join shape"
-    out = ctx.empty(n, int(shp[0]), 32)
-    ctx._pre()
-    ctx._check(ctx._lib.og_join_witness_d(ctx._h, depth, ctx.ptr(inputs_d), n, ctx.ptr(out)))
-    return out
+    return _records_witness(ctx, "join", J_N_REC + 2 * depth, depth, inputs_d, join_shape(depth), J_N_PUB)
 
 
 def join_prove(ctx, pk, depth, inputs_d, rs, return_public=False):
     """inputs_d: device uint8 [n, 11 + 2 depth, 32]; rs: (r, s) pairs or uint8 [n, 64] -> np.uint8 [n, 256] (og_join_prove_batch_d);
     return_public: also (root, nullifier_hash_a, nullifier_hash_b, chain_id, out_leaf) of every proof, np.uint8 [n, 5, 32]"""
-    n = inputs_d.shape[0]
-    assert tuple(inputs_d.shape[1:]) == (J_N_REC + 2 * depth, 32)
-    rsb = pk._rs_bytes(rs)
-    assert rsb.shape[0] == n
-    out = np.zeros((n, 256), dtype=np.uint8)
-    pub = np.zeros((n, J_N_PUB, 32), dtype=np.uint8) if return_public else None
-    ctx._pre()
-    ctx._check(ctx._lib.og_join_prove_batch_d(ctx._h, pk._h, depth, ctx.ptr(inputs_d), n, rsb.ctypes.data_as(C.c_void_p),
-                                              out.ctypes.data_as(C.c_void_p), pub.ctypes.data_as(C.c_void_p) if return_public else None))
-    return (out, pub) if return_public else out
+    return _records_prove(ctx, pk, "join", J_N_REC + 2 * depth, J_N_PUB, depth, inputs_d, rs, return_public)
 
 
 def join_out_leaf(out_commitment, total, token, ctx):
     """the ledger's and the receiver's side of a join: the leaf of the joined note, H(out_commitment, H(sum, token)), through
     og_mimc7_hash2_d (the value of public input 5; what og_mimc7_append_d appends).  Returns an int."""
-    def dev(v):
-        return ctx.to_device(np.frombuffer(int(v).to_bytes(32, "little"), dtype=np.uint8).reshape(1, 32).copy())
-
-    leaf = ctx.mimc7_hash2(dev(out_commitment), ctx.mimc7_hash2(dev(total), dev(token)))
+    leaf = ctx.mimc7_hash2(_dev(ctx, out_commitment), ctx.mimc7_hash2(_dev(ctx, total), _dev(ctx, token)))
     return int.from_bytes(ctx.to_host(leaf).tobytes(), "little")
 
 
@@ -628,31 +610,14 @@ def transfer_r1cs(mimc7_constants, depth=32):
     w_cbit = bld.alloc(T_N_BITS)
     bld.enforce([(TW_CHAIN, 1)], [(TW_CHAIN, 1)], [(w_csq, 1)])
     bld.enforce([(TW_PAY_AMOUNT, 1), (TW_CHANGE, 1)], [(0, 1)], [(TW_AMOUNT, 1)])
-    for value, bits in ((TW_PAY_AMOUNT, w_pbit), (TW_CHANGE, w_cbit)):   # value < 2^128: boolean bits, then the recomposition
-        for i in range(T_N_BITS):
-            bld.enforce([(bits + i, 1)], [(bits + i, 1), (0, R - 1)], [])
-        bld.enforce([(bits + i, 1 << i) for i in range(T_N_BITS)], [(0, 1)], [(value, 1)])
-    inner = bld.hash2([(TW_NULLIFIER, 1)], [(TW_SECRET, 1)])
-    asset = bld.hash2([(TW_AMOUNT, 1)], [(TW_TOKEN, 1)])
-    cur = bld.hash2([(inner, 1)], [(asset, 1)])
-    bld.hash2([(TW_NULLIFIER, 1)], [], out_wire=TW_NH)
-    for l in range(depth):
-        b, s = w_bit + l, w_sib + l
-        bld.enforce([(b, 1)], [(b, 1), (0, R - 1)], [])
-        left = bld.alloc()
-        bld.enforce([(b, 1)], [(s, 1), (cur, R - 1)], [(left, 1), (cur, R - 1)])
-        right = [(s, 1), (cur, 1), (left, R - 1)]
-        cur = bld.hash2([(left, 1)], right, out_wire=TW_ROOT if l == depth - 1 else None)
+    bld.range_check(TW_PAY_AMOUNT, w_pbit, T_N_BITS)
+    bld.range_check(TW_CHANGE, w_cbit, T_N_BITS)
+    bld.spend_note(TW_NULLIFIER, TW_SECRET, TW_AMOUNT, TW_TOKEN, TW_NH, w_sib, w_bit, depth, TW_ROOT)
     pay_asset = bld.hash2([(TW_PAY_AMOUNT, 1)], [(TW_TOKEN, 1)])
     bld.hash2([(TW_PAY_COMMITMENT, 1)], [(pay_asset, 1)], out_wire=TW_PAY_LEAF)
     change_asset = bld.hash2([(TW_CHANGE, 1)], [(TW_TOKEN, 1)])
     bld.hash2([(TW_CHANGE_COMMITMENT, 1)], [(change_asset, 1)], out_wire=TW_CHANGE_LEAF)
-    assert bld.next == n_wires
-    none = np.zeros(0, dtype=np.int64)
-    pad = (none, none, none)
-    r1cs = R1CS(n_wires, T_N_PUB, _csr(bld.a, *pad, n_wires), _csr(bld.b, *pad, n_wires), _csr(bld.c, *pad, n_wires))
-    assert r1cs.n_constraints == n_constraints
-    return r1cs
+    return _finish(bld, n_wires, T_N_PUB, n_constraints)
 
 
 def transfer_r1cs_native(ctx, depth=32):
@@ -665,47 +630,26 @@ def transfer_r1cs_native(ctx, depth=32):
 def pack_transfer_inputs(nullifier, secret, amount, index, siblings, token=0, chain_id=0, pay_commitment=0, pay_amount=0, change_commitment=0):
     """one transfer record: (9 + depth) x 32 B (include/owshen_gpu.h):
     nullifier | secret | amount | index | token | chain_id | pay_commitment | pay_amount | change_commitment | siblings[depth]"""
-    vals = [nullifier, secret, amount, index, token, chain_id, pay_commitment, pay_amount, change_commitment] + list(siblings)
-    return np.frombuffer(b"".join(int(v).to_bytes(32, "little") for v in vals), dtype=np.uint8).reshape(-1, 32).copy()
+    return _pack([nullifier, secret, amount, index, token, chain_id, pay_commitment, pay_amount, change_commitment] + list(siblings))
 
 
 def transfer_witness(ctx, depth, inputs_d):
     """inputs_d: device uint8 [n, 9 + depth, 32] -> device uint8 [n, n_wires, 32] (og_transfer_witness_d)"""
-    n = inputs_d.shape[0]
-    assert tuple(inputs_d.shape[1:]) == (T_N_REC + depth, 32)
-    shp = (C.c_uint64 * 3)()
-    ctx._check(ctx._lib.og_transfer_shape(depth, shp))
-    assert (int(shp[0]), int(shp[1]), int(shp[2])) == (*transfer_shape(depth), T_N_PUB), "circuit.py and witness.hip disagree on the transfer shape"
-    out = ctx.empty(n, int(shp[0]), 32)
-    ctx._pre()
-    ctx._check(ctx._lib.og_transfer_witness_d(ctx._h, depth, ctx.ptr(inputs_d), n, ctx.ptr(out)))
-    return out
+    return _records_witness(ctx, "transfer", T_N_REC + depth, depth, inputs_d, transfer_shape(depth), T_N_PUB)
 
 
 def transfer_prove(ctx, pk, depth, inputs_d, rs, return_public=False):
     """inputs_d: device uint8 [n, 9 + depth, 32]; rs: (r, s) pairs or uint8 [n, 64] -> np.uint8 [n, 256] (og_transfer_prove_batch_d);
     return_public: also (root, nullifier_hash, chain_id, pay_leaf, change_leaf) of every proof, np.uint8 [n, 5, 32]"""
-    n = inputs_d.shape[0]
-    assert tuple(inputs_d.shape[1:]) == (T_N_REC + depth, 32)
-    rsb = pk._rs_bytes(rs)
-    assert rsb.shape[0] == n
-    out = np.zeros((n, 256), dtype=np.uint8)
-    pub = np.zeros((n, T_N_PUB, 32), dtype=np.uint8) if return_public else None
-    ctx._pre()
-    ctx._check(ctx._lib.og_transfer_prove_batch_d(ctx._h, pk._h, depth, ctx.ptr(inputs_d), n, rsb.ctypes.data_as(C.c_void_p),
-                                                  out.ctypes.data_as(C.c_void_p), pub.ctypes.data_as(C.c_void_p) if return_public else None))
-    return (out, pub) if return_public else out
+    return _records_prove(ctx, pk, "transfer", T_N_REC + depth, T_N_PUB, depth, inputs_d, rs, return_public)
 
 
 def transfer_leaves(pay_commitment, pay_amount, change_commitment, change, token, ctx):
     """the ledger's and the payee's side of a transfer: (pay_leaf, change_leaf) = (H(pay_commitment, H(pay_amount, token)),
     H(change_commitment, H(change, token))) through og_mimc7_hash2_d -- the values of public inputs 4 and 5, what og_mimc7_append_d
     appends, in this order.  Returns two ints."""
-    def dev(*vs):
-        return ctx.to_device(np.frombuffer(b"".join(int(v).to_bytes(32, "little") for v in vs), dtype=np.uint8).reshape(len(vs), 32).copy())
-
-    tok = dev(token, token)
-    leaves = ctx.mimc7_hash2(dev(pay_commitment, change_commitment), ctx.mimc7_hash2(dev(pay_amount, change), tok))
+    tok = _dev(ctx, token, token)
+    leaves = ctx.mimc7_hash2(_dev(ctx, pay_commitment, change_commitment), ctx.mimc7_hash2(_dev(ctx, pay_amount, change), tok))
     return tuple(int.from_bytes(row.tobytes(), "little") for row in ctx.to_host(leaves))
 
 

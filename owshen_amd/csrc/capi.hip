@@ -3,6 +3,7 @@
 // thread-local message, mirroring the anyhow::Result convention of the reference's callers
 // (/root/reference/src/utils.rs:5-20).
 #include "ctx.h"
+#include "statements.h"
 #include "msm.hip.h"
 #include "glv.h"
 #include <string.h>
@@ -44,31 +45,8 @@ int prove_batch_device(og_ctx*, const og_pk*, const uint8_t*, size_t, const uint
 int prove_batch_host(og_ctx*, const og_pk*, const uint8_t*, size_t, const uint8_t*, uint8_t*);
 int scalar_mul_fixed(og_ctx*, int, const uint8_t*, const uint8_t*, size_t, uint8_t*);
 int lagrange_evals(og_ctx*, int, const uint8_t*, uint8_t*);
-int withdraw_shape_query(int, uint64_t, uint64_t, uint64_t*);
-int withdraw_witness(og_ctx*, int, uint64_t, uint64_t, const uint8_t*, size_t, uint8_t*);
-int withdraw_records_ok(og_ctx*, int, const uint8_t*, size_t, size_t);
 int verify_cpu(const uint8_t*, size_t, const uint8_t*, size_t, const uint8_t*, int*);
-int withdraw_prove_batch(og_ctx*, const og_pk*, int, uint64_t, uint64_t, const uint8_t*, size_t, const uint8_t*, uint8_t*, uint8_t*);
-int withdraw_prove_batch_submit(og_ctx*, const og_pk*, int, uint64_t, uint64_t, const uint8_t*, size_t, const uint8_t*, uint8_t*, uint8_t*,
-                                og_job**);
-int deposit_shape_query(uint64_t*);
-int deposit_records_ok(og_ctx*, const uint8_t*, size_t, size_t);
-int deposit_witness(og_ctx*, const uint8_t*, size_t, uint8_t*);
-int deposit_prove_batch(og_ctx*, const og_pk*, const uint8_t*, size_t, const uint8_t*, uint8_t*, uint8_t*);
-int split_shape_query(int, uint64_t*);
-int split_records_ok(og_ctx*, int, const uint8_t*, size_t, size_t);
-int split_witness(og_ctx*, int, const uint8_t*, size_t, uint8_t*);
-int split_prove_batch(og_ctx*, const og_pk*, int, const uint8_t*, size_t, const uint8_t*, uint8_t*, uint8_t*);
-int join_shape_query(int, uint64_t*);
-int join_records_ok(og_ctx*, int, const uint8_t*, size_t, size_t);
-int join_witness(og_ctx*, int, const uint8_t*, size_t, uint8_t*);
-int join_prove_batch(og_ctx*, const og_pk*, int, const uint8_t*, size_t, const uint8_t*, uint8_t*, uint8_t*);
-int transfer_shape_query(int, uint64_t*);
-int transfer_records_ok(og_ctx*, int, const uint8_t*, size_t, size_t);
-int transfer_witness(og_ctx*, int, const uint8_t*, size_t, uint8_t*);
-int transfer_prove_batch(og_ctx*, const og_pk*, int, const uint8_t*, size_t, const uint8_t*, uint8_t*, uint8_t*);
 int job_wait(og_job*);
-int withdraw_prove_partials_enqueue(og_ctx*, const og_pk*, int, uint64_t, uint64_t, const uint8_t*, size_t, int, int, uint8_t*, uint8_t*, og_job**);
 int prove_partials_enqueue(og_ctx*, const og_pk*, const uint8_t*, size_t, int, int, uint8_t*, og_job**);
 int prove_from_partials(og_ctx*, const og_pk*, const uint8_t*, int, size_t, const uint8_t*, uint8_t*);
 bool glv_pair_ok();
@@ -96,6 +74,39 @@ using namespace og;
   std::lock_guard<std::mutex> _lk((ctx)->mu);    \
   OG_HIP(hipSetDevice((ctx)->device))
 #define CTX_OK(ctx) OG_REQUIRE((ctx) != nullptr, "null og_ctx")
+
+// ---- the bodies behind og_<statement>_shape / _witness_d / _prove_batch_d of the record statements (statements.h) -------------------
+static int record_shape(const RecordStatement& st, int depth, uint64_t shape[3]) {
+  return guarded([&]() -> int {
+    OG_REQUIRE(shape != nullptr, "og_" + std::string(st.name) + "_shape: null argument");
+    return records_shape_query(st, depth, shape);
+  });
+}
+
+static int record_witness_d(const RecordStatement& st, og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, uint8_t* witness_out_d) {
+  return guarded([&]() -> int {
+    CTX_OK(ctx);
+    OG_REQUIRE(n <= 65535, "og_" + std::string(st.name) + "_witness_d: at most 65535 witnesses per call");  // (before any scratch is grown or any kernel launched)
+    OG_REQUIRE(n == 0 || (inputs_d && witness_out_d), "og_" + std::string(st.name) + "_witness_d: null argument");
+    LOCKED(ctx);
+    OG_TRY(records_ok(st, ctx, depth, inputs_d, n, 0));
+    OG_TRY(records_witness(st, ctx, depth, inputs_d, n, witness_out_d));
+    OG_HIP(hipStreamSynchronize(ctx->stream));
+    return OG_OK;
+  });
+}
+
+static int record_prove_batch_d(const RecordStatement& st, og_ctx* ctx, const og_pk* pk, int depth, const uint8_t* inputs_d, size_t n,
+                                const uint8_t* rs, uint8_t* proofs_out, uint8_t* public_out) {
+  return guarded([&]() -> int {
+    CTX_OK(ctx);
+    OG_REQUIRE(pk != nullptr, "og_" + std::string(st.name) + "_prove_batch_d: null key");
+    OG_REQUIRE(n == 0 || (inputs_d && rs && proofs_out), "og_" + std::string(st.name) + "_prove_batch_d: null argument");
+    if (n == 0) return OG_OK;
+    LOCKED(ctx);
+    return records_prove_batch(st, ctx, pk, depth, inputs_d, n, rs, proofs_out, public_out);
+  });
+}
 
 extern "C" {
 
@@ -796,100 +807,31 @@ int og_deposit_prove_batch_d(og_ctx* ctx, const og_pk* pk, const uint8_t* inputs
   });
 }
 
-int og_split_shape(int depth, uint64_t shape[3]) {
-  return guarded([&]() -> int {
-    OG_REQUIRE(shape != nullptr, "og_split_shape: null argument");
-    return split_shape_query(depth, shape);
-  });
-}
-
+int og_split_shape(int depth, uint64_t shape[3]) { return record_shape(ST_SPLIT, depth, shape); }
 int og_split_witness_d(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, uint8_t* witness_out_d) {
-  return guarded([&]() -> int {
-    CTX_OK(ctx);
-    OG_REQUIRE(n <= 65535, "og_split_witness_d: at most 65535 witnesses per call");  // (before any scratch is grown or any kernel launched)
-    OG_REQUIRE(n == 0 || (inputs_d && witness_out_d), "og_split_witness_d: null argument");
-    LOCKED(ctx);
-    OG_TRY(split_records_ok(ctx, depth, inputs_d, n, 0));
-    OG_TRY(split_witness(ctx, depth, inputs_d, n, witness_out_d));
-    OG_HIP(hipStreamSynchronize(ctx->stream));
-    return OG_OK;
-  });
+  return record_witness_d(ST_SPLIT, ctx, depth, inputs_d, n, witness_out_d);
 }
-
 int og_split_prove_batch_d(og_ctx* ctx, const og_pk* pk, int depth, const uint8_t* inputs_d, size_t n, const uint8_t* rs,
                            uint8_t* proofs_out, uint8_t* public_out) {
-  return guarded([&]() -> int {
-    CTX_OK(ctx);
-    OG_REQUIRE(pk != nullptr, "og_split_prove_batch_d: null key");
-    OG_REQUIRE(n == 0 || (inputs_d && rs && proofs_out), "og_split_prove_batch_d: null argument");
-    if (n == 0) return OG_OK;
-    LOCKED(ctx);
-    return split_prove_batch(ctx, pk, depth, inputs_d, n, rs, proofs_out, public_out);
-  });
+  return record_prove_batch_d(ST_SPLIT, ctx, pk, depth, inputs_d, n, rs, proofs_out, public_out);
 }
 
-int og_join_shape(int depth, uint64_t shape[3]) {
-  return guarded([&]() -> int {
-    OG_REQUIRE(shape != nullptr, "og_join_shape: null argument");
-    return join_shape_query(depth, shape);
-  });
-}
-
+int og_join_shape(int depth, uint64_t shape[3]) { return record_shape(ST_JOIN, depth, shape); }
 int og_join_witness_d(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, uint8_t* witness_out_d) {
-  return guarded([&]() -> int {
-    CTX_OK(ctx);
-    OG_REQUIRE(n <= 65535, "og_join_witness_d: at most 65535 witnesses per call");  // (before any scratch is grown or any kernel launched)
-    OG_REQUIRE(n == 0 || (inputs_d && witness_out_d), "og_join_witness_d: null argument");
-    LOCKED(ctx);
-    OG_TRY(join_records_ok(ctx, depth, inputs_d, n, 0));
-    OG_TRY(join_witness(ctx, depth, inputs_d, n, witness_out_d));
-    OG_HIP(hipStreamSynchronize(ctx->stream));
-    return OG_OK;
-  });
+  return record_witness_d(ST_JOIN, ctx, depth, inputs_d, n, witness_out_d);
 }
-
 int og_join_prove_batch_d(og_ctx* ctx, const og_pk* pk, int depth, const uint8_t* inputs_d, size_t n, const uint8_t* rs,
                           uint8_t* proofs_out, uint8_t* public_out) {
-  return guarded([&]() -> int {
-    CTX_OK(ctx);
-    OG_REQUIRE(pk != nullptr, "og_join_prove_batch_d: null key");
-    OG_REQUIRE(n == 0 || (inputs_d && rs && proofs_out), "og_join_prove_batch_d: null argument");
-    if (n == 0) return OG_OK;
-    LOCKED(ctx);
-    return join_prove_batch(ctx, pk, depth, inputs_d, n, rs, proofs_out, public_out);
-  });
+  return record_prove_batch_d(ST_JOIN, ctx, pk, depth, inputs_d, n, rs, proofs_out, public_out);
 }
 
-int og_transfer_shape(int depth, uint64_t shape[3]) {
-  return guarded([&]() -> int {
-    OG_REQUIRE(shape != nullptr, "og_transfer_shape: null argument");
-    return transfer_shape_query(depth, shape);
-  });
-}
-
+int og_transfer_shape(int depth, uint64_t shape[3]) { return record_shape(ST_TRANSFER, depth, shape); }
 int og_transfer_witness_d(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, uint8_t* witness_out_d) {
-  return guarded([&]() -> int {
-    CTX_OK(ctx);
-    OG_REQUIRE(n <= 65535, "og_transfer_witness_d: at most 65535 witnesses per call");  // (before any scratch is grown or any kernel launched)
-    OG_REQUIRE(n == 0 || (inputs_d && witness_out_d), "og_transfer_witness_d: null argument");
-    LOCKED(ctx);
-    OG_TRY(transfer_records_ok(ctx, depth, inputs_d, n, 0));
-    OG_TRY(transfer_witness(ctx, depth, inputs_d, n, witness_out_d));
-    OG_HIP(hipStreamSynchronize(ctx->stream));
-    return OG_OK;
-  });
+  return record_witness_d(ST_TRANSFER, ctx, depth, inputs_d, n, witness_out_d);
 }
-
 int og_transfer_prove_batch_d(og_ctx* ctx, const og_pk* pk, int depth, const uint8_t* inputs_d, size_t n, const uint8_t* rs,
                               uint8_t* proofs_out, uint8_t* public_out) {
-  return guarded([&]() -> int {
-    CTX_OK(ctx);
-    OG_REQUIRE(pk != nullptr, "og_transfer_prove_batch_d: null key");
-    OG_REQUIRE(n == 0 || (inputs_d && rs && proofs_out), "og_transfer_prove_batch_d: null argument");
-    if (n == 0) return OG_OK;
-    LOCKED(ctx);
-    return transfer_prove_batch(ctx, pk, depth, inputs_d, n, rs, proofs_out, public_out);
-  });
+  return record_prove_batch_d(ST_TRANSFER, ctx, pk, depth, inputs_d, n, rs, proofs_out, public_out);
 }
 
 int og_withdraw_prove_partials_d(og_ctx* ctx, const og_pk* pk, int depth, uint64_t n_pad3, uint64_t n_pad2, const uint8_t* inputs_d,

@@ -20,6 +20,7 @@
 //   k_assemble_*     r/s blinding (s delta2 from a fixed-base table), final sums, affine conversion, 256 B proofs
 // (r, s) are explicit inputs: proofs are reproducible and bit-comparable with the oracle.
 #include "ctx.h"
+#include "statements.h"
 #include "msm.hip.h"
 #include "field.hip.h"
 #include "glv.h"
@@ -76,10 +77,6 @@ int assemble_g1_early(og_ctx*, const uint8_t*, const uint8_t*, const uint8_t*, c
 int assemble_g1_late(og_ctx*, const uint8_t*, const uint8_t*, size_t, const uint8_t*, uint8_t*, bool);
 int fixed_table_g2(og_ctx*, const uint8_t*, uint8_t*);
 int ntt_domain_consts(og_ctx* ctx, int log_n, uint8_t** consts_d);
-int withdraw_witness(og_ctx* ctx, int depth, uint64_t n_pad3, uint64_t n_pad2, const uint8_t* inputs_d, size_t n, uint8_t* out_d);
-int withdraw_shape_query(int depth, uint64_t n_pad3, uint64_t n_pad2, uint64_t out[3]);
-int withdraw_check_records(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, uint32_t* bad_d);
-const char* withdraw_field_name(uint32_t f);
 
 // ---- sparse matrix x witness ---------------------------------------------------------
 // out[g][row] = sum_k val[k] * x[g][col[k]] for row < n_rows, 0 for n_rows <= row < n_out.
@@ -1330,8 +1327,7 @@ int withdraw_records_ok(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t 
   return OG_OK;
 }
 
-// inputs (withdraw circuit records) -> proofs: witness generation fused into the lanes
-int withdraw_prove_batch(og_ctx*, const og_pk*, int, uint64_t, uint64_t, const uint8_t*, size_t, const uint8_t*, uint8_t*, uint8_t*);
+// inputs (withdraw circuit records) -> proofs: witness generation fused into the lanes (withdraw_prove_batch, below)
 // witnesses are generated inside the pipeline from this many wire values per sub-batch on (OG_GEN_MIN: test hook)
 static size_t gen_threshold() { return (size_t)OG_HOOK_INT("OG_GEN_MIN", (long long)1 << 26); }
 // Witnesses inside prove_enqueue (on stream 0, the queries' streams waiting for an event) instead of a slab up front with the host
@@ -1458,9 +1454,6 @@ int withdraw_prove_batch(og_ctx* ctx, const og_pk* pk, int depth, uint64_t n_pad
 
 // deposit records (nullifier | secret | depositor) -> proofs of the deposit statement (witness.hip, oracle/py/deposit.py): a small
 // circuit, so whole slabs of witnesses in one launch, then the ordinary batched prover
-int deposit_shape_query(uint64_t out[3]);
-int deposit_records_ok(og_ctx*, const uint8_t*, size_t, size_t);
-int deposit_witness(og_ctx*, const uint8_t*, size_t, uint8_t*);
 int deposit_prove_batch(og_ctx* ctx, const og_pk* pk, const uint8_t* inputs_d, size_t n, const uint8_t* rs, uint8_t* proofs, uint8_t* pub_out) {
   uint64_t shp[3];
   OG_TRY(deposit_shape_query(shp));
@@ -1483,20 +1476,23 @@ int deposit_prove_batch(og_ctx* ctx, const og_pk* pk, const uint8_t* inputs_d, s
   return OG_OK;
 }
 
-// records -> proofs for the statements whose witnesses depend on a depth alone (split, join, transfer): per slab -- sized as the small-circuit
-// branch of withdraw_prove_batch -- check the records, generate the witnesses in one launch, then the ordinary batched prover.
-// `rec`: bytes per record; records_ok / witness: the statement's boundary check and its witness launch (witness.hip)
-typedef int (*records_ok_fn)(og_ctx*, int, const uint8_t*, size_t, size_t);
-typedef int (*witness_fn)(og_ctx*, int, const uint8_t*, size_t, uint8_t*);
-static int records_prove_batch(og_ctx* ctx, const og_pk* pk, int depth, size_t rec, records_ok_fn records_ok, witness_fn witness,
-                               const uint8_t* inputs_d, size_t n, const uint8_t* rs, uint8_t* proofs, uint8_t* pub_out) {
+// records -> proofs for the record statements (statements.h: split, join, transfer): per slab -- sized as the small-circuit branch of
+// withdraw_prove_batch -- check the records, generate the witnesses in one launch, then the ordinary batched prover.  For join, the
+// prover's row check is what answers OG_ERR_UNSATISFIED for two notes under different roots: the witness carries note a's root in wire 1
+int records_prove_batch(const RecordStatement& st, og_ctx* ctx, const og_pk* pk, int depth, const uint8_t* inputs_d, size_t n, const uint8_t* rs,
+                        uint8_t* proofs, uint8_t* pub_out) {
+  uint64_t shp[3];
+  OG_TRY(records_shape_query(st, depth, shp));
+  OG_REQUIRE(shp[0] == pk->m && shp[2] == pk->n_pub,
+             "og_" + std::string(st.name) + "_prove_batch_d: the key is not for this " + st.name + "-statement shape");
+  const size_t rec = record_bytes(st, depth);
   const size_t slab = std::min<size_t>(65535, std::max<size_t>(1, std::min<size_t>(n, ((size_t)16 << 30) / (pk->m * 32))));
   uint8_t* z_d = nullptr;
   OG_TRY(arena_get(ctx, "g16.zall", slab * pk->m * 32, (void**)&z_d));
   for (size_t g0 = 0; g0 < n;) {
     const size_t cnt = std::min(slab, n - g0);
-    OG_TRY(records_ok(ctx, depth, inputs_d + g0 * rec, cnt, g0));
-    OG_TRY(witness(ctx, depth, inputs_d + g0 * rec, cnt, z_d));
+    OG_TRY(records_ok(st, ctx, depth, inputs_d + g0 * rec, cnt, g0));
+    OG_TRY(records_witness(st, ctx, depth, inputs_d + g0 * rec, cnt, z_d));
     OG_HIP(hipStreamSynchronize(ctx->stream));  // both streams of the prover read the slab
     size_t bad = 0;
     int r = prove_batch_impl(ctx, pk, z_d, cnt, rs + g0 * 64, proofs + g0 * 256, &bad, nullptr, pub_out ? pub_out + g0 * pk->n_pub * 32 : nullptr, true);
@@ -1506,44 +1502,6 @@ static int records_prove_batch(og_ctx* ctx, const og_pk* pk, int depth, size_t r
     g0 += cnt;
   }
   return OG_OK;
-}
-
-// split records -> proofs of the split statement (witness.hip, tests/split_spec.py)
-int split_shape_query(int, uint64_t out[3]);
-int split_records_ok(og_ctx*, int, const uint8_t*, size_t, size_t);
-int split_witness(og_ctx*, int, const uint8_t*, size_t, uint8_t*);
-int split_prove_batch(og_ctx* ctx, const og_pk* pk, int depth, const uint8_t* inputs_d, size_t n, const uint8_t* rs, uint8_t* proofs,
-                      uint8_t* pub_out) {
-  uint64_t shp[3];
-  OG_TRY(split_shape_query(depth, shp));
-  OG_REQUIRE(shp[0] == pk->m && shp[2] == pk->n_pub, "og_split_prove_batch_d: the key is not for this split-statement shape");
-  return records_prove_batch(ctx, pk, depth, (size_t)(9 + depth) * 32, split_records_ok, split_witness, inputs_d, n, rs, proofs, pub_out);
-}
-
-// join records -> proofs of the join statement (witness.hip, tests/join_spec.py; two lanes per request in the witness launch).  The
-// prover's row check is what answers OG_ERR_UNSATISFIED for two notes under different roots: the witness carries note a's root in wire 1
-int join_shape_query(int, uint64_t out[3]);
-int join_records_ok(og_ctx*, int, const uint8_t*, size_t, size_t);
-int join_witness(og_ctx*, int, const uint8_t*, size_t, uint8_t*);
-int join_prove_batch(og_ctx* ctx, const og_pk* pk, int depth, const uint8_t* inputs_d, size_t n, const uint8_t* rs, uint8_t* proofs,
-                     uint8_t* pub_out) {
-  uint64_t shp[3];
-  OG_TRY(join_shape_query(depth, shp));
-  OG_REQUIRE(shp[0] == pk->m && shp[2] == pk->n_pub, "og_join_prove_batch_d: the key is not for this join-statement shape");
-  return records_prove_batch(ctx, pk, depth, (size_t)(11 + 2 * depth) * 32, join_records_ok, join_witness, inputs_d, n, rs, proofs, pub_out);
-}
-
-// transfer records -> proofs of the transfer statement (witness.hip, tests/transfer_spec.py): the third user of the slab loop; a call
-// of at most 512 requests walks wave-wide (k_tw9_*), a batch lane-local (k_transfer_core)
-int transfer_shape_query(int, uint64_t out[3]);
-int transfer_records_ok(og_ctx*, int, const uint8_t*, size_t, size_t);
-int transfer_witness(og_ctx*, int, const uint8_t*, size_t, uint8_t*);
-int transfer_prove_batch(og_ctx* ctx, const og_pk* pk, int depth, const uint8_t* inputs_d, size_t n, const uint8_t* rs, uint8_t* proofs,
-                         uint8_t* pub_out) {
-  uint64_t shp[3];
-  OG_TRY(transfer_shape_query(depth, shp));
-  OG_REQUIRE(shp[0] == pk->m && shp[2] == pk->n_pub, "og_transfer_prove_batch_d: the key is not for this transfer-statement shape");
-  return records_prove_batch(ctx, pk, depth, (size_t)(9 + depth) * 32, transfer_records_ok, transfer_witness, inputs_d, n, rs, proofs, pub_out);
 }
 
 // ---- window-sharded proving: the two halves (WinShard above) -------------------------------------------------------------------

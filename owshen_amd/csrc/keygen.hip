@@ -18,6 +18,7 @@
 #include "msm.hip.h"
 #include "field.hip.h"
 #include "keygen.h"
+#include "statements.h"
 #include <string.h>
 #include <stdlib.h>
 #include <algorithm>
@@ -131,39 +132,69 @@ struct R1csBuilder {
     enforce(lc_merge({&k2, &r_lc, &y91}), one(0), one(out));
     return out;
   }
+  // value < 2^128: 128 boolean rows over the wires bits .. bits + 127 (LSB first), then the recomposition row
+  void range128(uint32_t value, uint32_t bits) {
+    const HFr m1 = hfr_neg_one();
+    LC sum;
+    for (uint32_t i = 0; i < 128; i++) {
+      enforce(one(bits + i), LC{{bits + i, hfr_u64(1)}, {0u, m1}}, LC{});
+      HFr p2 = {{0, 0, 0, 0}};
+      p2.v[i >> 6] = 1ull << (i & 63);
+      sum.push_back({bits + i, p2});
+    }
+    enforce(sum, one(0), one(value));
+  }
+  // the path from `cur` up to the wire `root`, which is the output wire of the last level's hash: per level a boolean index bit, the
+  // `left` selector wire (allocated here) and one hash
+  void merkle_walk(uint32_t cur, uint32_t w_sib, uint32_t w_bit, int depth, uint32_t root) {
+    const HFr m1 = hfr_neg_one();
+    for (int l = 0; l < depth; l++) {
+      const uint32_t bit = w_bit + l, s = w_sib + l;
+      enforce(one(bit), LC{{bit, hfr_u64(1)}, {0u, m1}}, LC{});              // bit (bit - 1) = 0
+      const uint32_t left = alloc();
+      enforce(one(bit), LC{{s, hfr_u64(1)}, {cur, m1}}, LC{{left, hfr_u64(1)}, {cur, m1}});  // left = cur + bit (s - cur)
+      const LC right{{s, hfr_u64(1)}, {cur, hfr_u64(1)}, {left, m1}};
+      cur = hash2(one(left), right, l == depth - 1 ? (int)root : -1);
+    }
+  }
+  // a note is spent: leaf = H(inner = H(nullifier, secret), asset = H(amount, token)), nullifier_hash = H(nullifier, 0) into the
+  // wire `nh`, then the leaf's path up to `root`
+  void spend_note(uint32_t nullifier, uint32_t secret, uint32_t amount, uint32_t token, uint32_t nh, uint32_t w_sib, uint32_t w_bit, int depth,
+                  uint32_t root) {
+    const uint32_t inner = hash2(one(nullifier), one(secret));
+    const uint32_t asset = hash2(one(amount), one(token));
+    const uint32_t leaf = hash2(one(inner), one(asset));
+    hash2(one(nullifier), LC{}, (int)nh);
+    merkle_walk(leaf, w_sib, w_bit, depth, root);
+  }
 };
+
+// What every builder with a depth starts and ends with: the statement's shape into r and empty matrices -- `n_pub` is the count the
+// builder's wire table is written for --, and, behind the last row, that the rows and wires made are the shape's
+static int r1cs_begin(og_r1cs* r, const uint64_t shp[3], uint64_t n_pub, const std::string& who) {
+  static const char* const words[] = {"zero", "one", "two", "three", "four", "five", "six", "seven"};
+  const std::string count = n_pub < sizeof(words) / sizeof(words[0]) ? std::string(words[n_pub]) : std::to_string(n_pub);
+  r->n_wires = shp[0];
+  r->n_pub = shp[2];
+  for (int k = 0; k < 3; k++) r->ptr[k].assign(1, 0u);
+  OG_REQUIRE(r->n_pub == n_pub, who + ": the statement has " + count + " public inputs");
+  return OG_OK;
+}
 
 constexpr uint32_t KW_ROOT = 1, KW_NH = 2, KW_RECIPIENT = 3, KW_AMOUNT = 4, KW_TOKEN = 5, KW_CHAIN = 6, KW_NULLIFIER = 7, KW_SECRET = 8;
 constexpr uint32_t K_PAD_SEGMENT = 64;
-
-int withdraw_shape_query(int depth, uint64_t n_pad3, uint64_t n_pad2, uint64_t out[3]);
 
 int withdraw_r1cs_build(const uint8_t* mimc_consts, int depth, uint64_t n_pad3, uint64_t n_pad2, int dense, og_r1cs* r) {
   uint64_t shp[3];
   OG_TRY(withdraw_shape_query(depth, n_pad3, n_pad2, shp));
   OG_REQUIRE(n_pad3 < (1ull << 30) && n_pad2 < (1ull << 30), "og_withdraw_r1cs: too many padding gates");
-  r->n_wires = shp[0];
-  r->n_pub = shp[2];
-  for (int k = 0; k < 3; k++) r->ptr[k].assign(1, 0u);
+  OG_TRY(r1cs_begin(r, shp, 6, "og_withdraw_r1cs"));
   R1csBuilder b{r, 0, mimc_consts};
-  const HFr m1 = hfr_neg_one();
-  OG_REQUIRE(r->n_pub == 6, "og_withdraw_r1cs: the statement has six public inputs");
   b.alloc(1 + 6 + 2);
   const uint32_t w_sib = b.alloc(depth), w_bit = b.alloc(depth), w_rsq = b.alloc(), w_csq = b.alloc();
   b.enforce(R1csBuilder::one(KW_RECIPIENT), R1csBuilder::one(KW_RECIPIENT), R1csBuilder::one(w_rsq));
   b.enforce(R1csBuilder::one(KW_CHAIN), R1csBuilder::one(KW_CHAIN), R1csBuilder::one(w_csq));  // binds chain_id to the proof
-  const uint32_t inner = b.hash2(R1csBuilder::one(KW_NULLIFIER), R1csBuilder::one(KW_SECRET));
-  const uint32_t asset = b.hash2(R1csBuilder::one(KW_AMOUNT), R1csBuilder::one(KW_TOKEN));
-  uint32_t cur = b.hash2(R1csBuilder::one(inner), R1csBuilder::one(asset));
-  b.hash2(R1csBuilder::one(KW_NULLIFIER), LC{}, (int)KW_NH);
-  for (int l = 0; l < depth; l++) {
-    const uint32_t bit = w_bit + l, s = w_sib + l;
-    b.enforce(R1csBuilder::one(bit), LC{{bit, hfr_u64(1)}, {0u, m1}}, LC{});              // bit (bit - 1) = 0
-    const uint32_t left = b.alloc();
-    b.enforce(R1csBuilder::one(bit), LC{{s, hfr_u64(1)}, {cur, m1}}, LC{{left, hfr_u64(1)}, {cur, m1}});  // left = cur + bit (s - cur)
-    const LC right{{s, hfr_u64(1)}, {cur, hfr_u64(1)}, {left, m1}};
-    cur = b.hash2(R1csBuilder::one(left), right, l == depth - 1 ? (int)KW_ROOT : -1);
-  }
+  b.spend_note(KW_NULLIFIER, KW_SECRET, KW_AMOUNT, KW_TOKEN, KW_NH, w_sib, w_bit, depth, KW_ROOT);
   const uint32_t pad_base = b.next;
   OG_REQUIRE((uint64_t)pad_base + 3 * n_pad3 + 2 * n_pad2 == r->n_wires, "og_withdraw_r1cs: internal wire count mismatch");
   for (uint64_t g = 0; g < n_pad3; g++) {  // (p + 1)(q + 2) = w
@@ -188,7 +219,6 @@ int withdraw_r1cs_build(const uint8_t* mimc_consts, int depth, uint64_t n_pad3, 
 }
 
 // the deposit statement (oracle/py/deposit.py; witness.hip k_deposit_witness): 735 wires, 731 rows
-int deposit_shape_query(uint64_t out[3]);
 int deposit_r1cs_build(const uint8_t* mimc_consts, og_r1cs* r) {
   uint64_t shp[3];
   OG_TRY(deposit_shape_query(shp));
@@ -205,152 +235,72 @@ int deposit_r1cs_build(const uint8_t* mimc_consts, og_r1cs* r) {
   return OG_OK;
 }
 
-// the split statement (tests/split_spec.py; witness.hip k_split_core): withdraw part of a note, the rest into a change note
-int split_shape_query(int depth, uint64_t out[3]);
-int split_r1cs_build(const uint8_t* mimc_consts, int depth, og_r1cs* r) {
-  uint64_t shp[3];
-  OG_TRY(split_shape_query(depth, shp));
-  r->n_wires = shp[0];
-  r->n_pub = shp[2];
-  for (int k = 0; k < 3; k++) r->ptr[k].assign(1, 0u);
-  R1csBuilder b{r, 0, mimc_consts};
-  const HFr m1 = hfr_neg_one();
+// ---- the record statements (statements.h): each is its wire table, the rows of its own and calls of the shared gadgets ------------------
+// the split statement (tests/split_spec.py; witness.hip k_split_core / k_sw9_*): withdraw part of a note, the rest into a change note
+void split_r1cs_rows(R1csBuilder& b, int depth) {
   constexpr uint32_t SW_ROOT = 1, SW_NH = 2, SW_RECIPIENT = 3, SW_AMOUNT_OUT = 4, SW_TOKEN = 5, SW_CHAIN = 6, SW_CHANGE_LEAF = 7, SW_NULLIFIER = 8,
                      SW_SECRET = 9, SW_AMOUNT = 10, SW_CHANGE_COMMITMENT = 11, SW_CHANGE = 12;
-  OG_REQUIRE(r->n_pub == 7, "og_split_r1cs: the statement has seven public inputs");
   b.alloc(1 + 7 + 5);
   const uint32_t w_sib = b.alloc(depth), w_bit = b.alloc(depth), w_rsq = b.alloc(), w_csq = b.alloc();
   const uint32_t w_obit = b.alloc(128), w_cbit = b.alloc(128);
   b.enforce(R1csBuilder::one(SW_RECIPIENT), R1csBuilder::one(SW_RECIPIENT), R1csBuilder::one(w_rsq));
   b.enforce(R1csBuilder::one(SW_CHAIN), R1csBuilder::one(SW_CHAIN), R1csBuilder::one(w_csq));
   b.enforce(LC{{SW_AMOUNT_OUT, hfr_u64(1)}, {SW_CHANGE, hfr_u64(1)}}, R1csBuilder::one(0), R1csBuilder::one(SW_AMOUNT));  // amount_out + change = amount
-  for (int v = 0; v < 2; v++) {  // amount_out, then change: 128 boolean rows and the recomposition, so that each is < 2^128
-    const uint32_t bits = v ? w_cbit : w_obit;
-    LC sum;
-    for (uint32_t i = 0; i < 128; i++) {
-      b.enforce(R1csBuilder::one(bits + i), LC{{bits + i, hfr_u64(1)}, {0u, m1}}, LC{});
-      HFr p2 = {{0, 0, 0, 0}};
-      p2.v[i >> 6] = 1ull << (i & 63);
-      sum.push_back({bits + i, p2});
-    }
-    b.enforce(sum, R1csBuilder::one(0), R1csBuilder::one(v ? SW_CHANGE : SW_AMOUNT_OUT));
-  }
-  const uint32_t inner = b.hash2(R1csBuilder::one(SW_NULLIFIER), R1csBuilder::one(SW_SECRET));
-  const uint32_t asset = b.hash2(R1csBuilder::one(SW_AMOUNT), R1csBuilder::one(SW_TOKEN));
-  uint32_t cur = b.hash2(R1csBuilder::one(inner), R1csBuilder::one(asset));
-  b.hash2(R1csBuilder::one(SW_NULLIFIER), LC{}, (int)SW_NH);
-  for (int l = 0; l < depth; l++) {
-    const uint32_t bit = w_bit + l, s = w_sib + l;
-    b.enforce(R1csBuilder::one(bit), LC{{bit, hfr_u64(1)}, {0u, m1}}, LC{});              // bit (bit - 1) = 0
-    const uint32_t left = b.alloc();
-    b.enforce(R1csBuilder::one(bit), LC{{s, hfr_u64(1)}, {cur, m1}}, LC{{left, hfr_u64(1)}, {cur, m1}});  // left = cur + bit (s - cur)
-    const LC right{{s, hfr_u64(1)}, {cur, hfr_u64(1)}, {left, m1}};
-    cur = b.hash2(R1csBuilder::one(left), right, l == depth - 1 ? (int)SW_ROOT : -1);
-  }
+  b.range128(SW_AMOUNT_OUT, w_obit);
+  b.range128(SW_CHANGE, w_cbit);
+  b.spend_note(SW_NULLIFIER, SW_SECRET, SW_AMOUNT, SW_TOKEN, SW_NH, w_sib, w_bit, depth, SW_ROOT);
   const uint32_t change_asset = b.hash2(R1csBuilder::one(SW_CHANGE), R1csBuilder::one(SW_TOKEN));
   b.hash2(R1csBuilder::one(SW_CHANGE_COMMITMENT), R1csBuilder::one(change_asset), (int)SW_CHANGE_LEAF);
-  OG_REQUIRE(b.next == r->n_wires && r->n_constraints == shp[1], "og_split_r1cs: internal shape mismatch");
-  return OG_OK;
 }
 
-// the join statement (tests/join_spec.py; witness.hip k_join_core): two notes under one root into one note worth their sum
-int join_shape_query(int depth, uint64_t out[3]);
-int join_r1cs_build(const uint8_t* mimc_consts, int depth, og_r1cs* r) {
-  uint64_t shp[3];
-  OG_TRY(join_shape_query(depth, shp));
-  r->n_wires = shp[0];
-  r->n_pub = shp[2];
-  for (int k = 0; k < 3; k++) r->ptr[k].assign(1, 0u);
-  R1csBuilder b{r, 0, mimc_consts};
-  const HFr m1 = hfr_neg_one();
+// the join statement (tests/join_spec.py; witness.hip k_join_core / k_jw9_*): two notes under one root into one note worth their sum
+void join_r1cs_rows(R1csBuilder& b, int depth) {
   constexpr uint32_t JW_ROOT = 1, JW_NH_A = 2, JW_NH_B = 3, JW_CHAIN = 4, JW_OUT_LEAF = 5, JW_NOTE_A = 6, JW_NOTE_B = 9, JW_TOKEN = 12,
                      JW_OUT_COMMITMENT = 13, JW_SUM = 14, JW_NH_DIFF_INV = 15;  // a note: nullifier, secret, amount
-  OG_REQUIRE(r->n_pub == 5, "og_join_r1cs: the statement has five public inputs");
   b.alloc(1 + 5 + 10);
   const uint32_t w_sib = b.alloc(2 * depth), w_bit = b.alloc(2 * depth), w_csq = b.alloc();
   const uint32_t w_bits = b.alloc(3 * 128);
   b.enforce(R1csBuilder::one(JW_CHAIN), R1csBuilder::one(JW_CHAIN), R1csBuilder::one(w_csq));
   b.enforce(LC{{JW_NOTE_A + 2, hfr_u64(1)}, {JW_NOTE_B + 2, hfr_u64(1)}}, R1csBuilder::one(0), R1csBuilder::one(JW_SUM));  // amount_a + amount_b = sum
-  b.enforce(LC{{JW_NH_A, hfr_u64(1)}, {JW_NH_B, m1}}, R1csBuilder::one(JW_NH_DIFF_INV), R1csBuilder::one(0));  // two different notes
-  for (int v = 0; v < 3; v++) {  // amount_a, amount_b, sum: 128 boolean rows and the recomposition, so that each is < 2^128
-    const uint32_t bits = w_bits + 128 * v;
-    LC sum;
-    for (uint32_t i = 0; i < 128; i++) {
-      b.enforce(R1csBuilder::one(bits + i), LC{{bits + i, hfr_u64(1)}, {0u, m1}}, LC{});
-      HFr p2 = {{0, 0, 0, 0}};
-      p2.v[i >> 6] = 1ull << (i & 63);
-      sum.push_back({bits + i, p2});
-    }
-    b.enforce(sum, R1csBuilder::one(0), R1csBuilder::one(v == 0 ? JW_NOTE_A + 2 : v == 1 ? JW_NOTE_B + 2 : JW_SUM));
-  }
-  for (int x = 0; x < 2; x++) {  // the walk of note a, then of note b: both end in wire 1
+  b.enforce(LC{{JW_NH_A, hfr_u64(1)}, {JW_NH_B, hfr_neg_one()}}, R1csBuilder::one(JW_NH_DIFF_INV), R1csBuilder::one(0));  // two different notes
+  b.range128(JW_NOTE_A + 2, w_bits);
+  b.range128(JW_NOTE_B + 2, w_bits + 128);
+  b.range128(JW_SUM, w_bits + 256);
+  for (int x = 0; x < 2; x++) {  // note a, then note b: both walks end in wire 1
     const uint32_t nt = x ? JW_NOTE_B : JW_NOTE_A;
-    const uint32_t inner = b.hash2(R1csBuilder::one(nt), R1csBuilder::one(nt + 1));
-    const uint32_t asset = b.hash2(R1csBuilder::one(nt + 2), R1csBuilder::one(JW_TOKEN));
-    uint32_t cur = b.hash2(R1csBuilder::one(inner), R1csBuilder::one(asset));
-    b.hash2(R1csBuilder::one(nt), LC{}, (int)(x ? JW_NH_B : JW_NH_A));
-    for (int l = 0; l < depth; l++) {
-      const uint32_t bit = w_bit + x * depth + l, s = w_sib + x * depth + l;
-      b.enforce(R1csBuilder::one(bit), LC{{bit, hfr_u64(1)}, {0u, m1}}, LC{});              // bit (bit - 1) = 0
-      const uint32_t left = b.alloc();
-      b.enforce(R1csBuilder::one(bit), LC{{s, hfr_u64(1)}, {cur, m1}}, LC{{left, hfr_u64(1)}, {cur, m1}});  // left = cur + bit (s - cur)
-      const LC right{{s, hfr_u64(1)}, {cur, hfr_u64(1)}, {left, m1}};
-      cur = b.hash2(R1csBuilder::one(left), right, l == depth - 1 ? (int)JW_ROOT : -1);
-    }
+    b.spend_note(nt, nt + 1, nt + 2, JW_TOKEN, x ? JW_NH_B : JW_NH_A, w_sib + x * depth, w_bit + x * depth, depth, JW_ROOT);
   }
   const uint32_t out_asset = b.hash2(R1csBuilder::one(JW_SUM), R1csBuilder::one(JW_TOKEN));
   b.hash2(R1csBuilder::one(JW_OUT_COMMITMENT), R1csBuilder::one(out_asset), (int)JW_OUT_LEAF);
-  OG_REQUIRE(b.next == r->n_wires && r->n_constraints == shp[1], "og_join_r1cs: internal shape mismatch");
-  return OG_OK;
 }
 
 // the transfer statement (tests/transfer_spec.py; witness.hip k_transfer_core / k_tw9_*): part of a note into a leaf for the payee,
 // the rest into a change leaf, nothing out of the pool
-int transfer_shape_query(int depth, uint64_t out[3]);
-int transfer_r1cs_build(const uint8_t* mimc_consts, int depth, og_r1cs* r) {
-  uint64_t shp[3];
-  OG_TRY(transfer_shape_query(depth, shp));
-  r->n_wires = shp[0];
-  r->n_pub = shp[2];
-  for (int k = 0; k < 3; k++) r->ptr[k].assign(1, 0u);
-  R1csBuilder b{r, 0, mimc_consts};
-  const HFr m1 = hfr_neg_one();
+void transfer_r1cs_rows(R1csBuilder& b, int depth) {
   constexpr uint32_t TW_ROOT = 1, TW_NH = 2, TW_CHAIN = 3, TW_PAY_LEAF = 4, TW_CHANGE_LEAF = 5, TW_NULLIFIER = 6, TW_SECRET = 7, TW_AMOUNT = 8,
                      TW_TOKEN = 9, TW_PAY_COMMITMENT = 10, TW_PAY_AMOUNT = 11, TW_CHANGE_COMMITMENT = 12, TW_CHANGE = 13;
-  OG_REQUIRE(r->n_pub == 5, "og_transfer_r1cs: the statement has five public inputs");
   b.alloc(1 + 5 + 8);
   const uint32_t w_sib = b.alloc(depth), w_bit = b.alloc(depth), w_csq = b.alloc();
   const uint32_t w_pbit = b.alloc(128), w_cbit = b.alloc(128);
   b.enforce(R1csBuilder::one(TW_CHAIN), R1csBuilder::one(TW_CHAIN), R1csBuilder::one(w_csq));
   b.enforce(LC{{TW_PAY_AMOUNT, hfr_u64(1)}, {TW_CHANGE, hfr_u64(1)}}, R1csBuilder::one(0), R1csBuilder::one(TW_AMOUNT));  // pay_amount + change = amount
-  for (int v = 0; v < 2; v++) {  // pay_amount, then change: 128 boolean rows and the recomposition, so that each is < 2^128
-    const uint32_t bits = v ? w_cbit : w_pbit;
-    LC sum;
-    for (uint32_t i = 0; i < 128; i++) {
-      b.enforce(R1csBuilder::one(bits + i), LC{{bits + i, hfr_u64(1)}, {0u, m1}}, LC{});
-      HFr p2 = {{0, 0, 0, 0}};
-      p2.v[i >> 6] = 1ull << (i & 63);
-      sum.push_back({bits + i, p2});
-    }
-    b.enforce(sum, R1csBuilder::one(0), R1csBuilder::one(v ? TW_CHANGE : TW_PAY_AMOUNT));
-  }
-  const uint32_t inner = b.hash2(R1csBuilder::one(TW_NULLIFIER), R1csBuilder::one(TW_SECRET));
-  const uint32_t asset = b.hash2(R1csBuilder::one(TW_AMOUNT), R1csBuilder::one(TW_TOKEN));
-  uint32_t cur = b.hash2(R1csBuilder::one(inner), R1csBuilder::one(asset));
-  b.hash2(R1csBuilder::one(TW_NULLIFIER), LC{}, (int)TW_NH);
-  for (int l = 0; l < depth; l++) {
-    const uint32_t bit = w_bit + l, s = w_sib + l;
-    b.enforce(R1csBuilder::one(bit), LC{{bit, hfr_u64(1)}, {0u, m1}}, LC{});              // bit (bit - 1) = 0
-    const uint32_t left = b.alloc();
-    b.enforce(R1csBuilder::one(bit), LC{{s, hfr_u64(1)}, {cur, m1}}, LC{{left, hfr_u64(1)}, {cur, m1}});  // left = cur + bit (s - cur)
-    const LC right{{s, hfr_u64(1)}, {cur, hfr_u64(1)}, {left, m1}};
-    cur = b.hash2(R1csBuilder::one(left), right, l == depth - 1 ? (int)TW_ROOT : -1);
-  }
+  b.range128(TW_PAY_AMOUNT, w_pbit);
+  b.range128(TW_CHANGE, w_cbit);
+  b.spend_note(TW_NULLIFIER, TW_SECRET, TW_AMOUNT, TW_TOKEN, TW_NH, w_sib, w_bit, depth, TW_ROOT);
   const uint32_t pay_asset = b.hash2(R1csBuilder::one(TW_PAY_AMOUNT), R1csBuilder::one(TW_TOKEN));
   b.hash2(R1csBuilder::one(TW_PAY_COMMITMENT), R1csBuilder::one(pay_asset), (int)TW_PAY_LEAF);
   const uint32_t change_asset = b.hash2(R1csBuilder::one(TW_CHANGE), R1csBuilder::one(TW_TOKEN));
   b.hash2(R1csBuilder::one(TW_CHANGE_COMMITMENT), R1csBuilder::one(change_asset), (int)TW_CHANGE_LEAF);
-  OG_REQUIRE(b.next == r->n_wires && r->n_constraints == shp[1], "og_transfer_r1cs: internal shape mismatch");
+}
+
+int records_r1cs_build(const RecordStatement& st, const uint8_t* mimc_consts, int depth, og_r1cs* r) {
+  const std::string who = "og_" + std::string(st.name) + "_r1cs";
+  uint64_t shp[3];
+  OG_TRY(records_shape_query(st, depth, shp));
+  OG_TRY(r1cs_begin(r, shp, (uint64_t)st.n_pub, who));
+  R1csBuilder b{r, 0, mimc_consts};
+  st.r1cs_rows(b, depth);
+  OG_REQUIRE(b.next == r->n_wires && r->n_constraints == shp[1], who + ": internal shape mismatch");
   return OG_OK;
 }
 
@@ -548,6 +498,22 @@ int keygen_setup(og_ctx* ctx, const og_r1cs* r, const uint8_t toxic[160], std::v
 
 using namespace og;
 
+// the body behind og_<statement>_r1cs of the record statements (statements.h)
+static int record_r1cs(const RecordStatement& st, og_ctx* ctx, int depth, og_r1cs** out) {
+  return guarded([&]() -> int {
+    OG_REQUIRE(ctx != nullptr && out != nullptr, "og_" + std::string(st.name) + "_r1cs: null argument");
+    *out = nullptr;
+    og_r1cs* r = new og_r1cs();
+    int rc = records_r1cs_build(st, ctx->mimc_consts_canon, depth, r);
+    if (rc != OG_OK) {
+      delete r;
+      return rc;
+    }
+    *out = r;
+    return OG_OK;
+  });
+}
+
 extern "C" {
 
 int og_withdraw_r1cs(og_ctx* ctx, int depth, uint64_t n_pad3, uint64_t n_pad2, int dense, og_r1cs** out) {
@@ -580,50 +546,9 @@ int og_deposit_r1cs(og_ctx* ctx, og_r1cs** out) {
   });
 }
 
-int og_split_r1cs(og_ctx* ctx, int depth, og_r1cs** out) {
-  return guarded([&]() -> int {
-    OG_REQUIRE(ctx != nullptr && out != nullptr, "og_split_r1cs: null argument");
-    *out = nullptr;
-    og_r1cs* r = new og_r1cs();
-    int rc = split_r1cs_build(ctx->mimc_consts_canon, depth, r);
-    if (rc != OG_OK) {
-      delete r;
-      return rc;
-    }
-    *out = r;
-    return OG_OK;
-  });
-}
-
-int og_join_r1cs(og_ctx* ctx, int depth, og_r1cs** out) {
-  return guarded([&]() -> int {
-    OG_REQUIRE(ctx != nullptr && out != nullptr, "og_join_r1cs: null argument");
-    *out = nullptr;
-    og_r1cs* r = new og_r1cs();
-    int rc = join_r1cs_build(ctx->mimc_consts_canon, depth, r);
-    if (rc != OG_OK) {
-      delete r;
-      return rc;
-    }
-    *out = r;
-    return OG_OK;
-  });
-}
-
-int og_transfer_r1cs(og_ctx* ctx, int depth, og_r1cs** out) {
-  return guarded([&]() -> int {
-    OG_REQUIRE(ctx != nullptr && out != nullptr, "og_transfer_r1cs: null argument");
-    *out = nullptr;
-    og_r1cs* r = new og_r1cs();
-    int rc = transfer_r1cs_build(ctx->mimc_consts_canon, depth, r);
-    if (rc != OG_OK) {
-      delete r;
-      return rc;
-    }
-    *out = r;
-    return OG_OK;
-  });
-}
+int og_split_r1cs(og_ctx* ctx, int depth, og_r1cs** out) { return record_r1cs(ST_SPLIT, ctx, depth, out); }
+int og_join_r1cs(og_ctx* ctx, int depth, og_r1cs** out) { return record_r1cs(ST_JOIN, ctx, depth, out); }
+int og_transfer_r1cs(og_ctx* ctx, int depth, og_r1cs** out) { return record_r1cs(ST_TRANSFER, ctx, depth, out); }
 
 int og_r1cs_from_csr(uint64_t n_wires, uint64_t n_pub, uint64_t n_constraints, const uint32_t* const ptr[3], const uint32_t* const col[3],
                      const uint8_t* const val[3], og_r1cs** out) {

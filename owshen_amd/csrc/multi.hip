@@ -14,6 +14,7 @@
 //
 // Host threads only issue work and wait; they never touch results that another device produced except through RCCL.
 #include "ctx.h"
+#include "statements.h"
 #include "msm.hip.h"
 #include <algorithm>
 #include <condition_variable>
@@ -72,8 +73,6 @@ namespace og {
 int pk_load(og_ctx*, const uint8_t*, size_t, og_pk**);
 void pk_destroy(og_pk*);
 int prove_batch_host(og_ctx*, const og_pk*, const uint8_t*, size_t, const uint8_t*, uint8_t*);
-int withdraw_prove_batch(og_ctx*, const og_pk*, int, uint64_t, uint64_t, const uint8_t*, size_t, const uint8_t*, uint8_t*, uint8_t*);
-int withdraw_prove_partials_enqueue(og_ctx*, const og_pk*, int, uint64_t, uint64_t, const uint8_t*, size_t, int, int, uint8_t*, uint8_t*, og_job**);
 int prove_partials_enqueue(og_ctx*, const og_pk*, const uint8_t*, size_t, int, int, uint8_t*, og_job**);
 int prove_from_partials(og_ctx*, const og_pk*, const uint8_t*, int, size_t, const uint8_t*, uint8_t*);
 int job_join_stream(og_job*, hipStream_t);

@@ -19,6 +19,7 @@
 // (token and chain_id: the rest of what the reference's gate signs, /root/reference/contracts/src/Owshen.sol:69)
 // Output: n_wires x 32 B canonical per proof, wire order as documented in oracle/py/withdraw.py.
 #include "ctx.h"
+#include "statements.h"
 #include "mimc7.hip.h"
 #include "host_fr4.h"
 #include "field_w9.hip.h"
@@ -594,6 +595,21 @@ __global__ void __launch_bounds__(256) k_withdraw_pad(const uint8_t* __restrict_
 // the statement itself takes any field element.  bad[g] = lowest offending field of record g (atomicMin;
 // the caller initialises it to 0xffffffff): 0 nullifier, 1 secret, 2 amount, 3 recipient, 4 pad_seed, 5 index, 6 token,
 // 7 chain_id, 8 + l sibling l.
+// The predicates the four k_check_*_records kernels share, on the eight 32-bit words of a field -- compared as integers, not in the field:
+// an amount below 2^128; an index inside the tree (u64 in the low bytes, < 2^depth, upper bytes zero); w <= a, most significant word first
+__device__ __forceinline__ bool rec_amount_ok(const uint32_t* w) { return (w[4] | w[5] | w[6] | w[7]) == 0; }
+__device__ __forceinline__ bool rec_index_ok(const uint32_t* w, int depth) {
+  const uint64_t idx = (uint64_t)w[0] | ((uint64_t)w[1] << 32);
+  return (w[2] | w[3] | w[4] | w[5] | w[6] | w[7]) == 0 && (depth >= 64 || (idx >> depth) == 0);
+}
+__device__ __forceinline__ bool rec_le(const uint32_t* w, const uint32_t* a) {
+  bool gt = false, decided = false;
+  for (int i = 7; i >= 0; i--) {
+    if (!decided && w[i] != a[i]) { gt = w[i] > a[i]; decided = true; }
+  }
+  return !gt;
+}
+
 __global__ void __launch_bounds__(64) k_check_records(const uint8_t* __restrict__ inputs, int depth, size_t n, uint32_t* __restrict__ bad) {
   OG_FILLER_PRIO();
   const size_t g = blockIdx.y;
@@ -602,11 +618,7 @@ __global__ void __launch_bounds__(64) k_check_records(const uint8_t* __restrict_
   const uint8_t* p = inputs + (g * (size_t)(W_REC + depth) + f) * 32;
   bool ok = fe_lt_modulus(fe_load<FrParams>(p));
   const uint32_t* w = reinterpret_cast<const uint32_t*>(p);
-  if (f == 5) {  // index
-    ok = ok && (w[2] | w[3] | w[4] | w[5] | w[6] | w[7]) == 0;
-    const uint64_t idx = (uint64_t)w[0] | ((uint64_t)w[1] << 32);
-    ok = ok && (depth >= 64 || (idx >> depth) == 0);
-  }
+  if (f == 5) ok = ok && rec_index_ok(w, depth);
   if (!ok) atomicMin(&bad[g], f);
 }
 
@@ -729,7 +741,10 @@ static int withdraw_walk_on_host(og_ctx* ctx, int depth, const WithdrawShape& s,
   return OG_OK;
 }
 
-int arena_get(og_ctx* ctx, const char* name, size_t bytes, void** out);
+bool witness_walks_wave_wide(const og_ctx* ctx, size_t n) {
+  return OG_HOOK_SET("OG_WITNESS_W9") ? OG_HOOK_INT("OG_WITNESS_W9", 1) != 0
+                                      : std::max(n, ctx->call_requests) <= (size_t)OG_HOOK_INT("OG_WITNESS_W9_MAX", 512);
+}
 
 int withdraw_witness(og_ctx* ctx, int depth, uint64_t n_pad3, uint64_t n_pad2, const uint8_t* inputs_d, size_t n, uint8_t* out_d) {
   OG_REQUIRE(depth >= 1 && depth <= 64, "withdraw: depth must be 1..64");
@@ -745,13 +760,12 @@ int withdraw_witness(og_ctx* ctx, int depth, uint64_t n_pad3, uint64_t n_pad2, c
   const size_t lat_max = (size_t)OG_HOOK_INT("OG_WITNESS_LAT_MAX", 16);  // (64 requests: the two-lane form is level or better)
   const bool lat = OG_HOOK_SET("OG_WITNESS_LAT") ? OG_HOOK_INT("OG_WITNESS_LAT", 0) != 0 : (pair && n <= lat_max);
   const bool on_host = ctx->host_chains_max > 0 && std::max(n, ctx->call_requests) <= (size_t)ctx->host_chains_max;  // (a sub-batch of a larger call stays on the GPU)
-  // the wave-wide form (k_w9_*): one permutation per wave in three launches; OG_WITNESS_W9=0 | 1 forces either way, OG_WITNESS_W9_MAX moves the bound
+  // the wave-wide form (k_w9_*): one permutation per wave in three launches (witness_walks_wave_wide: the rule every statement shares)
   // -- for calls of at most 512 requests: there the walk is on the call's critical path (measured, same box, natural statement:
   // witness 7.4 -> 5.7 ms for one request, 9.3 -> 5.8 for 8, 9.3 -> 6.4 for 64, 9.4 -> 6.9 for 512; the call 10.9 -> 8.7, 14.7 -> 11.1,
   // 26.5 -> 23.3, 115 -> 113 ms: profiles/r06k_ab_witness_w9.txt); a wave per PERMUTATION is ~19 x the wave-instructions of the
   // lane-pair form (nine useful lanes of 64), which a throughput batch would pay out of its accumulations
-  const bool w9 = !on_host && (OG_HOOK_SET("OG_WITNESS_W9") ? OG_HOOK_INT("OG_WITNESS_W9", 1) != 0
-                                                            : std::max(n, ctx->call_requests) <= (size_t)OG_HOOK_INT("OG_WITNESS_W9_MAX", 512));
+  const bool w9 = !on_host && witness_walks_wave_wide(ctx, n);
   if (w9) {
     uint32_t *wl = nullptr, *xch = nullptr;
     OG_TRY(arena_get(ctx, "wit.w9.limbs", n * (size_t)s.pad_base * 36, (void**)&wl));
@@ -943,15 +957,15 @@ __device__ __forceinline__ Fr gadget_wires(const uint32_t* __restrict__ consts, 
 constexpr int S_PUB = 7;
 constexpr int S_REC = 9;  // fields of a split record before the siblings
 constexpr int S_BITS = 128;
+// byte offsets of the record's fields
+constexpr int S_NULLIFIER = 0, S_SECRET = 32, S_AMOUNT = 64, S_RECIPIENT = 96, S_AMOUNT_OUT = 128, S_INDEX = 160, S_TOKEN = 192, S_CHAIN = 224,
+              S_CHANGE_COMMITMENT = 256;
 
-struct SplitShape {
-  uint64_t n_wires, n_constraints, first_bit_wire;
-};
-
-static SplitShape split_shape(int depth) {
-  SplitShape s;
+static RecordShape split_shape(int depth) {
+  RecordShape s{};
   const uint64_t hashes = 6 + (uint64_t)depth;
   s.first_bit_wire = 1 + S_PUB + 5 + 2 * (uint64_t)depth + 2;
+  s.first_gadget_wire = s.first_bit_wire + 2 * S_BITS;
   s.n_wires = s.first_bit_wire + 2 * S_BITS + depth + hashes * 730 - 3;  // (the gadgets follow the bit wires)
   s.n_constraints = 3 + 2 * (S_BITS + 1) + 2 * (uint64_t)depth + hashes * 730;
   return s;
@@ -968,18 +982,18 @@ __global__ void __launch_bounds__(64) k_split_core(const uint32_t* __restrict__ 
   if (g >= n) return;
   const uint8_t* in = inputs + g * (size_t)(S_REC + depth) * 32;
   WireWriterT<false> ww{out + g * n_wires * 32, first_bit_wire};
-  const Fr nullifier = fe_to_mont(fe_load<FrParams>(in));
-  const Fr secret = fe_to_mont(fe_load<FrParams>(in + 32));
-  const Fr amount = fe_to_mont(fe_load<FrParams>(in + 64));
-  const Fr recipient = fe_to_mont(fe_load<FrParams>(in + 96));
-  const Fr amount_out = fe_to_mont(fe_load<FrParams>(in + 128));
-  const uint64_t index = *reinterpret_cast<const uint64_t*>(in + 160);
-  const Fr token = fe_to_mont(fe_load<FrParams>(in + 192));
-  const Fr chain_id = fe_to_mont(fe_load<FrParams>(in + 224));
-  const Fr change_commitment = fe_to_mont(fe_load<FrParams>(in + 256));
+  const Fr nullifier = fe_to_mont(fe_load<FrParams>(in + S_NULLIFIER));
+  const Fr secret = fe_to_mont(fe_load<FrParams>(in + S_SECRET));
+  const Fr amount = fe_to_mont(fe_load<FrParams>(in + S_AMOUNT));
+  const Fr recipient = fe_to_mont(fe_load<FrParams>(in + S_RECIPIENT));
+  const Fr amount_out = fe_to_mont(fe_load<FrParams>(in + S_AMOUNT_OUT));
+  const uint64_t index = *reinterpret_cast<const uint64_t*>(in + S_INDEX);
+  const Fr token = fe_to_mont(fe_load<FrParams>(in + S_TOKEN));
+  const Fr chain_id = fe_to_mont(fe_load<FrParams>(in + S_CHAIN));
+  const Fr change_commitment = fe_to_mont(fe_load<FrParams>(in + S_CHANGE_COMMITMENT));
   // change = amount - amount_out on the integer words
-  const uint64_t a_lo = *reinterpret_cast<const uint64_t*>(in + 64), a_hi = *reinterpret_cast<const uint64_t*>(in + 72);
-  const uint64_t o_lo = *reinterpret_cast<const uint64_t*>(in + 128), o_hi = *reinterpret_cast<const uint64_t*>(in + 136);
+  const uint64_t a_lo = *reinterpret_cast<const uint64_t*>(in + S_AMOUNT), a_hi = *reinterpret_cast<const uint64_t*>(in + S_AMOUNT + 8);
+  const uint64_t o_lo = *reinterpret_cast<const uint64_t*>(in + S_AMOUNT_OUT), o_hi = *reinterpret_cast<const uint64_t*>(in + S_AMOUNT_OUT + 8);
   const uint64_t c_lo = a_lo - o_lo, c_hi = a_hi - o_hi - (a_lo < o_lo ? 1u : 0u);
   const uint32_t cw[8] = {(uint32_t)c_lo, (uint32_t)(c_lo >> 32), (uint32_t)c_hi, (uint32_t)(c_hi >> 32), 0u, 0u, 0u, 0u};
   const Fr change = fe_to_mont(fe_from_words<FrParams>(cw));
@@ -1054,77 +1068,19 @@ __global__ void __launch_bounds__(64) k_check_split_records(const uint8_t* __res
   const uint8_t* p = rec + (size_t)f * 32;
   bool ok = fe_lt_modulus(fe_load<FrParams>(p));
   const uint32_t* w = reinterpret_cast<const uint32_t*>(p);
-  if (f == 2 || f == 4) ok = ok && (w[4] | w[5] | w[6] | w[7]) == 0;
-  if (f == 4) {  // amount_out <= amount, most significant word first
-    const uint32_t* a = reinterpret_cast<const uint32_t*>(rec + 64);
-    bool gt = false, decided = false;
-    for (int i = 7; i >= 0; i--) {
-      if (!decided && w[i] != a[i]) { gt = w[i] > a[i]; decided = true; }
-    }
-    ok = ok && !gt;
-  }
-  if (f == 5) {  // index
-    ok = ok && (w[2] | w[3] | w[4] | w[5] | w[6] | w[7]) == 0;
-    const uint64_t idx = (uint64_t)w[0] | ((uint64_t)w[1] << 32);
-    ok = ok && (depth >= 64 || (idx >> depth) == 0);
-  }
+  if (f == 2 || f == 4) ok = ok && rec_amount_ok(w);
+  if (f == 4) ok = ok && rec_le(w, reinterpret_cast<const uint32_t*>(rec + S_AMOUNT));  // amount_out <= amount
+  if (f == 5) ok = ok && rec_index_ok(w, depth);
   if (!ok) atomicMin(&bad[g], f);
 }
 
-int split_shape_query(int depth, uint64_t out[3]) {
-  OG_REQUIRE(depth >= 1 && depth <= 64, "split: depth must be 1..64");
-  const SplitShape s = split_shape(depth);
-  out[0] = s.n_wires; out[1] = s.n_constraints; out[2] = S_PUB;
-  return OG_OK;
-}
-
-// OG_ERR_INVALID names the first malformed record and its lowest offending field (`base` = index of record 0 in the caller's
-// batch); blocking
-int split_records_ok(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, size_t base) {
-  OG_REQUIRE(depth >= 1 && depth <= 64, "split: depth must be 1..64");
-  OG_REQUIRE(n <= 65535, "split: at most 65535 records per call");  // (the record index is grid.y)
-  if (n == 0) return OG_OK;
-  uint32_t* bad_d = nullptr;
-  OG_TRY(arena_get(ctx, "sp.bad", n * 4, (void**)&bad_d));
-  OG_HIP(hipMemsetAsync(bad_d, 0xff, n * 4, ctx->stream));
+static void split_launch_check(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, uint32_t* bad_d) {
   hipLaunchKernelGGL(k_check_split_records, dim3(grid_for(S_REC + depth, 64), (unsigned)n), dim3(64), 0, ctx->stream, inputs_d, depth, n, bad_d);
-  OG_HIP(hipGetLastError());
-  std::vector<uint32_t> b(n);
-  OG_HIP(hipMemcpyAsync(b.data(), bad_d, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-  OG_HIP(hipStreamSynchronize(ctx->stream));
-  static const char* names[S_REC] = {"nullifier", "secret", "amount", "recipient", "amount_out", "index", "token", "chain_id", "change_commitment"};
-  for (size_t g = 0; g < n; g++)
-    if (b[g] != 0xffffffffu) {
-      const std::string name = b[g] < (uint32_t)S_REC ? std::string(names[b[g]]) : "sibling " + std::to_string(b[g] - S_REC);
-      set_error("og_split: input record " + std::to_string(base + g) + ": field " + std::to_string(b[g]) + " (" + name +
-                ") is not a valid value (>= r, an index outside the tree, an amount >= 2^128, or amount_out > amount)");
-      return OG_ERR_INVALID;
-    }
-  return OG_OK;
 }
 
-static int split_walk_w9(og_ctx* ctx, int depth, const SplitShape& s, const uint8_t* inputs_d, size_t n, uint8_t* out_d);  // k_sw9_*: at the end of the file
-
-// records (checked: split_records_ok) -> n x n_wires x 32 B canonical.  The wave-wide walk (k_sw9_*, beside transfer's k_tw9_* at the end
-// of the file) for calls of at most 512 requests -- the rule and the hooks of transfer_witness, verbatim (OG_WITNESS_W9 = 0 | 1 forces
-// either way, OG_WITNESS_W9_MAX moves the bound, OG_W9_ROWS picks the round's form; hooks builds only) --, the lane-local kernel for
-// batches.  The wave-wide walk's limb buffer is n x n_wires x 36 B from the arena: 0.52 GB at 512 depth-32 requests
-int split_witness(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, uint8_t* out_d) {
-  OG_REQUIRE(depth >= 1 && depth <= 64, "split: depth must be 1..64");
-  OG_REQUIRE(n <= 65535, "split: at most 65535 witnesses per call");
-  if (n == 0) return OG_OK;
-  const SplitShape s = split_shape(depth);
-  ProfScope ps(ctx, PROF_WITNESS, (double)n);
-  const bool w9 = OG_HOOK_SET("OG_WITNESS_W9") ? OG_HOOK_INT("OG_WITNESS_W9", 1) != 0
-                                               : std::max(n, ctx->call_requests) <= (size_t)OG_HOOK_INT("OG_WITNESS_W9_MAX", 512);
-  if (w9) return split_walk_w9(ctx, depth, s, inputs_d, n, out_d);
+static void split_launch_core(og_ctx* ctx, int depth, const RecordShape& s, const uint8_t* inputs_d, size_t n, uint8_t* out_d) {
   hipLaunchKernelGGL(k_split_core, dim3(grid_for(n, 64)), dim3(64), 0, ctx->stream, (const uint32_t*)ctx->mimc_consts_d, inputs_d, depth,
                      (size_t)s.n_wires, (uint32_t)s.first_bit_wire, n, out_d);
-  OG_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_wires_from_mont, dim3(grid_for(s.n_wires, 256), (unsigned)n), dim3(256), 0, ctx->stream, out_d, (size_t)s.n_wires,
-                     (uint32_t)s.n_wires, 1u);
-  OG_HIP(hipGetLastError());
-  return OG_OK;
 }
 
 // ---- the join statement: merge two notes into one -----------------------------------------------------------------------------------
@@ -1152,14 +1108,11 @@ constexpr int J_PUB = 5;
 constexpr int J_REC = 11;  // fields of a join record before the siblings
 constexpr int J_BITS = 128;
 
-struct JoinShape {
-  uint64_t n_wires, n_constraints, first_bit_wire, note_gadget_wires;
-};
-
-static JoinShape join_shape(int depth) {
-  JoinShape s;
+static RecordShape join_shape(int depth) {
+  RecordShape s{};
   const uint64_t hashes = 10 + 2 * (uint64_t)depth;
   s.first_bit_wire = 1 + J_PUB + 10 + 4 * (uint64_t)depth + 1;
+  s.first_gadget_wire = s.first_bit_wire + 3 * J_BITS;
   s.note_gadget_wires = (4 + (uint64_t)depth) * 730 + depth - 2;  // a `left` per level; nullifier_hash and root are public wires
   s.n_wires = s.first_bit_wire + 3 * J_BITS + 2 * s.note_gadget_wires + 2 * 730 - 1;
   s.n_constraints = 3 + 3 * (J_BITS + 1) + 4 * (uint64_t)depth + hashes * 730;
@@ -1305,7 +1258,7 @@ __global__ void __launch_bounds__(64) k_check_join_records(const uint8_t* __rest
   const uint8_t* p = rec + (size_t)f * 32;
   bool ok = fe_lt_modulus(fe_load<FrParams>(p));
   const uint32_t* w = reinterpret_cast<const uint32_t*>(p);
-  if (f == 2 || f == 6) ok = ok && (w[4] | w[5] | w[6] | w[7]) == 0;
+  if (f == 2 || f == 6) ok = ok && rec_amount_ok(w);
   if (f == 6) {  // amount_a + amount_b < 2^128 as integers: no carry into word 4 or out of word 7
     const uint32_t* a = reinterpret_cast<const uint32_t*>(rec + 64);
     uint64_t carry = 0;
@@ -1323,72 +1276,17 @@ __global__ void __launch_bounds__(64) k_check_join_records(const uint8_t* __rest
     for (int i = 0; i < 8; i++) diff |= a[i] ^ w[i];
     ok = ok && diff != 0;
   }
-  if (f == 3 || f == 7) {  // an index
-    ok = ok && (w[2] | w[3] | w[4] | w[5] | w[6] | w[7]) == 0;
-    const uint64_t idx = (uint64_t)w[0] | ((uint64_t)w[1] << 32);
-    ok = ok && (depth >= 64 || (idx >> depth) == 0);
-  }
+  if (f == 3 || f == 7) ok = ok && rec_index_ok(w, depth);
   if (!ok) atomicMin(&bad[g], f);
 }
 
-int join_shape_query(int depth, uint64_t out[3]) {
-  OG_REQUIRE(depth >= 1 && depth <= 64, "join: depth must be 1..64");
-  const JoinShape s = join_shape(depth);
-  out[0] = s.n_wires; out[1] = s.n_constraints; out[2] = J_PUB;
-  return OG_OK;
-}
-
-// OG_ERR_INVALID names the first malformed record and its lowest offending field (`base` = index of record 0 in the caller's
-// batch); blocking
-int join_records_ok(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, size_t base) {
-  OG_REQUIRE(depth >= 1 && depth <= 64, "join: depth must be 1..64");
-  OG_REQUIRE(n <= 65535, "join: at most 65535 records per call");  // (the record index is grid.y)
-  if (n == 0) return OG_OK;
-  uint32_t* bad_d = nullptr;
-  OG_TRY(arena_get(ctx, "jn.bad", n * 4, (void**)&bad_d));
-  OG_HIP(hipMemsetAsync(bad_d, 0xff, n * 4, ctx->stream));
+static void join_launch_check(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, uint32_t* bad_d) {
   hipLaunchKernelGGL(k_check_join_records, dim3(grid_for(J_REC + 2 * depth, 64), (unsigned)n), dim3(64), 0, ctx->stream, inputs_d, depth, n, bad_d);
-  OG_HIP(hipGetLastError());
-  std::vector<uint32_t> bad(n);
-  OG_HIP(hipMemcpyAsync(bad.data(), bad_d, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-  OG_HIP(hipStreamSynchronize(ctx->stream));
-  static const char* names[J_REC] = {"nullifier_a", "secret_a", "amount_a", "index_a", "nullifier_b", "secret_b", "amount_b", "index_b",
-                                     "token", "chain_id", "out_commitment"};
-  for (size_t g = 0; g < n; g++)
-    if (bad[g] != 0xffffffffu) {
-      const uint32_t f = bad[g];
-      const std::string name = f < (uint32_t)J_REC ? std::string(names[f])
-                               : f < (uint32_t)(J_REC + depth) ? "sibling a " + std::to_string(f - J_REC)
-                                                               : "sibling b " + std::to_string(f - J_REC - depth);
-      set_error("og_join: input record " + std::to_string(base + g) + ": field " + std::to_string(f) + " (" + name +
-                ") is not a valid value (>= r, an index outside the tree, an amount >= 2^128, amount_a + amount_b >= 2^128, or "
-                "nullifier_b = nullifier_a)");
-      return OG_ERR_INVALID;
-    }
-  return OG_OK;
 }
 
-static int join_walk_w9(og_ctx* ctx, int depth, const JoinShape& s, const uint8_t* inputs_d, size_t n, uint8_t* out_d);  // k_jw9_*: at the end of the file
-
-// records (checked: join_records_ok) -> n x n_wires x 32 B canonical.  The wave-wide walk (k_jw9_*, at the end of the file) for calls of
-// at most 512 requests -- the rule and the hooks of transfer_witness, verbatim --, two lanes per request (k_join_core) for batches.  The
-// wave-wide walk's limb buffer is n x n_wires x 36 B from the arena: 1.0 GB at 512 depth-32 requests
-int join_witness(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, uint8_t* out_d) {
-  OG_REQUIRE(depth >= 1 && depth <= 64, "join: depth must be 1..64");
-  OG_REQUIRE(n <= 65535, "join: at most 65535 witnesses per call");
-  if (n == 0) return OG_OK;
-  const JoinShape s = join_shape(depth);
-  ProfScope ps(ctx, PROF_WITNESS, (double)n);
-  const bool w9 = OG_HOOK_SET("OG_WITNESS_W9") ? OG_HOOK_INT("OG_WITNESS_W9", 1) != 0
-                                               : std::max(n, ctx->call_requests) <= (size_t)OG_HOOK_INT("OG_WITNESS_W9_MAX", 512);
-  if (w9) return join_walk_w9(ctx, depth, s, inputs_d, n, out_d);
+static void join_launch_core(og_ctx* ctx, int depth, const RecordShape& s, const uint8_t* inputs_d, size_t n, uint8_t* out_d) {
   hipLaunchKernelGGL(k_join_core, dim3(grid_for(2 * n, 64)), dim3(64), 0, ctx->stream, (const uint32_t*)ctx->mimc_consts_d, inputs_d, depth,
                      (size_t)s.n_wires, (uint32_t)s.first_bit_wire, (uint32_t)s.note_gadget_wires, n, out_d);
-  OG_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_wires_from_mont, dim3(grid_for(s.n_wires, 256), (unsigned)n), dim3(256), 0, ctx->stream, out_d, (size_t)s.n_wires,
-                     (uint32_t)s.n_wires, 1u);
-  OG_HIP(hipGetLastError());
-  return OG_OK;
 }
 
 // ---- the transfer statement: pay part of a note inside the pool, keep the rest ------------------------------------------------------
@@ -1417,12 +1315,8 @@ constexpr int T_BITS = 128;
 constexpr int T_NULLIFIER = 0, T_SECRET = 32, T_AMOUNT = 64, T_INDEX = 96, T_TOKEN = 128, T_CHAIN = 160, T_PAY_COMMITMENT = 192, T_PAY_AMOUNT = 224,
               T_CHANGE_COMMITMENT = 256;
 
-struct TransferShape {
-  uint64_t n_wires, n_constraints, first_bit_wire, first_gadget_wire;
-};
-
-static TransferShape transfer_shape(int depth) {
-  TransferShape s;
+static RecordShape transfer_shape(int depth) {
+  RecordShape s{};
   const uint64_t hashes = 8 + (uint64_t)depth;
   s.first_bit_wire = 1 + T_PUB + 8 + 2 * (uint64_t)depth + 1;
   s.first_gadget_wire = s.first_bit_wire + 2 * T_BITS;
@@ -1744,91 +1638,29 @@ __global__ void __launch_bounds__(64) k_check_transfer_records(const uint8_t* __
   const uint8_t* p = rec + (size_t)f * 32;
   bool ok = fe_lt_modulus(fe_load<FrParams>(p));
   const uint32_t* w = reinterpret_cast<const uint32_t*>(p);
-  if (f == 2 || f == 7) ok = ok && (w[4] | w[5] | w[6] | w[7]) == 0;
-  if (f == 7) {  // pay_amount <= amount, most significant word first
-    const uint32_t* a = reinterpret_cast<const uint32_t*>(rec + T_AMOUNT);
-    bool gt = false, decided = false;
-    for (int i = 7; i >= 0; i--) {
-      if (!decided && w[i] != a[i]) { gt = w[i] > a[i]; decided = true; }
-    }
-    ok = ok && !gt;
-  }
-  if (f == 3) {  // index
-    ok = ok && (w[2] | w[3] | w[4] | w[5] | w[6] | w[7]) == 0;
-    const uint64_t idx = (uint64_t)w[0] | ((uint64_t)w[1] << 32);
-    ok = ok && (depth >= 64 || (idx >> depth) == 0);
-  }
+  if (f == 2 || f == 7) ok = ok && rec_amount_ok(w);
+  if (f == 7) ok = ok && rec_le(w, reinterpret_cast<const uint32_t*>(rec + T_AMOUNT));  // pay_amount <= amount
+  if (f == 3) ok = ok && rec_index_ok(w, depth);
   if (!ok) atomicMin(&bad[g], f);
 }
 
-int transfer_shape_query(int depth, uint64_t out[3]) {
-  OG_REQUIRE(depth >= 1 && depth <= 64, "transfer: depth must be 1..64");
-  const TransferShape s = transfer_shape(depth);
-  out[0] = s.n_wires; out[1] = s.n_constraints; out[2] = T_PUB;
-  return OG_OK;
-}
-
-// OG_ERR_INVALID names the first malformed record and its lowest offending field (`base` = index of record 0 in the caller's
-// batch); blocking
-int transfer_records_ok(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, size_t base) {
-  OG_REQUIRE(depth >= 1 && depth <= 64, "transfer: depth must be 1..64");
-  OG_REQUIRE(n <= 65535, "transfer: at most 65535 records per call");  // (the record index is grid.y)
-  if (n == 0) return OG_OK;
-  uint32_t* bad_d = nullptr;
-  OG_TRY(arena_get(ctx, "tr.bad", n * 4, (void**)&bad_d));
-  OG_HIP(hipMemsetAsync(bad_d, 0xff, n * 4, ctx->stream));
+static void transfer_launch_check(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, uint32_t* bad_d) {
   hipLaunchKernelGGL(k_check_transfer_records, dim3(grid_for(T_REC + depth, 64), (unsigned)n), dim3(64), 0, ctx->stream, inputs_d, depth, n, bad_d);
-  OG_HIP(hipGetLastError());
-  std::vector<uint32_t> bad(n);
-  OG_HIP(hipMemcpyAsync(bad.data(), bad_d, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-  OG_HIP(hipStreamSynchronize(ctx->stream));
-  static const char* names[T_REC] = {"nullifier", "secret", "amount", "index", "token", "chain_id", "pay_commitment", "pay_amount", "change_commitment"};
-  for (size_t g = 0; g < n; g++)
-    if (bad[g] != 0xffffffffu) {
-      const std::string name = bad[g] < (uint32_t)T_REC ? std::string(names[bad[g]]) : "sibling " + std::to_string(bad[g] - T_REC);
-      set_error("og_transfer: input record " + std::to_string(base + g) + ": field " + std::to_string(bad[g]) + " (" + name +
-                ") is not a valid value (>= r, an index outside the tree, an amount >= 2^128, or pay_amount > amount)");
-      return OG_ERR_INVALID;
-    }
-  return OG_OK;
 }
 
-// records (checked: transfer_records_ok) -> n x n_wires x 32 B canonical.  The wave-wide walk for calls of at most 512 requests -- the
-// rule and the hooks of withdraw_witness (OG_WITNESS_W9 = 0 | 1 forces either way, OG_WITNESS_W9_MAX moves the bound, OG_W9_ROWS picks
-// the round's form; hooks builds only) --, the lane-local kernel for batches: there a wave per permutation would be paid out of the
-// prover's accumulations
-int transfer_witness(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, uint8_t* out_d) {
-  OG_REQUIRE(depth >= 1 && depth <= 64, "transfer: depth must be 1..64");
-  OG_REQUIRE(n <= 65535, "transfer: at most 65535 witnesses per call");
-  if (n == 0) return OG_OK;
-  const TransferShape s = transfer_shape(depth);
-  ProfScope ps(ctx, PROF_WITNESS, (double)n);
-  const bool w9 = OG_HOOK_SET("OG_WITNESS_W9") ? OG_HOOK_INT("OG_WITNESS_W9", 1) != 0
-                                               : std::max(n, ctx->call_requests) <= (size_t)OG_HOOK_INT("OG_WITNESS_W9_MAX", 512);
-  if (w9) {
-    uint32_t *wl = nullptr, *xch = nullptr;
-    OG_TRY(arena_get(ctx, "wit.w9.limbs", n * (size_t)s.n_wires * 36, (void**)&wl));
-    OG_TRY(arena_get(ctx, "wit.w9.xch", n * (size_t)(depth + TW9_XCH) * 36, (void**)&xch));
-    const uint32_t* c9 = (const uint32_t*)ctx->mimc_consts9_d;
-    OG_W9_LAUNCH(k_tw9_first, w9_rows(), dim3((unsigned)(n * (size_t)(7 + depth))), dim3(64), 0, ctx->stream, c9, inputs_d, depth, (size_t)s.n_wires,
-                 (uint32_t)s.first_gadget_wire, wl, xch);
-    OG_W9_LAUNCH(k_tw9_second, w9_rows(), dim3((unsigned)(n * 5)), dim3(64), 0, ctx->stream, c9, inputs_d, depth, (size_t)s.n_wires,
-                 (uint32_t)s.first_gadget_wire, wl, xch);
-    OG_W9_LAUNCH(k_tw9_chain, w9_rows(), dim3((unsigned)(n * 3)), dim3(64), 0, ctx->stream, c9, inputs_d, depth, (size_t)s.n_wires,
-                 (uint32_t)s.first_gadget_wire, wl, xch);
-    OG_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_wires_from_limbs, dim3(grid_for(s.n_wires, 256), (unsigned)n), dim3(256), 0, ctx->stream, (const uint32_t*)wl, out_d,
-                       (size_t)s.n_wires, (uint32_t)s.n_wires);
-    OG_HIP(hipGetLastError());
-    return OG_OK;
-  }
+static void transfer_launch_core(og_ctx* ctx, int depth, const RecordShape& s, const uint8_t* inputs_d, size_t n, uint8_t* out_d) {
   hipLaunchKernelGGL(k_transfer_core, dim3(grid_for(n, 64)), dim3(64), 0, ctx->stream, (const uint32_t*)ctx->mimc_consts_d, inputs_d, depth,
                      (size_t)s.n_wires, (uint32_t)s.first_bit_wire, n, out_d);
-  OG_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_wires_from_mont, dim3(grid_for(s.n_wires, 256), (unsigned)n), dim3(256), 0, ctx->stream, out_d, (size_t)s.n_wires,
-                     (uint32_t)s.n_wires, 1u);
-  OG_HIP(hipGetLastError());
-  return OG_OK;
+}
+
+static void transfer_launch_w9(og_ctx* ctx, int depth, const RecordShape& s, const uint8_t* inputs_d, size_t n, uint32_t* wl, uint32_t* xch) {
+  const uint32_t* c9 = (const uint32_t*)ctx->mimc_consts9_d;
+  OG_W9_LAUNCH(k_tw9_first, w9_rows(), dim3((unsigned)(n * (size_t)(7 + depth))), dim3(64), 0, ctx->stream, c9, inputs_d, depth, (size_t)s.n_wires,
+               (uint32_t)s.first_gadget_wire, wl, xch);
+  OG_W9_LAUNCH(k_tw9_second, w9_rows(), dim3((unsigned)(n * 5)), dim3(64), 0, ctx->stream, c9, inputs_d, depth, (size_t)s.n_wires,
+               (uint32_t)s.first_gadget_wire, wl, xch);
+  OG_W9_LAUNCH(k_tw9_chain, w9_rows(), dim3((unsigned)(n * 3)), dim3(64), 0, ctx->stream, c9, inputs_d, depth, (size_t)s.n_wires,
+               (uint32_t)s.first_gadget_wire, wl, xch);
 }
 
 // ---- the wave-wide walk of the split and the join statement ---------------------------------------------------------------------------
@@ -1851,8 +1683,6 @@ int transfer_witness(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, 
 // change_asset, [5] k1 of change_leaf, [6] change_asset, [7 .. 10]: 36 words nobody reads -- where the lanes without a limb store
 // (w9_permute `dump`)
 constexpr int SW9_XCH = 11, SW9_DUMP = 7;
-constexpr int S_NULLIFIER = 0, S_SECRET = 32, S_AMOUNT = 64, S_RECIPIENT = 96, S_AMOUNT_OUT = 128, S_INDEX = 160, S_TOKEN = 192, S_CHAIN = 224,
-              S_CHANGE_COMMITMENT = 256;
 // amount_out and change = amount - amount_out as 64-bit halves (transfer's pair: p is what leaves the note, c what stays)
 __device__ __forceinline__ TransferChange split_change(const uint8_t* in) {
   const uint64_t a_lo = *reinterpret_cast<const uint64_t*>(in + S_AMOUNT), a_hi = *reinterpret_cast<const uint64_t*>(in + S_AMOUNT + 8);
@@ -1959,23 +1789,15 @@ __global__ void __launch_bounds__(64) k_sw9_chain(const uint32_t* __restrict__ c
                       xch + (size_t)(depth + 2) * 9, dump, nj, tid, lane);
 }
 
-// The wave-wide walk of n split requests (split_witness decides when).  wl is n x n_wires x 36 B from the arena: 0.52 GB for 512
-// depth-32 requests (28 104 wires each), the largest call that takes this walk by default.
-static int split_walk_w9(og_ctx* ctx, int depth, const SplitShape& s, const uint8_t* inputs_d, size_t n, uint8_t* out_d) {
-  uint32_t *wl = nullptr, *xch = nullptr;
-  OG_TRY(arena_get(ctx, "wit.w9.limbs", n * (size_t)s.n_wires * 36, (void**)&wl));
-  OG_TRY(arena_get(ctx, "wit.w9.xch", n * (size_t)(depth + SW9_XCH) * 36, (void**)&xch));
+// The wave-wide walk of n split requests.  wl is n x n_wires x 36 B from the arena: 0.52 GB for 512 depth-32 requests (28 104 wires
+// each), the largest call that takes this walk by default.
+static void split_launch_w9(og_ctx* ctx, int depth, const RecordShape& s, const uint8_t* inputs_d, size_t n, uint32_t* wl, uint32_t* xch) {
   const uint32_t* c9 = (const uint32_t*)ctx->mimc_consts9_d;
-  const uint32_t fgw = (uint32_t)s.first_bit_wire + 2 * S_BITS;
+  const uint32_t fgw = (uint32_t)s.first_gadget_wire;
   OG_W9_LAUNCH(k_sw9_first, w9_rows(), dim3((unsigned)(n * (size_t)(5 + depth))), dim3(64), 0, ctx->stream, c9, inputs_d, depth, (size_t)s.n_wires, fgw,
                wl, xch);
   OG_W9_LAUNCH(k_sw9_second, w9_rows(), dim3((unsigned)(n * 4)), dim3(64), 0, ctx->stream, c9, inputs_d, depth, (size_t)s.n_wires, fgw, wl, xch);
   OG_W9_LAUNCH(k_sw9_chain, w9_rows(), dim3((unsigned)(n * 2)), dim3(64), 0, ctx->stream, c9, inputs_d, depth, (size_t)s.n_wires, fgw, wl, xch);
-  OG_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_wires_from_limbs, dim3(grid_for(s.n_wires, 256), (unsigned)n), dim3(256), 0, ctx->stream, (const uint32_t*)wl, out_d,
-                     (size_t)s.n_wires, (uint32_t)s.n_wires);
-  OG_HIP(hipGetLastError());
-  return OG_OK;
 }
 
 // join:
@@ -2152,21 +1974,87 @@ __global__ void __launch_bounds__(64) k_jw9_chain(const uint32_t* __restrict__ c
                       lane);
 }
 
-// The wave-wide walk of n join requests (join_witness decides when).  wl is n x n_wires x 36 B from the arena: 1.0 GB for 512
-// depth-32 requests (54 608 wires each), the largest call that takes this walk by default.
-static int join_walk_w9(og_ctx* ctx, int depth, const JoinShape& s, const uint8_t* inputs_d, size_t n, uint8_t* out_d) {
-  uint32_t *wl = nullptr, *xch = nullptr;
-  OG_TRY(arena_get(ctx, "wit.w9.limbs", n * (size_t)s.n_wires * 36, (void**)&wl));
-  OG_TRY(arena_get(ctx, "wit.w9.xch", n * (size_t)(2 * depth + JW9_XCH) * 36, (void**)&xch));
+// The wave-wide walk of n join requests.  wl is n x n_wires x 36 B from the arena: 1.0 GB for 512 depth-32 requests (54 608 wires each),
+// the largest call that takes this walk by default.
+static void join_launch_w9(og_ctx* ctx, int depth, const RecordShape& s, const uint8_t* inputs_d, size_t n, uint32_t* wl, uint32_t* xch) {
   const uint32_t* c9 = (const uint32_t*)ctx->mimc_consts9_d;
-  const uint32_t fgw = (uint32_t)s.first_bit_wire + 3 * J_BITS, ngw = (uint32_t)s.note_gadget_wires;
+  const uint32_t fgw = (uint32_t)s.first_gadget_wire, ngw = (uint32_t)s.note_gadget_wires;
   OG_W9_LAUNCH(k_jw9_first, w9_rows(), dim3((unsigned)(n * (size_t)(7 + 2 * depth))), dim3(64), 0, ctx->stream, c9, inputs_d, depth, (size_t)s.n_wires,
                fgw, ngw, wl, xch);
   OG_W9_LAUNCH(k_jw9_second, w9_rows(), dim3((unsigned)(n * 7)), dim3(64), 0, ctx->stream, c9, inputs_d, depth, (size_t)s.n_wires, fgw, ngw, wl, xch);
   OG_W9_LAUNCH(k_jw9_chain, w9_rows(), dim3((unsigned)(n * 4)), dim3(64), 0, ctx->stream, c9, inputs_d, depth, (size_t)s.n_wires, fgw, ngw, wl, xch);
+}
+
+// ---- the record statements: one descriptor each, and the host code they share (statements.h) ------------------------------------------
+static const char* const SPLIT_FIELDS[S_REC] = {"nullifier", "secret", "amount", "recipient", "amount_out", "index", "token", "chain_id", "change_commitment"};
+static const char* const JOIN_FIELDS[J_REC] = {"nullifier_a", "secret_a", "amount_a", "index_a", "nullifier_b", "secret_b", "amount_b", "index_b",
+                                               "token", "chain_id", "out_commitment"};
+static const char* const TRANSFER_FIELDS[T_REC] = {"nullifier", "secret", "amount", "index", "token", "chain_id", "pay_commitment", "pay_amount",
+                                                   "change_commitment"};
+#ifndef __HIP_DEVICE_COMPILE__  // (host data: the device pass would emit the tables too, and has none of the functions they name)
+const RecordStatement ST_SPLIT = {"split", S_PUB, S_REC, 1, SPLIT_FIELDS, "or amount_out > amount", SW9_XCH, split_shape,
+                                  split_launch_check, split_launch_core, split_launch_w9, split_r1cs_rows};
+const RecordStatement ST_JOIN = {"join", J_PUB, J_REC, 2, JOIN_FIELDS, "amount_a + amount_b >= 2^128, or nullifier_b = nullifier_a", JW9_XCH, join_shape,
+                                 join_launch_check, join_launch_core, join_launch_w9, join_r1cs_rows};
+const RecordStatement ST_TRANSFER = {"transfer", T_PUB, T_REC, 1, TRANSFER_FIELDS, "or pay_amount > amount", TW9_XCH, transfer_shape,
+                                     transfer_launch_check, transfer_launch_core, transfer_launch_w9, transfer_r1cs_rows};
+#endif
+
+int records_shape_query(const RecordStatement& st, int depth, uint64_t out[3]) {
+  OG_REQUIRE(depth >= 1 && depth <= 64, std::string(st.name) + ": depth must be 1..64");
+  const RecordShape s = st.shape(depth);
+  out[0] = s.n_wires; out[1] = s.n_constraints; out[2] = (uint64_t)st.n_pub;
+  return OG_OK;
+}
+
+int records_ok(const RecordStatement& st, og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, size_t base) {
+  OG_REQUIRE(depth >= 1 && depth <= 64, std::string(st.name) + ": depth must be 1..64");
+  OG_REQUIRE(n <= 65535, std::string(st.name) + ": at most 65535 records per call");  // (the record index is grid.y)
+  if (n == 0) return OG_OK;
+  uint32_t* bad_d = nullptr;
+  OG_TRY(arena_get(ctx, "rec.bad", n * 4, (void**)&bad_d));
+  OG_HIP(hipMemsetAsync(bad_d, 0xff, n * 4, ctx->stream));
+  st.launch_check(ctx, depth, inputs_d, n, bad_d);
   OG_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_wires_from_limbs, dim3(grid_for(s.n_wires, 256), (unsigned)n), dim3(256), 0, ctx->stream, (const uint32_t*)wl, out_d,
-                     (size_t)s.n_wires, (uint32_t)s.n_wires);
+  std::vector<uint32_t> bad(n);
+  OG_HIP(hipMemcpyAsync(bad.data(), bad_d, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+  OG_HIP(hipStreamSynchronize(ctx->stream));
+  for (size_t g = 0; g < n; g++)
+    if (bad[g] != 0xffffffffu) {
+      const uint32_t f = bad[g], sib = f - (uint32_t)st.n_rec;  // (a sibling: path sib / depth, level sib % depth)
+      const std::string name = f < (uint32_t)st.n_rec ? std::string(st.field_names[f])
+                               : st.paths == 1        ? "sibling " + std::to_string(sib)
+                                                      : std::string("sibling ") + (char)('a' + sib / depth) + " " + std::to_string(sib % depth);
+      set_error("og_" + std::string(st.name) + ": input record " + std::to_string(base + g) + ": field " + std::to_string(f) + " (" + name +
+                ") is not a valid value (>= r, an index outside the tree, an amount >= 2^128, " + st.invalid_tail + ")");
+      return OG_ERR_INVALID;
+    }
+  return OG_OK;
+}
+
+// The wave-wide walk for the calls witness_walks_wave_wide names -- its limb buffer is n x n_wires x 36 B from the arena --, the lane-local
+// kernel for batches: there a wave per permutation would be paid out of the prover's accumulations
+int records_witness(const RecordStatement& st, og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, uint8_t* out_d) {
+  OG_REQUIRE(depth >= 1 && depth <= 64, std::string(st.name) + ": depth must be 1..64");
+  OG_REQUIRE(n <= 65535, std::string(st.name) + ": at most 65535 witnesses per call");
+  if (n == 0) return OG_OK;
+  const RecordShape s = st.shape(depth);
+  ProfScope ps(ctx, PROF_WITNESS, (double)n);
+  if (witness_walks_wave_wide(ctx, n)) {
+    uint32_t *wl = nullptr, *xch = nullptr;
+    OG_TRY(arena_get(ctx, "wit.w9.limbs", n * (size_t)s.n_wires * 36, (void**)&wl));
+    OG_TRY(arena_get(ctx, "wit.w9.xch", n * (size_t)(st.paths * depth + st.w9_xch) * 36, (void**)&xch));
+    st.launch_w9(ctx, depth, s, inputs_d, n, wl, xch);
+    OG_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_wires_from_limbs, dim3(grid_for(s.n_wires, 256), (unsigned)n), dim3(256), 0, ctx->stream, (const uint32_t*)wl, out_d,
+                       (size_t)s.n_wires, (uint32_t)s.n_wires);
+    OG_HIP(hipGetLastError());
+    return OG_OK;
+  }
+  st.launch_core(ctx, depth, s, inputs_d, n, out_d);
+  OG_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_wires_from_mont, dim3(grid_for(s.n_wires, 256), (unsigned)n), dim3(256), 0, ctx->stream, out_d, (size_t)s.n_wires,
+                     (uint32_t)s.n_wires, 1u);
   OG_HIP(hipGetLastError());
   return OG_OK;
 }
