@@ -5,6 +5,9 @@
 #include "ctx.h"
 #include "statements.h"
 #include "msm.hip.h"
+#include "prover.h"
+#include "primitives.h"
+#include "verify_vk.h"
 #include "glv.h"
 #include <string.h>
 #include <time.h>
@@ -20,49 +23,6 @@ bool debug_sync() {
   if (v < 0) v = getenv("OG_DEBUG_SYNC") ? 1 : 0;
   return v == 1;
 }
-
-int mimc7_init(og_ctx* ctx);
-int mimc7_hash2(og_ctx*, const uint8_t*, const uint8_t*, uint8_t*, size_t);
-int mimc7_merkle_paths(og_ctx*, const uint8_t*, const uint64_t*, const uint8_t*, int, uint8_t*, size_t);
-int mimc7_tree_build(og_ctx*, const uint8_t*, size_t, uint8_t*);
-int mimc7_append(og_ctx*, int, const uint8_t*, uint64_t, const uint8_t*, size_t, uint8_t*, uint8_t*);
-int field_op(og_ctx*, int, int, const uint8_t*, const uint8_t*, uint8_t*, size_t);
-int field_mulchain(og_ctx*, int, uint8_t*, const uint8_t*, size_t, int, float*);
-int field_mulchain_lat(og_ctx*, int, int, uint8_t*, const uint8_t*, size_t, int, float*, uint64_t*);
-int ubench(og_ctx*, int, int, int, float*, uint64_t*);
-int ubench_coresidency(og_ctx*, int, int, int, int, int, int, int, int, int, float*);
-int ntt_canonical(og_ctx*, const uint8_t*, uint8_t*, int, int, int, int);
-int h_poly_canonical(og_ctx*, const uint8_t*, const uint8_t*, const uint8_t*, int, int, uint8_t*);
-
-int pk_load(og_ctx*, const uint8_t*, size_t, og_pk**);
-void pk_destroy(og_pk*);
-void pk_info(const og_pk*, uint64_t*);
-void pk_density(const og_pk*, uint64_t*);
-void pk_windows(const og_pk*, uint64_t*);
-uint64_t pk_bytes(const og_pk*);
-int prove_plan(og_ctx*, const og_pk*, size_t, uint32_t*, size_t, size_t*, int*);
-int prove_batch_device(og_ctx*, const og_pk*, const uint8_t*, size_t, const uint8_t*, uint8_t*, size_t*);
-int prove_batch_host(og_ctx*, const og_pk*, const uint8_t*, size_t, const uint8_t*, uint8_t*);
-int scalar_mul_fixed(og_ctx*, int, const uint8_t*, const uint8_t*, size_t, uint8_t*);
-int lagrange_evals(og_ctx*, int, const uint8_t*, uint8_t*);
-int verify_cpu(const uint8_t*, size_t, const uint8_t*, size_t, const uint8_t*, int*);
-int job_wait(og_job*);
-int prove_partials_enqueue(og_ctx*, const og_pk*, const uint8_t*, size_t, int, int, uint8_t*, og_job**);
-int prove_from_partials(og_ctx*, const og_pk*, const uint8_t*, int, size_t, const uint8_t*, uint8_t*);
-bool glv_pair_ok();
-int job_done_events(og_job*, hipEvent_t*);
-int job_abandon(og_job*);
-bool job_is_live(og_ctx*, og_job*);
-bool job_mark_waiting(og_job*, bool, uint64_t*);
-bool job_same(og_job*, uint64_t);
-bool job_is_waited_for(og_job*);
-bool ctx_has_waiters(og_ctx*);
-int spmv_canonical(og_ctx*, const uint32_t*, const uint32_t*, const uint8_t*, size_t, const uint8_t*, uint8_t*);
-int eddsa_verify(og_ctx*, const uint8_t*, size_t, uint32_t*);
-int vk_load(og_ctx*, const uint8_t*, size_t, og_vk**);
-void vk_destroy(og_vk*);
-void vk_info(const og_vk*, uint64_t*);
-int verify_batch(og_ctx*, const og_vk*, const uint8_t*, const uint8_t*, size_t, uint32_t*);
 
 }  // namespace og
 

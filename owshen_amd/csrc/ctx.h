@@ -165,6 +165,7 @@ namespace og {
 static inline int w9_rows() { return (int)OG_HOOK_INT("OG_W9_ROWS", 2); }
 
 void set_error(const std::string& msg);
+std::string get_error();
 
 // every stream of a context that can hold work: the two lanes, the tail / aux streams of the stage pipeline and the copy
 // stream (which runs the B1 MSM of a single request).  Anything that frees or reuses scratch drains ALL of them.

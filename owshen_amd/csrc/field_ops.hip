@@ -1,6 +1,7 @@
 // Elementwise field kernels behind og_field_op_d / og_field_mulchain_d:
 // the parity surface for Montgomery add/sub/mul/inv and the mulmod/s micro-benchmark.
 #include "ctx.h"
+#include "primitives.h"
 #include "field.hip.h"
 #include "field_w9.hip.h"
 

@@ -22,6 +22,7 @@
 #include "ctx.h"
 #include "statements.h"
 #include "msm.hip.h"
+#include "prover.h"
 #include "field.hip.h"
 #include "glv.h"
 #include "ec.hip.h"
@@ -64,19 +65,6 @@ struct og_pk {
 };
 
 namespace og {
-
-int scalar_mul_fixed_g1(og_ctx*, const uint8_t*, const uint8_t*, size_t, uint8_t*);
-int scalar_mul_fixed_g2(og_ctx*, const uint8_t*, const uint8_t*, size_t, uint8_t*);
-int fixed_table_g1(og_ctx*, const uint8_t*, uint8_t*);
-int import_points_g1(og_ctx*, const uint8_t*, uint8_t*, size_t);
-int import_points_g2(og_ctx*, const uint8_t*, uint8_t*, size_t);
-int assemble_g1(og_ctx*, const uint8_t*, const uint8_t*, const uint8_t*, const uint8_t*, const uint8_t*, const uint8_t*, size_t,
-                uint8_t*, uint8_t*, const uint8_t*);
-int assemble_g2(og_ctx*, const uint8_t*, const uint8_t*, const uint8_t*, const uint8_t*, size_t, uint8_t*, bool wave_per_proof = false);
-int assemble_g1_early(og_ctx*, const uint8_t*, const uint8_t*, const uint8_t*, const uint8_t*, size_t, uint8_t*, uint8_t*, const uint8_t*, hipEvent_t);
-int assemble_g1_late(og_ctx*, const uint8_t*, const uint8_t*, size_t, const uint8_t*, uint8_t*, bool);
-int fixed_table_g2(og_ctx*, const uint8_t*, uint8_t*);
-int ntt_domain_consts(og_ctx* ctx, int log_n, uint8_t** consts_d);
 
 // ---- sparse matrix x witness ---------------------------------------------------------
 // out[g][row] = sum_k val[k] * x[g][col[k]] for row < n_rows, 0 for n_rows <= row < n_out.

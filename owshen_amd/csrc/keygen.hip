@@ -16,6 +16,7 @@
 //                      GPU; returns the OWPK0001 / OWVK0001 blobs of include/owshen_gpu.h
 #include "ctx.h"
 #include "msm.hip.h"
+#include "prover.h"
 #include "field.hip.h"
 #include "keygen.h"
 #include "statements.h"
@@ -26,10 +27,6 @@
 
 
 namespace og {
-
-int lagrange_evals(og_ctx*, int, const uint8_t*, uint8_t*);
-int spmv_canonical(og_ctx*, const uint32_t*, const uint32_t*, const uint8_t*, size_t, const uint8_t*, uint8_t*);
-int scalar_mul_fixed(og_ctx*, int, const uint8_t*, const uint8_t*, size_t, uint8_t*);
 
 // ---- tiny host-side Fr (only what building linear combinations needs: add, small constants, -1) -----------------
 struct HFr {
@@ -184,7 +181,7 @@ static int r1cs_begin(og_r1cs* r, const uint64_t shp[3], uint64_t n_pub, const s
 constexpr uint32_t KW_ROOT = 1, KW_NH = 2, KW_RECIPIENT = 3, KW_AMOUNT = 4, KW_TOKEN = 5, KW_CHAIN = 6, KW_NULLIFIER = 7, KW_SECRET = 8;
 constexpr uint32_t K_PAD_SEGMENT = 64;
 
-int withdraw_r1cs_build(const uint8_t* mimc_consts, int depth, uint64_t n_pad3, uint64_t n_pad2, int dense, og_r1cs* r) {
+static int withdraw_r1cs_build(const uint8_t* mimc_consts, int depth, uint64_t n_pad3, uint64_t n_pad2, int dense, og_r1cs* r) {
   uint64_t shp[3];
   OG_TRY(withdraw_shape_query(depth, n_pad3, n_pad2, shp));
   OG_REQUIRE(n_pad3 < (1ull << 30) && n_pad2 < (1ull << 30), "og_withdraw_r1cs: too many padding gates");
@@ -219,7 +216,7 @@ int withdraw_r1cs_build(const uint8_t* mimc_consts, int depth, uint64_t n_pad3, 
 }
 
 // the deposit statement (oracle/py/deposit.py; witness.hip k_deposit_witness): 735 wires, 731 rows
-int deposit_r1cs_build(const uint8_t* mimc_consts, og_r1cs* r) {
+static int deposit_r1cs_build(const uint8_t* mimc_consts, og_r1cs* r) {
   uint64_t shp[3];
   OG_TRY(deposit_shape_query(shp));
   r->n_wires = shp[0];
@@ -293,7 +290,7 @@ void transfer_r1cs_rows(R1csBuilder& b, int depth) {
   b.hash2(R1csBuilder::one(TW_CHANGE_COMMITMENT), R1csBuilder::one(change_asset), (int)TW_CHANGE_LEAF);
 }
 
-int records_r1cs_build(const RecordStatement& st, const uint8_t* mimc_consts, int depth, og_r1cs* r) {
+static int records_r1cs_build(const RecordStatement& st, const uint8_t* mimc_consts, int depth, og_r1cs* r) {
   const std::string who = "og_" + std::string(st.name) + "_r1cs";
   uint64_t shp[3];
   OG_TRY(records_shape_query(st, depth, shp));
@@ -419,7 +416,7 @@ void csr_transpose(const std::vector<uint32_t>& ptr, const std::vector<uint32_t>
     }
 }
 
-int keygen_setup(og_ctx* ctx, const og_r1cs* r, const uint8_t toxic[160], std::vector<uint8_t>& pk, std::vector<uint8_t>& vk) {
+static int keygen_setup(og_ctx* ctx, const og_r1cs* r, const uint8_t toxic[160], std::vector<uint8_t>& pk, std::vector<uint8_t>& vk) {
   const size_t m = r->n_wires, l = r->n_pub, nc = r->n_constraints, n_rows = nc + l + 1;
   QapRows rows;
   OG_TRY(r1cs_qap_rows(r, "og_setup", &rows));

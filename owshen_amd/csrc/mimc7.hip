@@ -1,6 +1,7 @@
 // Batched MiMC7 kernels: 2-to-1 hash, Merkle paths, full-tree build.
 // One lane per hash; purely VALU-bound (728 mulmod per 2-to-1 hash vs 96 B of traffic).
 #include "ctx.h"
+#include "primitives.h"
 #include "mimc7.hip.h"
 #include "host_fr4.h"
 #include <string.h>

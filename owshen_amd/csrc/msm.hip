@@ -1211,17 +1211,6 @@ int msm_digit_sort_windows(og_ctx* ctx, int slot, const uint8_t* scalars_d, size
 }
 
 // ---- dispatch to the per-group translation units ---------------------------------------
-int msm_run_g1(og_ctx*, const og_bases*, const DigitSort&, uint8_t*, bool, int);
-int msm_run_g2(og_ctx*, const og_bases*, const DigitSort&, uint8_t*, bool, int);
-int msm_combine_g1(og_ctx*, const og_bases*, const uint8_t*, int, int, uint8_t*);
-int msm_combine_g2(og_ctx*, const og_bases*, const uint8_t*, int, int, uint8_t*);
-int msm_sum_ranks_g1(og_ctx*, const uint8_t*, size_t, int, int, uint8_t*);
-int msm_sum_ranks_g2(og_ctx*, const uint8_t*, size_t, int, int, uint8_t*);
-int bases_fill_g1(og_ctx*, og_bases*, const uint8_t*);
-int bases_fill_g2(og_ctx*, og_bases*, const uint8_t*);
-int xyzz_to_affine_bytes_g1(og_ctx*, const uint8_t*, uint8_t*, size_t);
-int xyzz_to_affine_bytes_g2(og_ctx*, const uint8_t*, uint8_t*, size_t);
-
 static int msm_run_any(og_ctx* ctx, const og_bases* bases, const DigitSort& ds, uint8_t* out_xyzz_d, bool partial, int phase = MSM_FULL) {
   OG_REQUIRE(bases->c == ds.c && bases->precomp == ds.precomp, "msm: bases/digit-sort window mismatch");
   OG_REQUIRE(bases->n >= ds.n, "msm: more scalars than bases");

@@ -78,11 +78,39 @@ int xyzz_to_affine_bytes(og_ctx* ctx, int is_g2, const uint8_t* xyzz_d, uint8_t*
 int arena_get(og_ctx* ctx, const char* name, size_t bytes, void** out);
 bool arena_has(og_ctx* ctx, const char* name);
 
-}  // namespace og
+// ---- the per-group instantiations (msm_g1.hip, msm_g2.hip) --------------------------------------------------------------------------
+// what msm.hip dispatches to on og_bases::is_g2 ...
+int msm_run_g1(og_ctx* ctx, const og_bases* b, const DigitSort& ds, uint8_t* out, bool partial, int phase);
+int msm_run_g2(og_ctx* ctx, const og_bases* b, const DigitSort& ds, uint8_t* out, bool partial, int phase);
+int msm_combine_g1(og_ctx* ctx, const og_bases* b, const uint8_t* gathered, int world, int batch, uint8_t* out);
+int msm_combine_g2(og_ctx* ctx, const og_bases* b, const uint8_t* gathered, int world, int batch, uint8_t* out);
+int msm_sum_ranks_g1(og_ctx* ctx, const uint8_t* gathered, size_t rank_stride, int world, int batch, uint8_t* out);
+int msm_sum_ranks_g2(og_ctx* ctx, const uint8_t* gathered, size_t rank_stride, int world, int batch, uint8_t* out);
+int bases_fill_g1(og_ctx* ctx, og_bases* b, const uint8_t* pts);
+int bases_fill_g2(og_ctx* ctx, og_bases* b, const uint8_t* pts);
+int xyzz_to_affine_bytes_g1(og_ctx* ctx, const uint8_t* in, uint8_t* out, size_t n);
+int xyzz_to_affine_bytes_g2(og_ctx* ctx, const uint8_t* in, uint8_t* out, size_t n);
 
-// ---- other internal entry points used by the Groth16 prover (groth16.hip) ----------------
-namespace og {
-// H-polynomial on device buffers (ntt.hip): a, b, c Montgomery evaluations (destroyed), tmp scratch,
-// h_out canonical coefficients; all batch x d x 32 B
-int h_poly_device(og_ctx* ctx, uint8_t* a, uint8_t* b, uint8_t* c, uint8_t* tmp, uint8_t* h_out, int log_d, int batch);
+// ... and what the prover (groth16.hip) calls: fixed-base multiplication, point import, proof assembly (ecmul_impl.hip.h)
+// tab_d: 64 x 16 x 128 B fixed-base table of the point at base_mont_d (see k_fixed_table)
+int fixed_table_g1(og_ctx* ctx, const uint8_t* base_mont_d, uint8_t* tab_d);
+int fixed_table_g2(og_ctx* ctx, const uint8_t* base_mont_d, uint8_t* tab_d);
+int scalar_mul_fixed_g1(og_ctx* ctx, const uint8_t* tab_d, const uint8_t* k_d, size_t n, uint8_t* out_d);
+int scalar_mul_fixed_g2(og_ctx* ctx, const uint8_t* tab_d, const uint8_t* k_d, size_t n, uint8_t* out_d);
+int import_points_g1(og_ctx* ctx, const uint8_t* in_d, uint8_t* out_d, size_t n);
+int import_points_g2(og_ctx* ctx, const uint8_t* in_d, uint8_t* out_d, size_t n);
+// proofs_d[g][0:64] = A, [192:256] = C   (tmp_d: n x 4 x 17 x 128 B scratch: four products + their four window tables per proof)
+// glv_d (optional): n x 4 x 32 B, the GLV halves of r, r s, s, r per proof (glv.h) -- then eight lanes per proof walk
+// half-length chains (tmp_d: n x 8 x 17 x 128 B)
+int assemble_g1(og_ctx* ctx, const uint8_t* consts_d, const uint8_t* rs_d, const uint8_t* res_a, const uint8_t* res_b1,
+                const uint8_t* res_l, const uint8_t* res_h, size_t n, uint8_t* tmp_d, uint8_t* proofs_d, const uint8_t* glv_d);
+// assemble_g1 in two parts (ecmul_impl.hip.h), each on the ctx's current stream: the products (need the A and B1 results), then A's
+// sum (`early`); C's sum (`late`: needs the L and H results and the PRODUCTS -- `products_done`, if given, is recorded between the two)
+int assemble_g1_early(og_ctx* ctx, const uint8_t* consts_d, const uint8_t* rs_d, const uint8_t* res_a, const uint8_t* res_b1, size_t n,
+                      uint8_t* tmp_d, uint8_t* proofs_d, const uint8_t* glv_d, hipEvent_t products_done);
+int assemble_g1_late(og_ctx* ctx, const uint8_t* res_l, const uint8_t* res_h, size_t n, const uint8_t* tmp_d, uint8_t* proofs_d, bool glv);
+// proofs_d[g][64:192] = B
+int assemble_g2(og_ctx* ctx, const uint8_t* consts_d, const uint8_t* fb_tab_d, const uint8_t* rs_d, const uint8_t* res_b2, size_t n,
+                uint8_t* proofs_d, bool wave_per_proof = false);
+
 }  // namespace og

@@ -16,6 +16,7 @@
 #include "ctx.h"
 #include "statements.h"
 #include "msm.hip.h"
+#include "prover.h"
 #include <algorithm>
 #include <condition_variable>
 #include <functional>
@@ -69,16 +70,6 @@ struct og_multi {
 };
 
 namespace og {
-
-int pk_load(og_ctx*, const uint8_t*, size_t, og_pk**);
-void pk_destroy(og_pk*);
-int prove_batch_host(og_ctx*, const og_pk*, const uint8_t*, size_t, const uint8_t*, uint8_t*);
-int prove_partials_enqueue(og_ctx*, const og_pk*, const uint8_t*, size_t, int, int, uint8_t*, og_job**);
-int prove_from_partials(og_ctx*, const og_pk*, const uint8_t*, int, size_t, const uint8_t*, uint8_t*);
-int job_join_stream(og_job*, hipStream_t);
-int job_wait(og_job*);
-int job_abandon(og_job*);
-std::string get_error();
 
 #define OG_NCCL(expr)                                                                                          \
   do {                                                                                                         \
@@ -176,7 +167,7 @@ static int nccl_grouped(og_multi* m, F&& enqueue, const char* site = nullptr) {
   return OG_OK;
 }
 
-int multi_init(int n_devices, og_multi** out) {
+static int multi_init(int n_devices, og_multi** out) {
   int avail = 0;
   if (hipGetDeviceCount(&avail) != hipSuccess || avail == 0) {
     set_error("og_multi_init: no HIP device visible (this library has no CPU fallback)");
@@ -224,7 +215,7 @@ int multi_init(int n_devices, og_multi** out) {
   return OG_OK;
 }
 
-void multi_shutdown(og_multi* m) {
+static void multi_shutdown(og_multi* m) {
   if (!m) return;
   for (auto& w : m->workers) {
     {
@@ -240,7 +231,7 @@ void multi_shutdown(og_multi* m) {
   delete m;
 }
 
-int multi_pk_load(og_multi* m, const uint8_t* blob, size_t len, og_pk** pks_out) {
+static int multi_pk_load(og_multi* m, const uint8_t* blob, size_t len, og_pk** pks_out) {
   for (int r = 0; r < m->n; r++) pks_out[r] = nullptr;
   int rc = for_each_device(m, [&](int r) -> int {
     std::lock_guard<std::mutex> lk(m->ctx[r]->mu);
@@ -254,7 +245,7 @@ int multi_pk_load(og_multi* m, const uint8_t* blob, size_t len, og_pk** pks_out)
   return rc;
 }
 
-int multi_prove_batch(og_multi* m, og_pk* const* pks, const uint8_t* witnesses, size_t wit_bytes, size_t n, const uint8_t* rs,
+static int multi_prove_batch(og_multi* m, og_pk* const* pks, const uint8_t* witnesses, size_t wit_bytes, size_t n, const uint8_t* rs,
                       uint8_t* proofs_out) {
   return for_each_device(m, [&](int r) -> int {
     size_t lo, hi;
@@ -265,7 +256,7 @@ int multi_prove_batch(og_multi* m, og_pk* const* pks, const uint8_t* witnesses, 
   }, "prove");
 }
 
-int multi_withdraw_prove_batch(og_multi* m, og_pk* const* pks, int depth, uint64_t n_pad3, uint64_t n_pad2, const uint8_t* inputs,
+static int multi_withdraw_prove_batch(og_multi* m, og_pk* const* pks, int depth, uint64_t n_pad3, uint64_t n_pad2, const uint8_t* inputs,
                                size_t n, const uint8_t* rs, uint8_t* proofs_out, uint8_t* public_out) {
   uint64_t info[4];
   OG_TRY(og_pk_info(pks[0], info));
@@ -294,7 +285,7 @@ int multi_withdraw_prove_batch(og_multi* m, og_pk* const* pks, int depth, uint64
 //   3. device 0: adds the shares, assembles, copies the proofs out; every device: the front half's verdict (boundary flags,
 //      satisfiability -- all ranks saw the same inputs) and, on device 0, the public inputs.
 // A failure at any step leaves no job pending on any device and no RCCL group open: the next call works.
-int multi_prove_sharded(og_multi* m, og_pk* const* pks, int depth, uint64_t n_pad3, uint64_t n_pad2, const uint8_t* inputs,
+static int multi_prove_sharded(og_multi* m, og_pk* const* pks, int depth, uint64_t n_pad3, uint64_t n_pad2, const uint8_t* inputs,
                         const uint8_t* witnesses, size_t wit_bytes, size_t n, const uint8_t* rs, uint8_t* proofs_out, uint8_t* public_out) {
   const int G = m->n;
   const size_t pbytes = n * (size_t)OG_PARTIAL_BYTES;
@@ -365,7 +356,7 @@ int multi_prove_sharded(og_multi* m, og_pk* const* pks, int depth, uint64_t n_pa
   return rc;
 }
 
-int multi_bases_create(og_multi* m, int is_g2, const uint8_t* points, size_t n, int c, int precomp, og_bases** out) {
+static int multi_bases_create(og_multi* m, int is_g2, const uint8_t* points, size_t n, int c, int precomp, og_bases** out) {
   for (int r = 0; r < m->n; r++) out[r] = nullptr;
   const size_t pb = is_g2 ? 128 : 64;
   int rc = for_each_device(m, [&](int r) -> int {
@@ -387,7 +378,7 @@ int multi_bases_create(og_multi* m, int is_g2, const uint8_t* points, size_t n, 
   return rc;
 }
 
-int multi_msm(og_multi* m, og_bases* const* bases, const uint8_t* scalars, size_t n, uint8_t* out) {
+static int multi_msm(og_multi* m, og_bases* const* bases, const uint8_t* scalars, size_t n, uint8_t* out) {
   const int G = m->n;
   const og_bases* b0 = bases[0];
   const size_t pb = b0->is_g2 ? 128 : 64, xb = 2 * pb;

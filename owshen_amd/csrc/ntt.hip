@@ -16,6 +16,7 @@
 #include "ctx.h"
 #include "field.hip.h"
 #include "msm.hip.h"  // arena_get
+#include "prover.h"
 
 namespace og {
 

@@ -1,0 +1,33 @@
+// What the leaf units offer to the entry points (capi.hip): the MiMC7 hash and tree (mimc7.hip), the field operations (field_ops.hip),
+// the micro-benchmarks (ubench.hip) and EdDSA verification (eddsa.hip).
+#pragma once
+#include "ctx.h"
+
+namespace og {
+
+// ---- mimc7.hip ----------------------------------------------------------------------------------------------------------------------
+int mimc7_init(og_ctx* ctx);
+int mimc7_hash2(og_ctx* ctx, const uint8_t* l, const uint8_t* r, uint8_t* out, size_t n);
+int mimc7_merkle_paths(og_ctx* ctx, const uint8_t* leaves, const uint64_t* idx, const uint8_t* sib, int depth,
+                       uint8_t* nodes, size_t n);
+int mimc7_tree_build(og_ctx* ctx, const uint8_t* leaves, size_t n, uint8_t* nodes);
+int mimc7_append(og_ctx* ctx, int depth, const uint8_t* frontier_in, uint64_t next_index, const uint8_t* leaves, size_t k,
+                 uint8_t* frontier_out, uint8_t* root_out);
+
+// ---- field_ops.hip ------------------------------------------------------------------------------------------------------------------
+int field_op(og_ctx* ctx, int field, int op, const uint8_t* a, const uint8_t* b, uint8_t* out, size_t n);
+int field_mulchain(og_ctx* ctx, int field, uint8_t* x, const uint8_t* y, size_t n, int iters, float* ms);
+// form 0: lane-local fe_mul, one lane per element (64-lane workgroups); form 1: w9, one wave per element
+int field_mulchain_lat(og_ctx* ctx, int field, int form, uint8_t* x, const uint8_t* y, size_t n, int iters, float* ms, uint64_t* cycles_out);
+
+// ---- ubench.hip ---------------------------------------------------------------------------------------------------------------------
+int ubench(og_ctx* ctx, int kind, int iters, int blocks, float* ms, uint64_t* wave_cycles);
+// out[0] = resident kernel ms, out[1] = filler ms while the resident kernel runs (queued `delay_us` after it), out[2] = the
+// same filler launch alone
+int ubench_coresidency(og_ctx* ctx, int wgs_per_cu, int kind, int iters, int filler_blocks, int filler_threads, int filler_lds,
+                       int filler_prio, int filler_work, int delay_us, float out[3]);
+
+// ---- eddsa.hip ----------------------------------------------------------------------------------------------------------------------
+int eddsa_verify(og_ctx* ctx, const uint8_t* recs_d, size_t n, uint32_t* ok_d);
+
+}  // namespace og

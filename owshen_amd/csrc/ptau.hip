@@ -295,7 +295,7 @@ static int ptau_sections(BinFile& bf, const PtauHeader& hd, const std::string& w
 }
 
 // who: the entry point the reasons name (og_setup_ptau, or og_pk_verify rebuilding the delta = 1 key)
-int ptau_setup(og_ctx* ctx, const og_r1cs* r, const uint8_t* data, size_t len, std::vector<uint8_t>& pk, std::vector<uint8_t>& vk,
+static int ptau_setup(og_ctx* ctx, const og_r1cs* r, const uint8_t* data, size_t len, std::vector<uint8_t>& pk, std::vector<uint8_t>& vk,
                const std::string& who = "og_setup_ptau") {
   BinFile bf;
   PtauHeader hd;
@@ -407,7 +407,7 @@ static int smul_uniform(og_ctx* ctx, ZDev& dev, const uint8_t* in, size_t n, con
   return OG_OK;
 }
 
-int pk_contribute(og_ctx* ctx, const uint8_t* pkb, size_t pk_len, const uint8_t* vkb, size_t vk_len, const uint8_t dd[32], std::vector<uint8_t>& pk,
+static int pk_contribute(og_ctx* ctx, const uint8_t* pkb, size_t pk_len, const uint8_t* vkb, size_t vk_len, const uint8_t dd[32], std::vector<uint8_t>& pk,
                   std::vector<uint8_t>& vk) {
   const std::string who = "og_pk_contribute";
   const Fr dv = zfr_load(dd);
@@ -535,7 +535,7 @@ static int ctx_is_idle(og_ctx* ctx, const std::string& who) {
   return OG_OK;
 }
 
-int ptau_verify(og_ctx* ctx, const uint8_t* data, size_t len, uint32_t* failed_out) {
+static int ptau_verify(og_ctx* ctx, const uint8_t* data, size_t len, uint32_t* failed_out) {
   const std::string who = "og_ptau_verify";
   BinFile bf;
   PtauHeader hd;
@@ -605,7 +605,7 @@ static int canon_to_mont(og_ctx* ctx, ZDev& dev, const uint8_t* in, size_t n, ui
   });
 }
 
-int pk_verify(og_ctx* ctx, const og_r1cs* r, const uint8_t* data, size_t len, const uint8_t* pkb, size_t pk_len, const uint8_t* vkb, size_t vk_len,
+static int pk_verify(og_ctx* ctx, const og_r1cs* r, const uint8_t* data, size_t len, const uint8_t* pkb, size_t pk_len, const uint8_t* vkb, size_t vk_len,
               uint32_t* failed_out) {
   const std::string who = "og_pk_verify";
   OG_REQUIRE(pk_is_blob(pkb, pk_len), who + ": not an OWPK0001 blob");

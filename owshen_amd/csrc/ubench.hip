@@ -2,6 +2,7 @@
 // kernels (SURVEY.md 8d caveat: the path is bound by 32-bit integer-multiply VALU rate, not
 // HBM).  Each lane runs `iters` iterations of 16 independent instructions of one kind.
 #include "ctx.h"
+#include "primitives.h"
 #include "mimc7.hip.h"
 #include <time.h>
 

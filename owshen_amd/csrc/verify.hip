@@ -7,6 +7,7 @@
 // final exponentiation.  It reuses the SAME 9 x 29-bit field layer and group law as the kernels, compiled for
 // the host (no GPU is touched: the verifier must work on a sequencer without one).
 #include "verify_tower.h"
+#include "verify_vk.h"
 #include "key_blob.h"
 
 namespace og {

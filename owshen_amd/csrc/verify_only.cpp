@@ -7,12 +7,12 @@
 // into a library whose only dependencies are libstdc++ and libc.  Same entry points, same bytes in and out as the full
 // library's og_verify (include/owshen_gpu.h).
 #include "ctx.h"
+#include "verify_vk.h"
 
 namespace og {
 
 static thread_local std::string g_err;
 void set_error(const std::string& msg) { g_err = msg; }
-int verify_cpu(const uint8_t*, size_t, const uint8_t*, size_t, const uint8_t*, int*);
 
 }  // namespace og
 

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include <vector>
+#include "../../include/owshen_gpu.h"  // og_ctx, og_vk
 
 namespace og {
 
@@ -23,5 +24,14 @@ struct VkHost {
 int vk_precompute(const uint8_t* vk, size_t vk_len, VkHost& out);
 // og_verify's own final exponentiation (the plain 2790-bit power) on a value in VkHost::ab's layout: is the result one?
 bool f12_plain_is_one(const uint32_t limbs[108]);
+
+// ---- the verifier's functions behind the entry points (capi.hip, verify_only.cpp) --------------------------------------------------
+// og_verify on the CPU (verify.hip); the verifying key's layout: key_blob.h
+int verify_cpu(const uint8_t* vk, size_t vk_len, const uint8_t* pub, size_t n_pub, const uint8_t* proof, int* ok);
+// the og_vk handle and batched verification on the GPU (verify_gpu.hip)
+int vk_load(og_ctx* ctx, const uint8_t* blob, size_t len, og_vk** out);
+void vk_destroy(og_vk* vk);
+void vk_info(const og_vk* vk, uint64_t info[4]);
+int verify_batch(og_ctx* ctx, const og_vk* vk, const uint8_t* pub_d, const uint8_t* proofs_d, size_t n, uint32_t* ok_out);
 
 }  // namespace og

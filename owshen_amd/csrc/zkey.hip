@@ -87,7 +87,7 @@ static void zcsr(std::vector<ZEnt>& ent, uint64_t d, std::vector<uint32_t>& ptr,
 // r1cs (optional): the circuit the key was made for (og_r1cs_read of circom's .r1cs).  Its A and B matrices must be the key's
 // coefficient section, row for row; its C matrix then rides in the imported key (header flag 0), and the prover refuses a
 // witness that violates a constraint exactly as it does for a key of og_setup.
-int zkey_import(og_ctx* ctx, const uint8_t* data, size_t len, const og_r1cs* r1cs, std::vector<uint8_t>& pk, std::vector<uint8_t>& vk) {
+static int zkey_import(og_ctx* ctx, const uint8_t* data, size_t len, const og_r1cs* r1cs, std::vector<uint8_t>& pk, std::vector<uint8_t>& vk) {
   const std::string who = "og_zkey_import";
   BinFile bf;
   OG_TRY(binfile_parse(data, len, "zkey", 1, who, &bf));
@@ -206,7 +206,7 @@ int zkey_import(og_ctx* ctx, const uint8_t* data, size_t len, const og_r1cs* r1c
 // snarkjs' prover takes C z = (A z) o (B z), which is C z for every satisfying witness); the H section is the inverse transform
 //   H'[i] = 1/d sum_j w^(-i j) (-2 psi^j)^-1 H[j],   H[d - 1] := the point at infinity
 // (the quotient has degree <= d - 2, so its d-th coefficient never meets a base); section 10 says "no contributions".
-int zkey_export(og_ctx* ctx, const uint8_t* pkb, size_t pk_len, const uint8_t* vkb, size_t vk_len, std::vector<uint8_t>& out) {
+static int zkey_export(og_ctx* ctx, const uint8_t* pkb, size_t pk_len, const uint8_t* vkb, size_t vk_len, std::vector<uint8_t>& out) {
   const std::string who = "og_zkey_export";
   PkView pv;
   VkView vv;
