@@ -195,7 +195,13 @@ int og_msm_combine_d(og_ctx* ctx, const og_bases* bases, const uint8_t* gathered
  * the witness and its first such wire.  Checked on the GPU for every caller-supplied witness (one more read of it), before
  * "does not satisfy": the reference's `Fp::from_repr` rejects such bytes
  * (/root/reference/src/blockchain/tx/owshen_airdrop/babyjubjub/mod.rs:7-11), and reducing them silently would prove a
- * statement about a different byte string than the caller holds. */
+ * statement about a different byte string than the caller holds.
+ * The blinding scalars are NOT under that rule: r and s are any 32-byte values, read as integers below 2^256 and used modulo the
+ * group order, so the proof for (r, s) is byte for byte the proof for (r mod order, s mod order) -- they are randomness the caller
+ * chose, not part of a statement, and a reduced value proves nothing different.  Every form of the assembly keeps this (the
+ * kernels walk all 256 bits and reduce r s in the field layer; a call that holds one such scalar forms none of its products from
+ * GLV halves, since og_glv_decompose refuses a non-canonical scalar): tests/assembly_edge_cases.py pins it for r, s in
+ * {order, order + 7, 2^256 - 1}. */
 int og_pk_load(og_ctx* ctx, const uint8_t* blob, size_t len, og_pk** out);
 /* Frees the key's device memory.  Waits for the device first, so a submitted call that still reads the key finishes its
  * kernels -- but its results are only delivered by og_job_wait, which the caller still owes (or og_job_abandon). */

@@ -367,4 +367,156 @@ extern "C" int og_hook_ec_chain_d(og_ctx* ctx, int g2, const uint32_t* acc_d, co
     return OG_OK;
   });
 }
+// ---- the wave-wide forms driven alone, on raw limbs ---------------------------------------------------------------------------
+// og_hook_w9_raw_d hands ONE routine of field_w9.hip.h / mimc7.hip.h its operands as limbs, one 64-lane workgroup per case, and
+// returns the result word of ALL 64 lanes (tests/w9_raw_cases.py holds the cases and the integer models).  in: n x 3 slots x 9 limbs,
+// out: n x 5 words x 64 lanes.  Ops (a = slot 0 where it is the uniform operand):
+//   0  w9_mul<M>(a, slot 1)                      one digit per wave, the element in lanes 0 .. 8
+//   1  w9_mul<M, true, false>(a, slot 1 | 2)     a digit per row: slot 1 in row 0, slot 2 in row 1
+//   2  w9_mul<M, true, true>                     the same with the 32-bit digit
+//   3  w9_carry(slot 0 | 1)                      rows 0 | 1
+//   4, 5, 6  w9_carry(w9_sub(slot 0, slot 1, w9_kn_limb<M, 4 | 8 | 16>))        (Fq, as the group law uses them)
+//   7  w9_spread -> word 0, w9_collect -> fe_from_lazy_limbs -> word 1 (every row of 16 lanes gives its lanes' own copy)
+//   8  w9_mimc7_round<2>(t = slot 0 in both rows) -> t2, t4, t6, t6r0, x       (Fr)
+//   9  w9_mimc7_hash2<2>(l = slot 0, r = slot 1, lane-local) -> word 0 as in op 7      (Fr)
+#include "ec_w9.hip.h"
+#include "mimc7.hip.h"
+
+namespace og {
+
+constexpr int W9_SLOTS = 3, W9_OUTS = 5, W9_NOPS = 10;
+
+template <class M>
+constexpr bool w9_raw_valid(int op) {
+  return op >= 0 && op < W9_NOPS && (op < 4 || op == 7 || (op < 7 ? std::is_same<M, FqParams>::value : std::is_same<M, FrParams>::value));
+}
+
+template <class M>
+__device__ __forceinline__ Fe<M> w9_raw_fe(const uint32_t* p) {
+  Fe<M> r;
+#pragma unroll
+  for (int k = 0; k < 9; k++) r.l[k] = p[k];
+  return r;
+}
+
+template <class M, int OP>
+__global__ void __launch_bounds__(64) k_w9_raw(const uint32_t* __restrict__ in, size_t n, uint32_t* __restrict__ out,
+                                              const uint32_t* __restrict__ consts9) {
+  const size_t i = blockIdx.x;
+  if (i >= n) return;
+  const int tid = threadIdx.x, rl = w9_row_limb(tid);
+  const bool row1 = (tid & 16) != 0;
+  const uint32_t* x = in + i * (W9_SLOTS * 9);
+  uint32_t o[W9_OUTS] = {0u, 0u, 0u, 0u, 0u};
+  if constexpr (OP == 0) {
+    o[0] = w9_mul<M>(w9_gather(w9_const_limb(x, tid)), w9_const_limb(x + 9, tid), w9_modulus_limb<M>(tid));
+  } else if constexpr (OP == 1 || OP == 2) {
+    o[0] = w9_mul<M, true, OP == 2>(w9_gather(w9_const_limb(x, tid)), w9_const_limb(row1 ? x + 18 : x + 9, rl), w9_modulus_limb<M>(rl));
+  } else if constexpr (OP == 3) {
+    o[0] = w9_carry(w9_const_limb(row1 ? x + 9 : x, rl), rl);
+  } else if constexpr (OP >= 4 && OP <= 6) {
+    constexpr int K = OP == 4 ? 4 : OP == 5 ? 8 : 16;
+    o[0] = w9_carry(w9_sub(w9_const_limb(x, tid), w9_const_limb(x + 9, tid), w9_kn_limb<M, K>(tid)), tid);
+  } else if constexpr (OP == 7) {
+    o[0] = w9_spread(w9_raw_fe<M>(x), tid);
+    const Fe<M> c = w9_collect<M>(o[0]);
+    o[1] = w9_const_limb(fe_from_lazy_limbs<M>(c.l).l, tid & 15);
+  } else if constexpr (OP == 8) {
+    w9_mimc7_round<2>(w9_const_limb(x, rl), w9_modulus_limb<M>(rl), row1, o[0], o[1], o[2], o[3], o[4]);
+  } else {
+    const Fr h = w9_mimc7_hash2<2>(consts9, w9_raw_fe<FrParams>(x), w9_raw_fe<FrParams>(x + 9), tid);
+    o[0] = w9_const_limb(h.l, tid & 15);
+  }
+#pragma unroll
+  for (int s = 0; s < W9_OUTS; s++) out[(i * W9_OUTS + s) * 64 + tid] = o[s];
+}
+
+typedef void (*W9RawLaunch)(hipStream_t, const uint32_t*, size_t, uint32_t*, const uint32_t*);
+
+template <class M, int OP>
+void w9_raw_launch(hipStream_t st, const uint32_t* in, size_t n, uint32_t* out, const uint32_t* consts9) {
+  hipLaunchKernelGGL((k_w9_raw<M, OP>), dim3((unsigned)n), dim3(64), 0, st, in, n, out, consts9);
+}
+
+template <class M, int OP>
+constexpr W9RawLaunch w9_raw_pick() {
+  if constexpr (w9_raw_valid<M>(OP)) return &w9_raw_launch<M, OP>;
+  else return nullptr;
+}
+
+template <class M, int... OPS>
+W9RawLaunch w9_raw_lookup(int op, std::integer_sequence<int, OPS...>) {
+  static const W9RawLaunch table[W9_NOPS] = {w9_raw_pick<M, OPS>()...};
+  return op >= 0 && op < W9_NOPS ? table[op] : nullptr;
+}
+
+// og_hook_w9_ec_chain_d: one WAVE per chain of w9_xyzz_dbl / w9_xyzz_add (ec_w9.hip.h), nothing in between.  acc: n x 4 x 9 limbs
+// (x, y, zz, zzz as the wave holds them: raw, spread); steps: n x n_steps records of 1 + 4 x 9 words -- kind 0: doubling; 1: addition
+// of the operand in the record; 2: acc = the operand (the walk's first non-zero digit); 3: the kernel's exit (a strict product by
+// one per coordinate, w9_collect, fe_from_lazy_limbs), the result spread again; 4: nothing (padding of a cut chain).
+// out: n x 4 words x 64 lanes.
+constexpr int W9_CHAIN_REC = 1 + 4 * 9;
+
+__global__ void __launch_bounds__(64) k_w9_ec_chain(const uint32_t* __restrict__ acc_in, const uint32_t* __restrict__ steps, size_t n,
+                                                   uint32_t n_steps, uint32_t* __restrict__ out) {
+  const size_t i = blockIdx.x;
+  if (i >= n) return;
+  const int lane = threadIdx.x;
+  const uint32_t nj = w9_modulus_limb<FqParams>(lane);
+  const uint32_t* a = acc_in + i * 36;
+  W9Pt acc = {w9_const_limb(a, lane), w9_const_limb(a + 9, lane), w9_const_limb(a + 18, lane), w9_const_limb(a + 27, lane)};
+#pragma unroll 1
+  for (uint32_t s = 0; s < n_steps; s++) {  // one inlined site per primitive; the kind is wave-uniform
+    const uint32_t* rec = steps + (i * n_steps + s) * W9_CHAIN_REC;
+    const uint32_t kind = rec[0];
+    const W9Pt e = {w9_const_limb(rec + 1, lane), w9_const_limb(rec + 10, lane), w9_const_limb(rec + 19, lane), w9_const_limb(rec + 28, lane)};
+    if (kind == 0) acc = w9_xyzz_dbl(acc, nj, lane);
+    else if (kind == 1) acc = w9_xyzz_add(acc, e, nj, lane);
+    else if (kind == 2) acc = e;
+    else if (kind == 3) {
+      const U9 one = w9_uniform(FqParams::ONE);
+      const Fq ox = w9_collect<FqParams>(w9q_mul(one, acc.x, nj)), oy = w9_collect<FqParams>(w9q_mul(one, acc.y, nj));
+      const Fq ozz = w9_collect<FqParams>(w9q_mul(one, acc.zz, nj)), ozzz = w9_collect<FqParams>(w9q_mul(one, acc.zzz, nj));
+      acc = {w9_spread(fe_from_lazy_limbs<FqParams>(ox.l), lane), w9_spread(fe_from_lazy_limbs<FqParams>(oy.l), lane),
+             w9_spread(fe_from_lazy_limbs<FqParams>(ozz.l), lane), w9_spread(fe_from_lazy_limbs<FqParams>(ozzz.l), lane)};
+    }
+  }
+  uint32_t* o = out + i * 4 * 64;
+  o[lane] = acc.x;
+  o[64 + lane] = acc.y;
+  o[128 + lane] = acc.zz;
+  o[192 + lane] = acc.zzz;
+}
+
+}  // namespace og
+
+extern "C" int og_hook_w9_raw_d(og_ctx* ctx, int field, int op, const uint32_t* operands_d, size_t n, uint32_t* out_d) {
+  using namespace og;
+  return guarded([&]() -> int {
+    OG_REQUIRE(ctx && operands_d && out_d && n >= 1 && n <= ((size_t)1 << 20) && (field == 0 || field == 1), "og_hook_w9_raw_d: bad argument");
+    const W9RawLaunch f = field == 0 ? w9_raw_lookup<FrParams>(op, std::make_integer_sequence<int, W9_NOPS>{})
+                                     : w9_raw_lookup<FqParams>(op, std::make_integer_sequence<int, W9_NOPS>{});
+    OG_REQUIRE(f != nullptr, "og_hook_w9_raw_d: no such op in this field");
+    OG_REQUIRE(ctx->mimc_consts9_d != nullptr, "og_hook_w9_raw_d: the context has no round constants");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    OG_HIP(hipSetDevice(ctx->device));
+    f(ctx->stream, operands_d, n, out_d, (const uint32_t*)ctx->mimc_consts9_d);
+    OG_HIP(hipGetLastError());
+    OG_HIP(hipStreamSynchronize(ctx->stream));
+    return OG_OK;
+  });
+}
+
+extern "C" int og_hook_w9_ec_chain_d(og_ctx* ctx, const uint32_t* acc_d, const uint32_t* steps_d, size_t n, uint32_t n_steps, uint32_t* out_d) {
+  using namespace og;
+  return guarded([&]() -> int {
+    OG_REQUIRE(ctx && acc_d && steps_d && out_d && n >= 1 && n <= ((size_t)1 << 16) && n_steps <= (1u << 16), "og_hook_w9_ec_chain_d: bad argument");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    OG_HIP(hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(k_w9_ec_chain, dim3((unsigned)n), dim3(64), 0, ctx->stream, acc_d, steps_d, n, n_steps, out_d);
+    OG_HIP(hipGetLastError());
+    OG_HIP(hipStreamSynchronize(ctx->stream));
+    return OG_OK;
+  });
+}
 #endif  // OG_AB_HOOKS

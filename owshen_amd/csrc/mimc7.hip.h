@@ -108,8 +108,12 @@ __device__ __forceinline__ Fr mimc7_hash2(const uint32_t* __restrict__ consts, c
 // FORM 0: one row, four products deep (as first built); 1: two rows, three deep; 2: two rows and the 32-bit Montgomery digit
 // (field_w9.hip.h LAZY) -- what the launches use; 0 and 1 exist in hooks builds (OG_W9_ROWS).  Bounds with FORM 2, in multiples of
 // N: a product is below a b / 169 + 8.01; inputs x < 8.5 (an earlier round) or < 2 (a hash input), k < 10.5 (k1 = l + x with l < 2: every
-// hash output passes the strict product of w9_renorm / w9_mimc7_hash2's `red`), c < 2: t < 21, t^2 < 10.5, t^3 < 9.3, t^4 < 8.7,
-// t^6 < 8.6, t^7 < 8.5 -- all below 2^258, limbs < 2^31 + 2^9 going in (a_i b_j + m' N_j + carry < 2^62.6).
+// hash output passes the strict product of w9_renorm / w9_mimc7_hash2's `red`), c < 2: t < 21, and from that alone
+//   t^2 < 441 / 169 + 8.01 < 10.7;  t^3 < 10.7 x 21 / 169 + 8.01 < 9.4;  t^4 < 10.7^2 / 169 + 8.01 < 8.7;  t^6 < 8.7 x 10.7 / 169 + 8.01
+//   < 8.6;  t^7 < 8.7 x 9.4 / 169 + 8.01 < 8.5, which closes the loop (x < 8.5)
+// (the exact model of tests/w9_raw_cases.py reaches t^2 = 10.58 at t = 21 N - 1: "t^2 < 10.5", which this table used to say, holds
+// only for t < 20) -- all below 2^258, limbs < 2^31 + 2^9 going in (a_i b_j + m' N_j + carry < 2^62.6: no 64-bit accumulator overflows,
+// which the model asserts step by step).
 // With rows (FORM >= 1) t4 / t6 are what the two rows hold after the second / third product -- row 0: t^4, t^6; row 1: t^3, t^7 --
 // and t6r0 is t^6 in BOTH rows (the other half of the swap that hands t^7 to both): the witness walk stores two wires per row from them.
 template <int FORM>
@@ -132,7 +136,8 @@ __device__ __forceinline__ void w9_mimc7_round(uint32_t t, uint32_t nj, bool row
     x = w9_mul<FrParams>(ta, t6, nj);
   }
 }
-// E_k(x) without the final + k; x, k spread (limbs < 2^31; x < 2 N, k < 4 N).  The next round's constant is asked for a round ahead:
+// E_k(x) without the final + k; x, k spread (limbs < 2^31; x < 2 N, k < 4 N with the strict products of forms 0 and 1, k < 10.5 N with
+// form 2: the table above; the result is below 2 N | 8.5 N).  The next round's constant is asked for a round ahead:
 // on a lone wave a load that is waited for where it is issued costs its whole latency, every round.
 template <int FORM>
 __device__ __forceinline__ uint32_t w9_mimc7_rounds(const uint32_t* __restrict__ consts9, uint32_t x, uint32_t k, uint32_t nj, int lane, bool row1) {
@@ -154,9 +159,9 @@ __device__ __forceinline__ Fr w9_mimc7_hash2(const uint32_t* __restrict__ consts
   const bool row1 = (tid & 16) != 0;
   const uint32_t nj = w9_modulus_limb<FrParams>(lane);
   const uint32_t ls = w9_spread(l, lane), rs = w9_spread(r, lane);
-  const uint32_t k1 = ls + w9_mimc7_rounds<FORM>(consts9, ls, 0u, nj, lane, row1);                 // l + E_0(l): < 4 N
-  const uint32_t out = 2u * k1 + rs + w9_mimc7_rounds<FORM>(consts9, rs, k1, nj, lane, row1);      // 2 k1 + r + x_91: < 12 N, limbs < 2^32
-  const uint32_t red = w9_mul<FrParams>(w9_uniform(FrParams::ONE), w9_carry(out, lane), nj);   // the same value below 2 N
+  const uint32_t k1 = ls + w9_mimc7_rounds<FORM>(consts9, ls, 0u, nj, lane, row1);                 // l + E_0(l): < 4 N (form 2: < 10.5 N)
+  const uint32_t out = 2u * k1 + rs + w9_mimc7_rounds<FORM>(consts9, rs, k1, nj, lane, row1);      // 2 k1 + r + x_91: < 12 N (form 2: < 31.5 N), limbs < 2^31 + 2^30 + 96
+  const uint32_t red = w9_mul<FrParams>(w9_uniform(FrParams::ONE), w9_carry(out, lane), nj);   // the same value below 2 N (a strict product: 31.5 N x ONE < 169 N^2)
   const Fr lazy = w9_collect<FrParams>(red);
   return fe_from_lazy_limbs<FrParams>(lazy.l);  // normalized limbs, < 2 N (v or v + N: callers take it out of Montgomery form, which is unique)
 }

@@ -453,7 +453,7 @@ __global__ void __launch_bounds__(64) k_w9_first(const uint32_t* __restrict__ co
   if (job >= 2) w9_store(wl, wbase - 1, l_in, tid);  // the level's `left` selector wire: the sibling
   uint32_t* dump = xch + (size_t)(depth + 4) * 9;
   const uint32_t k1 = l_in + (dup ? w9_permute<FORM, true>(consts9, l_in, 0u, nj, tid, lane, wl, wbase, dup, dump)
-                                  : w9_permute<FORM, false>(consts9, l_in, 0u, nj, tid, lane, wl, wbase, 0u, dump));  // l + E_0(l): < 4 N, lazy limbs
+                                  : w9_permute<FORM, false>(consts9, l_in, 0u, nj, tid, lane, wl, wbase, 0u, dump));  // l + E_0(l): < 4 N (form 2: < 10.5 N, mimc7.hip.h), lazy limbs
   w9_store(wl, wbase + 364, k1, tid);
   if (dup) w9_store(wl, dup + 364, k1, tid);
   if (tid < 9) xch[(size_t)slot * 9 + lane] = k1;
@@ -1494,7 +1494,7 @@ __device__ __forceinline__ void w9_note_chain(const uint32_t* __restrict__ const
 }
 
 // the first permutation of a gadget whose left input is known before the walk (k_tw9_first, k_sw9_first, k_jw9_first): k1 = l + E_0(l)
-// (< 4 N, lazy limbs) with its round wires at wbase (and at dup, if non-zero: a nullifier's, which is the left input of two gadgets),
+// (< 4 N; form 2: < 10.5 N; lazy limbs) with its round wires at wbase (and at dup, if non-zero: a nullifier's, which is the left input of two gadgets),
 // k1 into xch slot `slot`; selector: l is a level's sibling, which is also that level's `left` wire
 template <int FORM>
 __device__ __forceinline__ void w9_first_half(const uint32_t* __restrict__ consts9, const Fr& l_fe, uint32_t nj, int tid, int lane,

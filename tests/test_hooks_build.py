@@ -39,7 +39,7 @@ def test_hooks_library_has_the_switches_and_the_same_abi():
     assert set(_lib.SIGNATURES) == set(_header_symbols())
     # the test seams exist in the hooks build only: the shipped library's exported set is the header's and nothing else
     shipped = C.CDLL(os.path.join(PKG, "libowshen_gpu.so"))
-    for seam in ("og_hook_verify_miller_d", "og_hook_final_exp_d", "og_hook_fe_raw_d"):
+    for seam in ("og_hook_verify_miller_d", "og_hook_final_exp_d", "og_hook_fe_raw_d", "og_hook_ec_chain_d", "og_hook_w9_raw_d", "og_hook_w9_ec_chain_d"):
         assert hasattr(lib, seam), f"{seam} missing from the hooks build"
         assert not hasattr(shipped, seam), f"{seam} is in the shipped library"
 
