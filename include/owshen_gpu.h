@@ -125,9 +125,36 @@ int og_mimc7_append_d(og_ctx* ctx, int depth, const uint8_t* frontier_in_d, uint
  * The reference's `PointCompressed::verify` (/root/reference/src/blockchain/tx/owshen_airdrop/babyjubjub/mod.rs:99-115)
  * with its placeholder product hash (:202-204) replaced by MultiMiMC7: accepts iff pk and R lie on the curve and
  *   s * BASE == R + h * pk,   h = MultiMiMC7([R.x, R.y, pk.x, pk.y, message], key 0).
- * records_d: n records of 6 x 32 B canonical LE: pk.x | pk.y | R.x | R.y | s | message (public keys affine: decompression,
- * mod.rs:88-98, stays on the host).  ok_out: HOST, n x u32 (1 accept / 0 reject; a non-canonical field element rejects). */
+ * records_d: n records of 6 x 32 B canonical LE: pk.x | pk.y | R.x | R.y | s | message (public keys affine; for compressed
+ * keys, mod.rs:88-98, see og_eddsa_verify_compressed_batch_d below).  ok_out: HOST, n x u32 (1 accept / 0 reject; a
+ * non-canonical field element rejects). */
 int og_eddsa_verify_batch_d(og_ctx* ctx, const uint8_t* records_d, size_t n, uint32_t* ok_out);
+
+/* ---- airdrop keys: compressed keys, key derivation and signing on the GPU -------------------------------------------
+ * The rest of the reference's BabyJubJub surface: `PrivateKey::to_pub` (mod.rs:207-209), `PrivateKey::sign` (:210-236, hash :=
+ * MultiMiMC7 as above) and the decompression inside `PointCompressed::verify` (:88-98).  One item per lane; device pointers in,
+ * ok_out a HOST array of n x u32; n = 0 is OG_OK; a null handle or pointer is OG_ERR_INVALID before the device is touched.
+ *
+ * Compressed key, 32 B: x canonical LE with the parity of y (`is_odd` of the canonical integer, mod.rs:82-84) in bit 255
+ * (0x80 of byte 31).  Bit 254 must be clear and x < r, otherwise the key is refused.  The reference's `PointCompressed(Fp, bool)`
+ * has no packed form: this one is this library's (it is NOT circomlib's packing, which stores y with the sign of x).
+ *
+ * og_eddsa_pubkey_batch_d: pk = sk * BASE as x | y (pk_out_d, n x 64 B) and / or compressed (pkc_out_d, n x 32 B); either output
+ *   may be NULL.  ok = 0 and zeroed outputs for a non-canonical sk; sk = 0 and sk = l (the order of BASE) give the identity (0, 1).
+ * og_eddsa_decompress_batch_d: y = sqrt((1 - a x^2) / (1 - d x^2)), negated when its parity differs from the flag; y = 0 is
+ *   returned for either flag.  ok = 0 and 64 zero bytes when the encoding is refused or the value has no square root (the
+ *   reference's "Cannot take sqrt": about half of all x).
+ * og_eddsa_sign_batch_d: requests of 3 x 32 B: sk | randomness | message.  r = MultiMiMC7([randomness, message]), R = r * BASE,
+ *   pk = sk * BASE, h = MultiMiMC7([R.x, R.y, pk.x, pk.y, message]), s = (r + h * sk) mod ORDER (ORDER = 8 l).  records_out_d:
+ *   n complete records of og_eddsa_verify_batch_d (6 x 32 B), so signing and verification chain on the device.  ok = 0 and a
+ *   zeroed record for a non-canonical input, and when s >= r (the reference's "Invalid repr").
+ * og_eddsa_verify_compressed_batch_d: records of 5 x 32 B: compressed pk | R.x | R.y | s | message.  ok = 1 iff the key
+ *   decompresses and og_eddsa_verify_batch_d accepts the record with the decompressed key; everything else is 0 (where the
+ *   reference returns Err: a refused encoding, a key without a square root, a non-canonical field). */
+int og_eddsa_pubkey_batch_d(og_ctx* ctx, const uint8_t* sk_d, size_t n, uint8_t* pk_out_d, uint8_t* pkc_out_d, uint32_t* ok_out);
+int og_eddsa_decompress_batch_d(og_ctx* ctx, const uint8_t* pkc_d, size_t n, uint8_t* pk_out_d, uint32_t* ok_out);
+int og_eddsa_sign_batch_d(og_ctx* ctx, const uint8_t* requests_d, size_t n, uint8_t* records_out_d, uint32_t* ok_out);
+int og_eddsa_verify_compressed_batch_d(og_ctx* ctx, const uint8_t* records_d, size_t n, uint32_t* ok_out);
 
 /* ---- N4: radix-2 Fr NTT (domain generator 7^((r-1)/n), coset generator 7) ------
  * batch transforms of size n = 2^log_n, natural order in and out, canonical bytes.

@@ -212,6 +212,42 @@ class Context:
         self._check(self._lib.og_eddsa_verify_batch_d(self._h, self.ptr(records), n, out.ctypes.data_as(C.c_void_p)))
         return out
 
+    def eddsa_pubkey(self, sks, affine=True, compressed=True):
+        """sks: device uint8 [n, 32] -> (pk device [n, 64] x | y or None, pkc device [n, 32] or None, np.uint32 [n] (0 = refused))"""
+        self._pre()
+        n = sks.shape[0]
+        pk = self.empty(n, 64) if affine else None
+        pkc = self.empty(n, 32) if compressed else None
+        ok = np.zeros(n, dtype=np.uint32)
+        self._check(self._lib.og_eddsa_pubkey_batch_d(self._h, self.ptr(sks), n, self.ptr(pk), self.ptr(pkc), ok.ctypes.data_as(C.c_void_p)))
+        return pk, pkc, ok
+
+    def eddsa_decompress(self, pkcs):
+        """pkcs: device uint8 [n, 32] (x, the parity of y in bit 255) -> (device [n, 64] x | y, np.uint32 [n] (0 = refused or no root))"""
+        self._pre()
+        n = pkcs.shape[0]
+        pk = self.empty(n, 64)
+        ok = np.zeros(n, dtype=np.uint32)
+        self._check(self._lib.og_eddsa_decompress_batch_d(self._h, self.ptr(pkcs), n, self.ptr(pk), ok.ctypes.data_as(C.c_void_p)))
+        return pk, ok
+
+    def eddsa_sign(self, requests):
+        """requests: device uint8 [n, 3, 32] (sk | randomness | message) -> (device [n, 6, 32] records of eddsa_verify, np.uint32 [n])"""
+        self._pre()
+        n = requests.shape[0]
+        recs = self.empty(n, 6, 32)
+        ok = np.zeros(n, dtype=np.uint32)
+        self._check(self._lib.og_eddsa_sign_batch_d(self._h, self.ptr(requests), n, self.ptr(recs), ok.ctypes.data_as(C.c_void_p)))
+        return recs, ok
+
+    def eddsa_verify_compressed(self, records):
+        """records: device uint8 [n, 5, 32] (compressed pk | R.x | R.y | s | message) -> np.uint32 [n] (1 = accept)"""
+        self._pre()
+        n = records.shape[0]
+        out = np.zeros(n, dtype=np.uint32)
+        self._check(self._lib.og_eddsa_verify_compressed_batch_d(self._h, self.ptr(records), n, out.ctypes.data_as(C.c_void_p)))
+        return out
+
     # -- N4 NTT --
     def ntt(self, data, inverse=False, coset=False):
         """data: device uint8 [n,32] or [batch,n,32] canonical -> same shape."""

@@ -904,6 +904,71 @@ int og_eddsa_verify_batch_d(og_ctx* ctx, const uint8_t* records_d, size_t n, uin
   });
 }
 
+// the decisions of a batched EdDSA call: out of their arena entry into the caller's host array
+static int eddsa_ok_out(og_ctx* ctx, const uint32_t* ok_d, size_t n, uint32_t* ok_out) {
+  OG_HIP(hipMemcpyAsync(ok_out, ok_d, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+  OG_HIP(hipStreamSynchronize(ctx->stream));
+  return OG_OK;
+}
+
+int og_eddsa_pubkey_batch_d(og_ctx* ctx, const uint8_t* sk_d, size_t n, uint8_t* pk_out_d, uint8_t* pkc_out_d, uint32_t* ok_out) {
+  return guarded([&]() -> int {
+    CTX_OK(ctx);
+    OG_REQUIRE(n == 0 || (sk_d && ok_out), "og_eddsa_pubkey_batch_d: null argument");
+    if (n == 0) return OG_OK;
+    LOCKED(ctx);
+    uint32_t* ok_d = nullptr;
+    OG_TRY(arena_get(ctx, "eddsa.ok", n * 4, (void**)&ok_d));
+    OG_TRY(eddsa_pubkey(ctx, sk_d, n, pk_out_d, pkc_out_d, ok_d));
+    return eddsa_ok_out(ctx, ok_d, n, ok_out);
+  });
+}
+
+int og_eddsa_decompress_batch_d(og_ctx* ctx, const uint8_t* pkc_d, size_t n, uint8_t* pk_out_d, uint32_t* ok_out) {
+  return guarded([&]() -> int {
+    CTX_OK(ctx);
+    OG_REQUIRE(n == 0 || (pkc_d && pk_out_d && ok_out), "og_eddsa_decompress_batch_d: null argument");
+    if (n == 0) return OG_OK;
+    LOCKED(ctx);
+    uint32_t* ok_d = nullptr;
+    OG_TRY(arena_get(ctx, "eddsa.ok", n * 4, (void**)&ok_d));
+    OG_TRY(eddsa_decompress(ctx, pkc_d, 32, n, pk_out_d, 64, ok_d));
+    return eddsa_ok_out(ctx, ok_d, n, ok_out);
+  });
+}
+
+int og_eddsa_sign_batch_d(og_ctx* ctx, const uint8_t* requests_d, size_t n, uint8_t* records_out_d, uint32_t* ok_out) {
+  return guarded([&]() -> int {
+    CTX_OK(ctx);
+    OG_REQUIRE(n == 0 || (requests_d && records_out_d && ok_out), "og_eddsa_sign_batch_d: null argument");
+    if (n == 0) return OG_OK;
+    LOCKED(ctx);
+    uint32_t* ok_d = nullptr;
+    OG_TRY(arena_get(ctx, "eddsa.ok", n * 4, (void**)&ok_d));
+    OG_TRY(eddsa_sign(ctx, requests_d, n, records_out_d, ok_d));
+    return eddsa_ok_out(ctx, ok_d, n, ok_out);
+  });
+}
+
+int og_eddsa_verify_compressed_batch_d(og_ctx* ctx, const uint8_t* records_d, size_t n, uint32_t* ok_out) {
+  return guarded([&]() -> int {
+    CTX_OK(ctx);
+    OG_REQUIRE(n == 0 || (records_d && ok_out), "og_eddsa_verify_compressed_batch_d: null argument");
+    if (n == 0) return OG_OK;
+    LOCKED(ctx);
+    // the records widened to the affine form (a key that does not decompress becomes (0, 0), which is not on the curve: the
+    // verification kernel, unchanged, rejects it), then og_eddsa_verify_batch_d's own kernel
+    uint32_t *ok_d = nullptr, *dec_ok_d = nullptr;
+    uint8_t* wide_d = nullptr;
+    OG_TRY(arena_get(ctx, "eddsa.ok", n * 4, (void**)&ok_d));
+    OG_TRY(arena_get(ctx, "eddsa.dec_ok", n * 4, (void**)&dec_ok_d));
+    OG_TRY(arena_get(ctx, "eddsa.wide", n * 192, (void**)&wide_d));
+    OG_TRY(eddsa_decompress(ctx, records_d, 160, n, wide_d, 192, dec_ok_d));
+    OG_TRY(eddsa_verify(ctx, wide_d, n, ok_d));
+    return eddsa_ok_out(ctx, ok_d, n, ok_out);
+  });
+}
+
 int og_vk_load(og_ctx* ctx, const uint8_t* vk, size_t vk_len, og_vk** out) {
   return guarded([&]() -> int {
     CTX_OK(ctx);

@@ -63,6 +63,8 @@ struct og_ctx {
   uint8_t fb_base[2][128] = {};                 // scalar_mul_fixed: the G1 / G2 point (canonical bytes) whose 64 x 16 fixed-base table
   uint8_t* fb_tab[2] = {nullptr, nullptr};      //   fb_tab holds (device, in `owned`; not arena scratch, which is per lane): key
   bool fb_valid[2] = {false, false};            //   generation multiplies the same generator once per query
+  uint8_t* ed_tab_d = nullptr;                  // eddsa_keys.hip: 64 x 16 affine multiples d 16^j BASE of BabyJubJub's base point (device, in `owned`;
+                                                //   Montgomery form, 64 KiB), built by the first call that multiplies BASE
   std::vector<struct og_job*> done_jobs;        // jobs that completed inside the submit call (small circuits): live handles
                                                 // og_job_wait / og_job_abandon still have to see
   bool last_call_piped = false;        // the previous call went through the stage pipeline (its scratch is guarded by slot events)

@@ -1,5 +1,5 @@
 // What the leaf units offer to the entry points (capi.hip): the MiMC7 hash and tree (mimc7.hip), the field operations (field_ops.hip),
-// the micro-benchmarks (ubench.hip) and EdDSA verification (eddsa.hip).
+// the micro-benchmarks (ubench.hip), EdDSA verification (eddsa.hip) and EdDSA keys and signing (eddsa_keys.hip).
 #pragma once
 #include "ctx.h"
 
@@ -29,5 +29,13 @@ int ubench_coresidency(og_ctx* ctx, int wgs_per_cu, int kind, int iters, int fil
 
 // ---- eddsa.hip ----------------------------------------------------------------------------------------------------------------------
 int eddsa_verify(og_ctx* ctx, const uint8_t* recs_d, size_t n, uint32_t* ok_d);
+
+// ---- eddsa_keys.hip -----------------------------------------------------------------------------------------------------------------
+// pk_d (n x 64) and pkc_d (n x 32) may each be null
+int eddsa_pubkey(og_ctx* ctx, const uint8_t* sk_d, size_t n, uint8_t* pk_d, uint8_t* pkc_d, uint32_t* ok_d);
+// item i: the compressed key at in_d + i in_stride -> x | y at out_d + i out_stride, followed by a copy of the in_stride - 32 bytes
+// behind the key (og_eddsa_verify_compressed_batch_d widens its 160-byte records to the 192 bytes eddsa_verify reads)
+int eddsa_decompress(og_ctx* ctx, const uint8_t* in_d, size_t in_stride, size_t n, uint8_t* out_d, size_t out_stride, uint32_t* ok_d);
+int eddsa_sign(og_ctx* ctx, const uint8_t* requests_d, size_t n, uint8_t* records_d, uint32_t* ok_d);
 
 }  // namespace og
