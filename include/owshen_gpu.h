@@ -156,6 +156,34 @@ int og_eddsa_decompress_batch_d(og_ctx* ctx, const uint8_t* pkc_d, size_t n, uin
 int og_eddsa_sign_batch_d(og_ctx* ctx, const uint8_t* requests_d, size_t n, uint8_t* records_out_d, uint32_t* ok_out);
 int og_eddsa_verify_compressed_batch_d(og_ctx* ctx, const uint8_t* records_d, size_t n, uint32_t* ok_out);
 
+/* ---- stealth notes: seal a note to a public key, scan the pool's memos on the GPU ------------------------------------
+ * What connects the keys above to the pool's statements: a sender pays a payee it knows only by its public key, with no round
+ * trip, and the payee's wallet finds and opens its notes by scanning every memo the pool has published.  With H = MultiMiMC7
+ * 2-to-1 (key 0), BASE and `multiply` as in the reference's babyjubjub/mod.rs (:68-78, :177-188), l the order of BASE, and
+ * small(P) <=> 8 P = (0, 1):
+ *   keys    sk: any canonical Fr element; pk = sk * BASE (og_eddsa_pubkey_batch_d).
+ *   KDF     from a shared point S (affine): k = H(S.x, S.y); tag = H(k, 1); nullifier' = H(k, 2); secret' = H(k, 3);
+ *           pad_a = H(k, 4); pad_t = H(k, 5).
+ *   seal    request, 5 x 32 B: e | pk.x | pk.y | amount | token.  E = e * BASE, S = e * pk, c' = H(nullifier', secret'),
+ *           leaf = H(c', H(amount, token)) -- the leaf shape of every statement.
+ *           memo, 5 x 32 B: E.x | E.y | tag | amount + pad_a mod r | token + pad_t mod r  (what a ledger publishes beside the leaf);
+ *           note, 2 x 32 B: c' | leaf  (c' is the `pay_commitment` of og_transfer_prove_batch_d, leaf its `pay_leaf`).
+ *           Refused (ok = 0, memo and note zeroed): a field >= r, amount >= 2^128, pk off the curve, small(pk), small(E)
+ *           (that is, e = 0 mod l).
+ *   scan    per memo S = sk * E, then the KDF.  hit = 0: a field >= r, E off the curve, small(E), or another tag -- memos come from
+ *           anybody, so a malformed memo is never an error of the call; hit = 2: the tag is this key's and the memo does not
+ *           open (the decrypted amount is >= 2^128, or leaves were given and the recomputed leaf differs): hostile or broken,
+ *           to be ignored; hit = 1: the payee's, opened as nullifier' | secret' | amount | token (4 x 32 B) -- what a withdraw /
+ *           split / join / transfer record of the leaf's index spends.  small(E) is refused because E = (0, 1) would give every
+ *           wallet the same S.  sk is NOT reduced mod l: E may carry torsion, and S is `multiply` on the integer sk < r.
+ * Every field 32 B little-endian canonical.  Device pointers in; ok_out / hit_out are HOST arrays of n x u32; n = 0 is OG_OK with no
+ * pointer needed; a null handle or required pointer is OG_ERR_INVALID before the device is touched.
+ * og_note_scan_batch_d: sk is a HOST pointer (OG_ERR_INVALID for sk >= r); leaves_d (n x 32 B, the published leaf beside each memo)
+ *   and opened_out_d (n x 4 x 32 B) may each be NULL; rows of opened_out_d are zero unless the hit is 1.  The scalar is the same
+ *   for all n memos: it is recoded once on the host and neither sk nor its digits stay in the context after the call. */
+int og_note_seal_batch_d(og_ctx* ctx, const uint8_t* requests_d, size_t n, uint8_t* memos_out_d, uint8_t* notes_out_d, uint32_t* ok_out);
+int og_note_scan_batch_d(og_ctx* ctx, const uint8_t sk[32], const uint8_t* memos_d, const uint8_t* leaves_d, size_t n, uint8_t* opened_out_d, uint32_t* hit_out);
+
 /* ---- N4: radix-2 Fr NTT (domain generator 7^((r-1)/n), coset generator 7) ------
  * batch transforms of size n = 2^log_n, natural order in and out, canonical bytes.
  *   inverse = 0, coset = 0 : out[i] = sum_j in[j] w^(ij)

@@ -43,4 +43,52 @@ __device__ __forceinline__ bool canonical_fr(const uint8_t* p) {  // value < r
   return c != 0;  // borrow out: v < N
 }
 
+// ---- k * BASE from the window table (built by eddsa_keys.hip k_ed_table, handed out by eddsa_base_table: primitives.h) -------------
+constexpr int ED_TAB_WINDOWS = 64, ED_TAB_DIGITS = 16;  // 4-bit windows over 256 bits: scalars range over all of Fr, not only [0, l)
+constexpr size_t ED_TAB_BYTES = (size_t)ED_TAB_WINDOWS * ED_TAB_DIGITS * 64;
+
+
+__device__ __forceinline__ EdPoint ed_identity() {
+  EdPoint o;
+  o.x = Fr::zero();
+  o.y = Fr::one();
+  o.z = Fr::one();
+  return o;
+}
+
+// p0 = k0 BASE and, with TWO, p1 = k1 BASE (the scalars as 8 words each: integers, any value below 2^256), projective.  One rolled
+// loop around one addition site; 64 additions per product, the table entry gathered per lane (the table is 64 KiB: it stays in L2).
+template <bool TWO>
+__device__ __forceinline__ void ed_mul_base(const uint8_t* __restrict__ tab, const uint32_t w0[8], const uint32_t w1[8], EdPoint& p0, EdPoint& p1,
+                                            const Fr& ca, const Fr& cd) {
+  EdPoint acc = ed_identity();
+#pragma unroll 1
+  for (int step = 0; step < (TWO ? 2 : 1) * ED_TAB_WINDOWS; step++) {
+    const int j = step & (ED_TAB_WINDOWS - 1);
+    const bool second = TWO && step >= ED_TAB_WINDOWS;
+    if (TWO && step == ED_TAB_WINDOWS) {
+      p0 = acc;
+      acc = ed_identity();
+    }
+    uint32_t word = 0;
+#pragma unroll
+    for (int k = 0; k < 8; k++) word = k == (j >> 3) ? (second ? w1[k] : w0[k]) : word;
+    const uint32_t d = (word >> (4 * (j & 7))) & 15u;
+    const uint8_t* e = tab + (size_t)(j * ED_TAB_DIGITS + (int)d) * 64;
+    EdPoint q;
+    q.x = fe_load<FrParams>(e);
+    q.y = fe_load<FrParams>(e + 32);
+    q.z = Fr::one();
+    acc = ed_add(acc, q, ca, cd);
+  }
+  if (TWO) p1 = acc;
+  else p0 = acc;
+}
+
+__device__ __forceinline__ void store_zeros(uint8_t* p, int n16) {
+  uint4* q = reinterpret_cast<uint4*>(p);
+  for (int k = 0; k < n16; k++) q[k] = make_uint4(0u, 0u, 0u, 0u);
+}
+
+
 }  // namespace og

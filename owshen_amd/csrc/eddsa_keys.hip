@@ -111,11 +111,6 @@ __device__ __forceinline__ void ed_store_compressed(uint8_t* p, const Fr& x, con
   q[1] = make_uint4(w[4], w[5], w[6], w[7] | ((y.l[0] & 1u) << 31));
 }
 
-__device__ __forceinline__ void store_zeros(uint8_t* p, int n16) {
-  uint4* q = reinterpret_cast<uint4*>(p);
-  for (int k = 0; k < n16; k++) q[k] = make_uint4(0u, 0u, 0u, 0u);
-}
-
 __global__ void __launch_bounds__(64) k_eddsa_decompress(const uint8_t* __restrict__ in, size_t in_stride, size_t n, uint8_t* __restrict__ out,
                                                         size_t out_stride, uint32_t* __restrict__ ok) {
   const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -136,9 +131,6 @@ __global__ void __launch_bounds__(64) k_eddsa_decompress(const uint8_t* __restri
 }
 
 // ---- k * BASE from the window table ------------------------------------------------------------------------------------------------
-constexpr int ED_TAB_WINDOWS = 64, ED_TAB_DIGITS = 16;  // 4-bit windows over 256 bits: scalars range over all of Fr, not only [0, l)
-constexpr size_t ED_TAB_BYTES = (size_t)ED_TAB_WINDOWS * ED_TAB_DIGITS * 64;
-
 // tab[j][d] = d 16^j BASE, affine x | y in Montgomery form (d = 0: the identity (0, 1), so a zero digit is an addition like any
 // other).  Lane j: 4 j doublings of BASE, then the sixteen multiples, each brought to affine by its own inversion -- one wave, once
 // per context.  One addition site: steps below 4 j double p, the rest store acc and add p to it.
@@ -168,43 +160,6 @@ __global__ void __launch_bounds__(64) k_ed_table(uint8_t* __restrict__ tab) {
     if (dbl) p = sum;
     else acc = sum;
   }
-}
-
-__device__ __forceinline__ EdPoint ed_identity() {
-  EdPoint o;
-  o.x = Fr::zero();
-  o.y = Fr::one();
-  o.z = Fr::one();
-  return o;
-}
-
-// p0 = k0 BASE and, with TWO, p1 = k1 BASE (the scalars as 8 words each: integers, any value below 2^256), projective.  One rolled
-// loop around one addition site; 64 additions per product, the table entry gathered per lane (the table is 64 KiB: it stays in L2).
-template <bool TWO>
-__device__ __forceinline__ void ed_mul_base(const uint8_t* __restrict__ tab, const uint32_t w0[8], const uint32_t w1[8], EdPoint& p0, EdPoint& p1,
-                                            const Fr& ca, const Fr& cd) {
-  EdPoint acc = ed_identity();
-#pragma unroll 1
-  for (int step = 0; step < (TWO ? 2 : 1) * ED_TAB_WINDOWS; step++) {
-    const int j = step & (ED_TAB_WINDOWS - 1);
-    const bool second = TWO && step >= ED_TAB_WINDOWS;
-    if (TWO && step == ED_TAB_WINDOWS) {
-      p0 = acc;
-      acc = ed_identity();
-    }
-    uint32_t word = 0;
-#pragma unroll
-    for (int k = 0; k < 8; k++) word = k == (j >> 3) ? (second ? w1[k] : w0[k]) : word;
-    const uint32_t d = (word >> (4 * (j & 7))) & 15u;
-    const uint8_t* e = tab + (size_t)(j * ED_TAB_DIGITS + (int)d) * 64;
-    EdPoint q;
-    q.x = fe_load<FrParams>(e);
-    q.y = fe_load<FrParams>(e + 32);
-    q.z = Fr::one();
-    acc = ed_add(acc, q, ca, cd);
-  }
-  if (TWO) p1 = acc;
-  else p0 = acc;
 }
 
 __global__ void __launch_bounds__(64) k_eddsa_pubkey(const uint8_t* __restrict__ tab, const uint8_t* __restrict__ sks, size_t n, uint8_t* __restrict__ pk,
@@ -334,7 +289,7 @@ __global__ void __launch_bounds__(64) k_eddsa_sign(const uint32_t* __restrict__ 
 }
 
 // ---- launches --------------------------------------------------------------------------------------------------------------------
-static int ed_table(og_ctx* ctx, const uint8_t** tab) {
+int eddsa_base_table(og_ctx* ctx, const uint8_t** tab) {
   if (!ctx->ed_tab_d) {
     uint8_t* t = nullptr;
     OG_HIP(hipMalloc((void**)&t, ED_TAB_BYTES));
@@ -350,7 +305,7 @@ static int ed_table(og_ctx* ctx, const uint8_t** tab) {
 int eddsa_pubkey(og_ctx* ctx, const uint8_t* sk_d, size_t n, uint8_t* pk_d, uint8_t* pkc_d, uint32_t* ok_d) {
   if (n == 0) return OG_OK;
   const uint8_t* tab = nullptr;
-  OG_TRY(ed_table(ctx, &tab));
+  OG_TRY(eddsa_base_table(ctx, &tab));
   hipLaunchKernelGGL(k_eddsa_pubkey, dim3(grid_for(n, 64)), dim3(64), 0, ctx->stream, tab, sk_d, n, pk_d, pkc_d, ok_d);
   OG_HIP(hipGetLastError());
   return OG_OK;
@@ -367,7 +322,7 @@ int eddsa_decompress(og_ctx* ctx, const uint8_t* in_d, size_t in_stride, size_t 
 int eddsa_sign(og_ctx* ctx, const uint8_t* requests_d, size_t n, uint8_t* records_d, uint32_t* ok_d) {
   if (n == 0) return OG_OK;
   const uint8_t* tab = nullptr;
-  OG_TRY(ed_table(ctx, &tab));
+  OG_TRY(eddsa_base_table(ctx, &tab));
   hipLaunchKernelGGL(k_eddsa_sign, dim3(grid_for(n, 64)), dim3(64), 0, ctx->stream, (const uint32_t*)ctx->mimc_consts_d, tab, requests_d, n, records_d,
                      ok_d);
   OG_HIP(hipGetLastError());

@@ -1,5 +1,5 @@
 // What the leaf units offer to the entry points (capi.hip): the MiMC7 hash and tree (mimc7.hip), the field operations (field_ops.hip),
-// the micro-benchmarks (ubench.hip), EdDSA verification (eddsa.hip) and EdDSA keys and signing (eddsa_keys.hip).
+// the micro-benchmarks (ubench.hip), EdDSA verification (eddsa.hip), EdDSA keys and signing (eddsa_keys.hip) and stealth notes (notes.hip).
 #pragma once
 #include "ctx.h"
 
@@ -37,5 +37,14 @@ int eddsa_pubkey(og_ctx* ctx, const uint8_t* sk_d, size_t n, uint8_t* pk_d, uint
 // behind the key (og_eddsa_verify_compressed_batch_d widens its 160-byte records to the 192 bytes eddsa_verify reads)
 int eddsa_decompress(og_ctx* ctx, const uint8_t* in_d, size_t in_stride, size_t n, uint8_t* out_d, size_t out_stride, uint32_t* ok_d);
 int eddsa_sign(og_ctx* ctx, const uint8_t* requests_d, size_t n, uint8_t* records_d, uint32_t* ok_d);
+// the 64 x 16 window table of BASE that ed_mul_base (eddsa.hip.h) walks: built on the context's stream by the first call, kept in ctx
+int eddsa_base_table(og_ctx* ctx, const uint8_t** tab);
+
+// ---- notes.hip ----------------------------------------------------------------------------------------------------------------------
+// requests n x 160 B -> memos n x 160 B and notes n x 64 B
+int note_seal(og_ctx* ctx, const uint8_t* requests_d, size_t n, uint8_t* memos_d, uint8_t* notes_d, uint32_t* ok_d);
+bool note_sk_canonical(const uint8_t sk[32]);
+// sk: HOST, canonical (the caller has checked it); leaves_d (n x 32) and opened_d (n x 128) may each be null
+int note_scan(og_ctx* ctx, const uint8_t sk[32], const uint8_t* memos_d, const uint8_t* leaves_d, size_t n, uint8_t* opened_d, uint32_t* hit_d);
 
 }  // namespace og

@@ -10,7 +10,7 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "owshen_amd", "csrc")
-UNITS = ["msm_g1.hip", "msm_g2.hip", "msm.hip", "ntt.hip", "groth16.hip", "witness.hip", "mimc7.hip", "eddsa.hip", "eddsa_keys.hip", "keygen.hip", "field_ops.hip", "zkey.hip", "ptau.hip"]
+UNITS = ["msm_g1.hip", "msm_g2.hip", "msm.hip", "ntt.hip", "groth16.hip", "witness.hip", "mimc7.hip", "eddsa.hip", "eddsa_keys.hip", "notes.hip", "keygen.hip", "field_ops.hip", "zkey.hip", "ptau.hip"]
 
 
 def demangle(names):
