@@ -35,28 +35,30 @@ using namespace og;
   OG_HIP(hipSetDevice((ctx)->device))
 #define CTX_OK(ctx) OG_REQUIRE((ctx) != nullptr, "null og_ctx")
 
-// ---- the bodies behind og_<statement>_shape / _witness_d / _prove_batch_d of the record statements (statements.h) -------------------
-static int record_shape(const RecordStatement& st, int depth, uint64_t shape[3]) {
+// ---- the bodies behind og_<statement>_shape / _witness_d / _prove_batch_d (statements.h) ---------------------------------------------
+// Two entry points keep a body of their own, over the same helpers, because their refusals differ: og_deposit_witness_d has no bound on
+// n of its own (its witness launch names it), and og_withdraw_prove_batch_d checks depth and key of an empty batch too.
+static int record_shape(const Statement& st, const StatementArgs& a, uint64_t shape[3]) {
   return guarded([&]() -> int {
     OG_REQUIRE(shape != nullptr, "og_" + std::string(st.name) + "_shape: null argument");
-    return records_shape_query(st, depth, shape);
+    return records_shape_query(st, a, shape);
   });
 }
 
-static int record_witness_d(const RecordStatement& st, og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, uint8_t* witness_out_d) {
+static int record_witness_d(const Statement& st, og_ctx* ctx, const StatementArgs& a, const uint8_t* inputs_d, size_t n, uint8_t* witness_out_d) {
   return guarded([&]() -> int {
     CTX_OK(ctx);
     OG_REQUIRE(n <= 65535, "og_" + std::string(st.name) + "_witness_d: at most 65535 witnesses per call");  // (before any scratch is grown or any kernel launched)
     OG_REQUIRE(n == 0 || (inputs_d && witness_out_d), "og_" + std::string(st.name) + "_witness_d: null argument");
     LOCKED(ctx);
-    OG_TRY(records_ok(st, ctx, depth, inputs_d, n, 0));
-    OG_TRY(records_witness(st, ctx, depth, inputs_d, n, witness_out_d));
+    OG_TRY(records_ok(st, ctx, a, inputs_d, n, 0));
+    OG_TRY(st.witness(st, ctx, a, inputs_d, n, witness_out_d));
     OG_HIP(hipStreamSynchronize(ctx->stream));
     return OG_OK;
   });
 }
 
-static int record_prove_batch_d(const RecordStatement& st, og_ctx* ctx, const og_pk* pk, int depth, const uint8_t* inputs_d, size_t n,
+static int record_prove_batch_d(const Statement& st, og_ctx* ctx, const og_pk* pk, const StatementArgs& a, const uint8_t* inputs_d, size_t n,
                                 const uint8_t* rs, uint8_t* proofs_out, uint8_t* public_out) {
   return guarded([&]() -> int {
     CTX_OK(ctx);
@@ -64,7 +66,7 @@ static int record_prove_batch_d(const RecordStatement& st, og_ctx* ctx, const og
     OG_REQUIRE(n == 0 || (inputs_d && rs && proofs_out), "og_" + std::string(st.name) + "_prove_batch_d: null argument");
     if (n == 0) return OG_OK;
     LOCKED(ctx);
-    return records_prove_batch(st, ctx, pk, depth, inputs_d, n, rs, proofs_out, public_out);
+    return statement_prove_batch(st, ctx, pk, a, inputs_d, n, rs, proofs_out, public_out);
   });
 }
 
@@ -568,23 +570,11 @@ int og_spmv_fr_d(og_ctx* ctx, const uint32_t* row_ptr_d, const uint32_t* col_d, 
 }
 
 int og_withdraw_shape(int depth, uint64_t n_pad3, uint64_t n_pad2, uint64_t shape[3]) {
-  return guarded([&]() -> int {
-    OG_REQUIRE(shape != nullptr, "og_withdraw_shape: null argument");
-    return withdraw_shape_query(depth, n_pad3, n_pad2, shape);
-  });
+  return record_shape(ST_WITHDRAW, {depth, n_pad3, n_pad2}, shape);
 }
-
 int og_withdraw_witness_d(og_ctx* ctx, int depth, uint64_t n_pad3, uint64_t n_pad2, const uint8_t* inputs_d, size_t n,
                           uint8_t* witness_out_d) {
-  return guarded([&]() -> int {
-    CTX_OK(ctx);
-    OG_REQUIRE(n <= 65535, "og_withdraw_witness_d: at most 65535 witnesses per call");  // (before any scratch is grown or any kernel launched)
-    LOCKED(ctx);
-    OG_TRY(withdraw_records_ok(ctx, depth, inputs_d, n, 0));
-    OG_TRY(withdraw_witness(ctx, depth, n_pad3, n_pad2, inputs_d, n, witness_out_d));
-    OG_HIP(hipStreamSynchronize(ctx->stream));
-    return OG_OK;
-  });
+  return record_witness_d(ST_WITHDRAW, ctx, {depth, n_pad3, n_pad2}, inputs_d, n, witness_out_d);
 }
 
 int og_set_lanes(og_ctx* ctx, int n_lanes) {
@@ -719,8 +709,7 @@ int og_withdraw_prove_batch_d(og_ctx* ctx, const og_pk* pk, int depth, uint64_t 
     OG_REQUIRE(pk != nullptr, "og_withdraw_prove_batch_d: null key");
     OG_REQUIRE(n == 0 || (inputs_d && rs && proofs_out), "og_withdraw_prove_batch_d: null argument");
     LOCKED(ctx);
-    OG_HIP(hipSetDevice(ctx->device));
-    return withdraw_prove_batch(ctx, pk, depth, n_pad3, n_pad2, inputs_d, n, rs, proofs_out, public_out);
+    return withdraw_prove_batch(ctx, pk, {depth, n_pad3, n_pad2}, inputs_d, n, rs, proofs_out, public_out);
   });
 }
 
@@ -732,66 +721,52 @@ int og_withdraw_prove_batch_submit_d(og_ctx* ctx, const og_pk* pk, int depth, ui
     OG_REQUIRE(n >= 1 && inputs_d && rs && proofs_out, "og_withdraw_prove_batch_submit_d: null argument or empty batch");
     *job_out = nullptr;
     LOCKED(ctx);
-    return withdraw_prove_batch_submit(ctx, pk, depth, n_pad3, n_pad2, inputs_d, n, rs, proofs_out, public_out, job_out);
+    return withdraw_prove_batch_submit(ctx, pk, {depth, n_pad3, n_pad2}, inputs_d, n, rs, proofs_out, public_out, job_out);
   });
 }
 
-int og_deposit_shape(uint64_t shape[3]) {
-  return guarded([&]() -> int {
-    OG_REQUIRE(shape != nullptr, "og_deposit_shape: null argument");
-    return deposit_shape_query(shape);
-  });
-}
-
+int og_deposit_shape(uint64_t shape[3]) { return record_shape(ST_DEPOSIT, {}, shape); }
 int og_deposit_witness_d(og_ctx* ctx, const uint8_t* inputs_d, size_t n, uint8_t* witness_out_d) {
   return guarded([&]() -> int {
     CTX_OK(ctx);
     OG_REQUIRE(n == 0 || (inputs_d && witness_out_d), "og_deposit_witness_d: null argument");
     LOCKED(ctx);
-    OG_TRY(deposit_records_ok(ctx, inputs_d, n, 0));
-    OG_TRY(deposit_witness(ctx, inputs_d, n, witness_out_d));
+    OG_TRY(records_ok(ST_DEPOSIT, ctx, {}, inputs_d, n, 0));
+    OG_TRY(ST_DEPOSIT.witness(ST_DEPOSIT, ctx, {}, inputs_d, n, witness_out_d));
     OG_HIP(hipStreamSynchronize(ctx->stream));
     return OG_OK;
   });
 }
-
 int og_deposit_prove_batch_d(og_ctx* ctx, const og_pk* pk, const uint8_t* inputs_d, size_t n, const uint8_t* rs, uint8_t* proofs_out,
                              uint8_t* public_out) {
-  return guarded([&]() -> int {
-    CTX_OK(ctx);
-    OG_REQUIRE(pk != nullptr, "og_deposit_prove_batch_d: null key");
-    OG_REQUIRE(n == 0 || (inputs_d && rs && proofs_out), "og_deposit_prove_batch_d: null argument");
-    if (n == 0) return OG_OK;
-    LOCKED(ctx);
-    return deposit_prove_batch(ctx, pk, inputs_d, n, rs, proofs_out, public_out);
-  });
+  return record_prove_batch_d(ST_DEPOSIT, ctx, pk, {}, inputs_d, n, rs, proofs_out, public_out);
 }
 
-int og_split_shape(int depth, uint64_t shape[3]) { return record_shape(ST_SPLIT, depth, shape); }
+int og_split_shape(int depth, uint64_t shape[3]) { return record_shape(ST_SPLIT, {depth}, shape); }
 int og_split_witness_d(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, uint8_t* witness_out_d) {
-  return record_witness_d(ST_SPLIT, ctx, depth, inputs_d, n, witness_out_d);
+  return record_witness_d(ST_SPLIT, ctx, {depth}, inputs_d, n, witness_out_d);
 }
 int og_split_prove_batch_d(og_ctx* ctx, const og_pk* pk, int depth, const uint8_t* inputs_d, size_t n, const uint8_t* rs,
                            uint8_t* proofs_out, uint8_t* public_out) {
-  return record_prove_batch_d(ST_SPLIT, ctx, pk, depth, inputs_d, n, rs, proofs_out, public_out);
+  return record_prove_batch_d(ST_SPLIT, ctx, pk, {depth}, inputs_d, n, rs, proofs_out, public_out);
 }
 
-int og_join_shape(int depth, uint64_t shape[3]) { return record_shape(ST_JOIN, depth, shape); }
+int og_join_shape(int depth, uint64_t shape[3]) { return record_shape(ST_JOIN, {depth}, shape); }
 int og_join_witness_d(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, uint8_t* witness_out_d) {
-  return record_witness_d(ST_JOIN, ctx, depth, inputs_d, n, witness_out_d);
+  return record_witness_d(ST_JOIN, ctx, {depth}, inputs_d, n, witness_out_d);
 }
 int og_join_prove_batch_d(og_ctx* ctx, const og_pk* pk, int depth, const uint8_t* inputs_d, size_t n, const uint8_t* rs,
                           uint8_t* proofs_out, uint8_t* public_out) {
-  return record_prove_batch_d(ST_JOIN, ctx, pk, depth, inputs_d, n, rs, proofs_out, public_out);
+  return record_prove_batch_d(ST_JOIN, ctx, pk, {depth}, inputs_d, n, rs, proofs_out, public_out);
 }
 
-int og_transfer_shape(int depth, uint64_t shape[3]) { return record_shape(ST_TRANSFER, depth, shape); }
+int og_transfer_shape(int depth, uint64_t shape[3]) { return record_shape(ST_TRANSFER, {depth}, shape); }
 int og_transfer_witness_d(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, uint8_t* witness_out_d) {
-  return record_witness_d(ST_TRANSFER, ctx, depth, inputs_d, n, witness_out_d);
+  return record_witness_d(ST_TRANSFER, ctx, {depth}, inputs_d, n, witness_out_d);
 }
 int og_transfer_prove_batch_d(og_ctx* ctx, const og_pk* pk, int depth, const uint8_t* inputs_d, size_t n, const uint8_t* rs,
                               uint8_t* proofs_out, uint8_t* public_out) {
-  return record_prove_batch_d(ST_TRANSFER, ctx, pk, depth, inputs_d, n, rs, proofs_out, public_out);
+  return record_prove_batch_d(ST_TRANSFER, ctx, pk, {depth}, inputs_d, n, rs, proofs_out, public_out);
 }
 
 int og_withdraw_prove_partials_d(og_ctx* ctx, const og_pk* pk, int depth, uint64_t n_pad3, uint64_t n_pad2, const uint8_t* inputs_d,
@@ -801,7 +776,7 @@ int og_withdraw_prove_partials_d(og_ctx* ctx, const og_pk* pk, int depth, uint64
     OG_REQUIRE(pk != nullptr && inputs_d && partials_d && n >= 1, "og_withdraw_prove_partials_d: null argument or empty batch");
     LOCKED(ctx);
     og_job* job = nullptr;
-    OG_TRY(withdraw_prove_partials_enqueue(ctx, pk, depth, n_pad3, n_pad2, inputs_d, n, win_rank, win_world, partials_d, public_out, &job));
+    OG_TRY(withdraw_prove_partials_enqueue(ctx, pk, {depth, n_pad3, n_pad2}, inputs_d, n, win_rank, win_world, partials_d, public_out, &job));
     return job_wait(job);
   });
 }

@@ -10,6 +10,8 @@
 #include <map>
 #include "../../include/owshen_gpu.h"
 
+namespace og { struct Statement; }  // statements.h
+
 // Events of the batched prover's stage pipeline (groth16.hip issue_pipeline), a set per scratch slot: og_ctx::pipe_ev[slot][...]
 enum PipeEvent {
   EV_ROWS,       // prep: A z, B z, C z exist                         -> math (quotient)
@@ -105,7 +107,9 @@ struct og_job {
   uint8_t* pub_out = nullptr;
   uint8_t *proofs_d = nullptr, *pub_d = nullptr;
   uint32_t* flags_d = nullptr;     // [n] unsatisfied flags | [n] first non-canonical wire / record field (0xffffffff = none)
-  int bad_kind = 0;                // what the second half indexes: 0 nothing checked, 1 witness wires, 2 withdraw input-record fields
+  int bad_kind = 0;                // what the second half indexes: 0 nothing checked, 1 witness wires, 2 input-record fields of ...
+  const og::Statement* gen_st = nullptr;  // ... this statement at gen_depth (statements.h): the call generated its witnesses itself
+  int gen_depth = 0;
   hipEvent_t done[4] = {nullptr, nullptr, nullptr, nullptr};  // one per stream, recorded behind the call's last work
   int n_done = 0;
   uint64_t id = 0;                 // per-process serial number: a handle's ADDRESS can be reused by a later job, its id cannot

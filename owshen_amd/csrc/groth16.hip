@@ -483,12 +483,12 @@ static int choose_sub_batch(og_ctx* ctx, const og_pk* pk, size_t n) {
   return (int)std::min(sb, n);
 }
 
-// Optional in-lane witness generation for the withdraw circuit: the sub-batch's witnesses are produced by the
+// Optional in-lane witness generation (withdraw is the one statement routed here): the sub-batch's witnesses are produced by the
 // lane that proves them (into lane-private scratch), so the latency-bound MiMC7 walk overlaps the other lane.
-struct WithdrawGen {
-  int depth;
-  uint64_t n_pad3, n_pad2;
-  const uint8_t* inputs_d;  // n records of (8 + depth) x 32 B
+struct StatementGen {
+  const Statement* st;
+  StatementArgs args;
+  const uint8_t* inputs_d;  // n records of record_bytes(*st, args.depth)
 };
 
 // Window-sharded PROVING (round 6; north_star: "MSM windows shard naturally across GPUs", BASELINE.json configs[3]).  A rank
@@ -741,7 +741,7 @@ struct ProveCall {
   size_t n;
   ProvePlan plan;
   int call_slot;
-  const WithdrawGen* gen;       // the witnesses: generated per sub-batch | host memory | the caller's device buffer (canonical
+  const StatementGen* gen;      // the witnesses: generated per sub-batch | host memory | the caller's device buffer (canonical
   const uint8_t *z_host, *z_d;  // unless trusted_z)
   bool trusted_z;
   const WinShard* sh;  // a window-sharded front: the five results are the call's output, nothing is assembled
@@ -829,12 +829,12 @@ static int sub_front(const ProveCall& c, SubBatch& s) {
   OG_TRY(arena_get(ctx, "g16.h", sb_max * d * 32, (void**)&s.h));
   s.zs = c.z_d ? c.z_d + g0 * m * 32 : nullptr;
   OG_HIP(hipMemsetAsync(c.bad + g0, 0xff, (size_t)s.sb * 4, ctx->stream));
-  if (const WithdrawGen* gen = c.gen) {
-    const uint8_t* records = gen->inputs_d + g0 * (size_t)(8 + gen->depth) * 32;
+  if (const StatementGen* gen = c.gen) {
+    const uint8_t* records = gen->inputs_d + g0 * record_bytes(*gen->st, gen->args.depth);
     uint8_t* zbuf = nullptr;
-    OG_TRY(withdraw_check_records(ctx, gen->depth, records, (size_t)s.sb, c.bad + g0));
+    OG_TRY(records_check_enqueue(*gen->st, ctx, gen->args, records, (size_t)s.sb, c.bad + g0));
     OG_TRY(arena_get(ctx, "g16.zgen", sb_max * m * 32, (void**)&zbuf));
-    OG_TRY(withdraw_witness(ctx, gen->depth, gen->n_pad3, gen->n_pad2, records, (size_t)s.sb, zbuf));
+    OG_TRY(gen->st->witness(*gen->st, ctx, gen->args, records, (size_t)s.sb, zbuf));
     s.zs = zbuf;
   } else if (c.z_host) {
     // witnesses in HOST memory (og_prove_batch): the sub-batch crosses PCIe into its slot's staging buffer -- in the stage
@@ -1144,6 +1144,7 @@ static int job_publish(const ProveCall& c, og_job** job_out) {
   job->ctx = ctx; job->call_slot = c.call_slot; job->n = c.n; job->n_pub = c.pub_d ? c.pk->n_pub : 0;
   job->proofs = c.proofs; job->pub_out = c.pub_out; job->proofs_d = c.proofs_d; job->pub_d = c.pub_d; job->flags_d = c.flags;
   job->bad_kind = c.gen ? 2 : (c.trusted_z ? 0 : 1);
+  if (c.gen) { job->gen_st = c.gen->st; job->gen_depth = c.gen->args.depth; }
   if (c.host_asm) {
     job->host_asm_pk = c.pk;
     for (int k = 0; k < 5; k++) job->res_d[k] = c.res[k];
@@ -1166,7 +1167,7 @@ static int job_publish(const ProveCall& c, og_job** job_out) {
 }
 
 static int prove_enqueue(og_ctx* ctx, const og_pk* pk, const uint8_t* z_d, size_t n, const uint8_t* rs, uint8_t* proofs,
-                         const WithdrawGen* gen, uint8_t* pub_out, og_job** job_out, const uint8_t* z_host = nullptr,
+                         const StatementGen* gen, uint8_t* pub_out, og_job** job_out, const uint8_t* z_host = nullptr,
                          bool trusted_z = false, const WinShard* sh = nullptr) {
   *job_out = nullptr;
   ProveCall c{};
@@ -1213,6 +1214,12 @@ static int prove_enqueue(og_ctx* ctx, const og_pk* pk, const uint8_t* z_d, size_
   return OG_OK;
 }
 
+// OG_ERR_UNSATISFIED for witness g of the caller's batch: the ONE place the message is formed
+static int unsatisfied(size_t g) {
+  set_error("og_prove: witness " + std::to_string(g) + " does not satisfy the circuit (a row has a*b != c, or wire 0 is not 1)");
+  return OG_ERR_UNSATISFIED;
+}
+
 // waits for the job's last kernels, copies proofs / flags / public inputs to the caller's buffers, frees the job
 static int prove_finish(og_job* job, size_t* first_bad) {
   og_ctx* ctx = job->ctx;
@@ -1250,8 +1257,7 @@ static int prove_finish(og_job* job, size_t* first_bad) {
       if (b == 0xffffffffu) continue;
       if (first_bad) *first_bad = g;
       if (job->bad_kind == 2)
-        set_error("og_withdraw_prove: input record " + std::to_string(g) + ": field " + std::to_string(b) + " (" + withdraw_field_name(b) +
-                  (b >= 8 ? " " + std::to_string(b - 8) : std::string()) + ") is not a canonical value (>= r, or an index outside the tree)");
+        set_error(invalid_record_message(*job->gen_st, "og_" + std::string(job->gen_st->name) + "_prove", job->gen_depth, g, b));
       else
         set_error("og_prove: witness " + std::to_string(g) + ": wire " + std::to_string(b) + " is not a canonical Fr element (>= r)");
       return OG_ERR_INVALID;
@@ -1259,15 +1265,14 @@ static int prove_finish(og_job* job, size_t* first_bad) {
   for (size_t g = 0; g < n; g++)
     if (fl[g]) {
       if (first_bad) *first_bad = g;
-      set_error("og_prove: witness " + std::to_string(g) + " does not satisfy the circuit (a row has a*b != c, or wire 0 is not 1)");
-      return OG_ERR_UNSATISFIED;
+      return unsatisfied(g);
     }
   return OG_OK;
 }
 
 // blocking form: enqueue + finish
 static int prove_batch_impl(og_ctx* ctx, const og_pk* pk, const uint8_t* z_d, size_t n, const uint8_t* rs, uint8_t* proofs,
-                            size_t* first_bad, const WithdrawGen* gen, uint8_t* pub_out, bool trusted_z = false) {
+                            size_t* first_bad, const StatementGen* gen, uint8_t* pub_out, bool trusted_z = false) {
   if (n == 0) return OG_OK;
   og_job* job = nullptr;
   OG_TRY(prove_enqueue(ctx, pk, z_d, n, rs, proofs, gen, pub_out, &job, nullptr, trusted_z));
@@ -1288,31 +1293,7 @@ int prove_batch_host(og_ctx* ctx, const og_pk* pk, const uint8_t* z, size_t n, c
   // profiles/r03_host_boundary.json.)
   og_job* job = nullptr;
   OG_TRY(prove_enqueue(ctx, pk, nullptr, n, rs, proofs, nullptr, nullptr, &job, z));
-  size_t bad = 0;
-  const int r = prove_finish(job, &bad);
-  if (r == OG_ERR_UNSATISFIED)
-    set_error("og_prove: witness " + std::to_string(bad) + " does not satisfy the circuit (a row has a*b != c, or wire 0 is not 1)");
-  return r;
-}
-
-// blocking form of the record check (og_withdraw_witness_d, the whole-slab path of small circuits): OG_ERR_INVALID names the
-// first malformed record (`base` = index of record 0 in the caller's batch)
-int withdraw_records_ok(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, size_t base) {
-  if (n == 0) return OG_OK;
-  uint32_t* bad_d = nullptr;
-  OG_TRY(arena_get(ctx, "wd.bad", n * 4, (void**)&bad_d));
-  OG_HIP(hipMemsetAsync(bad_d, 0xff, n * 4, ctx->stream));
-  OG_TRY(withdraw_check_records(ctx, depth, inputs_d, n, bad_d));
-  std::vector<uint32_t> b(n);
-  OG_HIP(hipMemcpyAsync(b.data(), bad_d, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-  OG_HIP(hipStreamSynchronize(ctx->stream));
-  for (size_t g = 0; g < n; g++)
-    if (b[g] != 0xffffffffu) {
-      set_error("og_withdraw: input record " + std::to_string(base + g) + ": field " + std::to_string(b[g]) + " (" + withdraw_field_name(b[g]) +
-                (b[g] >= 8 ? " " + std::to_string(b[g] - 8) : std::string()) + ") is not a canonical value (>= r, or an index outside the tree)");
-      return OG_ERR_INVALID;
-    }
-  return OG_OK;
+  return prove_finish(job, nullptr);
 }
 
 // inputs (withdraw circuit records) -> proofs: witness generation fused into the lanes (withdraw_prove_batch, below)
@@ -1383,22 +1364,86 @@ int job_abandon(og_job* job) {
   return OG_OK;
 }
 
+// ---- records -> proofs, every statement (statements.h) -------------------------------------------------------------------------
+// the key must have the wires and the public inputs of the statement at these arguments: "og_<st>_<entry>: the key is not for ..."
+static int statement_key_ok(const Statement& st, const StatementArgs& a, const og_pk* pk, const char* entry) {
+  uint64_t shp[3];
+  OG_TRY(records_shape_query(st, a, shp));
+  OG_REQUIRE(shp[0] == pk->m && shp[2] == pk->n_pub, "og_" + std::string(st.name) + "_" + entry + ": the key is not for " + st.key_noun);
+  return OG_OK;
+}
+
+// A slab: the witnesses generated in ONE launch up front and proved from one buffer -- 16 GiB of wires, at most 65 535 (a record's
+// index is grid.y of its check).  OG_SLAB_MAX (hooks builds) lowers the bound: tests/statement_slab_cases.py reaches a second slab with
+// it.  A window-sharded call is one slab, so there the hook lowers the call's cap too ("at most N proofs ... per window-sharded call").
+static size_t slab_limit(const og_pk* pk) {
+  const size_t by_bytes = std::max<size_t>(1, ((size_t)16 << 30) / (pk->m * 32));
+  return std::min(std::min<size_t>(65535, by_bytes), (size_t)std::max<long long>(1, OG_HOOK_INT("OG_SLAB_MAX", 65535)));
+}
+
+// one slab's witnesses in z_d: the records checked (blocking; `base` = index of record 0 in the caller's batch), the walk launched,
+// the stream idle -- every stream of the prover reads the slab
+static int slab_witnesses(const Statement& st, og_ctx* ctx, const StatementArgs& a, const uint8_t* records_d, size_t cnt, size_t base,
+                          uint8_t* z_d) {
+  OG_TRY(records_ok(st, ctx, a, records_d, cnt, base));
+  OG_TRY(st.witness(st, ctx, a, records_d, cnt, z_d));
+  OG_HIP(hipStreamSynchronize(ctx->stream));
+  return OG_OK;
+}
+
+// The witness generators are latency-bound (one lane, or one wave, walks a request's hashes whatever the launch size), and a sub-batch
+// of a small circuit proves in about the same time: so whole slabs of witnesses in one launch, then the ordinary batched prover.  For
+// join, the prover's row check is what answers OG_ERR_UNSATISFIED for two notes under different roots: the witness carries note a's
+// root in wire 1.
+static int prove_slabs(const Statement& st, og_ctx* ctx, const og_pk* pk, const StatementArgs& a, const uint8_t* inputs_d, size_t n,
+                       const uint8_t* rs, uint8_t* proofs, uint8_t* pub_out) {
+  if (n == 0) return OG_OK;
+  const size_t rec = record_bytes(st, a.depth), slab = std::min(n, slab_limit(pk));
+  uint8_t* z_d = nullptr;
+  OG_TRY(arena_get(ctx, "g16.zall", slab * pk->m * 32, (void**)&z_d));
+  for (size_t g0 = 0; g0 < n; g0 += slab) {
+    const size_t cnt = std::min(slab, n - g0);
+    OG_TRY(slab_witnesses(st, ctx, a, inputs_d + g0 * rec, cnt, g0, z_d));
+    size_t bad = 0;
+    const int r = prove_batch_impl(ctx, pk, z_d, cnt, rs + g0 * 64, proofs + g0 * 256, &bad, nullptr,
+                                   pub_out ? pub_out + g0 * pk->n_pub * 32 : nullptr, true);  // (our own generator's wires are canonical)
+    if (r == OG_ERR_UNSATISFIED) return unsatisfied(g0 + bad);
+    if (r != OG_OK) return r;
+  }
+  return OG_OK;
+}
+
+int statement_prove_batch(const Statement& st, og_ctx* ctx, const og_pk* pk, const StatementArgs& a, const uint8_t* inputs_d, size_t n,
+                          const uint8_t* rs, uint8_t* proofs, uint8_t* pub_out) {
+  OG_TRY(statement_key_ok(st, a, pk, "prove_batch_d"));
+  return prove_slabs(st, ctx, pk, a, inputs_d, n, rs, proofs, pub_out);
+}
+
+// Withdraw: big circuits hide the walk inside the lanes (a sub-batch proves for hundreds of ms), and so does every call of one
+// sub-batch (gen_inside); the rest goes slab by slab like every other statement.
+int withdraw_prove_batch(og_ctx* ctx, const og_pk* pk, const StatementArgs& a, const uint8_t* inputs_d, size_t n, const uint8_t* rs,
+                         uint8_t* proofs, uint8_t* pub_out) {
+  OG_TRY(statement_key_ok(ST_WITHDRAW, a, pk, "prove_batch_d"));
+  if (gen_inside(ctx, pk, n, (size_t)choose_sub_batch(ctx, pk, n))) {
+    const StatementGen gen{&ST_WITHDRAW, a, inputs_d};
+    return prove_batch_impl(ctx, pk, nullptr, n, rs, proofs, nullptr, &gen, pub_out);
+  }
+  return prove_slabs(ST_WITHDRAW, ctx, pk, a, inputs_d, n, rs, proofs, pub_out);
+}
+
 // Enqueue-only form of withdraw_prove_batch: returns a job whose results og_job_wait delivers.  Circuits whose witnesses are
 // generated inside the pipeline (the large ones) are really left running; for small circuits (whole-slab witness
 // generation up front, shared staging) the call completes here and the job only carries the status.
-int withdraw_prove_batch_submit(og_ctx* ctx, const og_pk* pk, int depth, uint64_t n_pad3, uint64_t n_pad2, const uint8_t* inputs_d,
-                                size_t n, const uint8_t* rs, uint8_t* proofs, uint8_t* pub_out, og_job** job_out) {
+int withdraw_prove_batch_submit(og_ctx* ctx, const og_pk* pk, const StatementArgs& a, const uint8_t* inputs_d, size_t n, const uint8_t* rs,
+                                uint8_t* proofs, uint8_t* pub_out, og_job** job_out) {
   *job_out = nullptr;
-  uint64_t shp[3];
-  OG_TRY(withdraw_shape_query(depth, n_pad3, n_pad2, shp));
-  OG_REQUIRE(shp[0] == pk->m && shp[2] == pk->n_pub, "og_withdraw_prove_batch_submit_d: the key is not for this withdraw-circuit shape");
+  OG_TRY(statement_key_ok(ST_WITHDRAW, a, pk, "prove_batch_submit_d"));
   OG_REQUIRE(n >= 1, "og_withdraw_prove_batch_submit_d: empty batch");
-  const size_t sb = (size_t)choose_sub_batch(ctx, pk, n);
-  if (gen_inside(ctx, pk, n, sb)) {
-    WithdrawGen gen{depth, n_pad3, n_pad2, inputs_d};
+  if (gen_inside(ctx, pk, n, (size_t)choose_sub_batch(ctx, pk, n))) {
+    const StatementGen gen{&ST_WITHDRAW, a, inputs_d};
     return prove_enqueue(ctx, pk, nullptr, n, rs, proofs, &gen, pub_out, job_out);
   }
-  OG_TRY(withdraw_prove_batch(ctx, pk, depth, n_pad3, n_pad2, inputs_d, n, rs, proofs, pub_out));
+  OG_TRY(withdraw_prove_batch(ctx, pk, a, inputs_d, n, rs, proofs, pub_out));
   og_job* job = new og_job();  // nothing left to wait for
   job->id = next_job_id();
   job->ctx = ctx;
@@ -1408,117 +1453,28 @@ int withdraw_prove_batch_submit(og_ctx* ctx, const og_pk* pk, int depth, uint64_
   return OG_OK;
 }
 
-int withdraw_prove_batch(og_ctx* ctx, const og_pk* pk, int depth, uint64_t n_pad3, uint64_t n_pad2, const uint8_t* inputs_d, size_t n,
-                         const uint8_t* rs, uint8_t* proofs, uint8_t* pub_out) {
-  uint64_t shp[3];
-  OG_TRY(withdraw_shape_query(depth, n_pad3, n_pad2, shp));
-  OG_REQUIRE(shp[0] == pk->m && shp[2] == pk->n_pub, "og_withdraw_prove_batch_d: the key is not for this withdraw-circuit shape");
-  // The witness generator is latency-bound (one lane walks a proof's 35 hashes: ~30 ms whatever the launch size).
-  // Big circuits hide that inside the lanes (a sub-batch proves for hundreds of ms); for small circuits a
-  // sub-batch proves in about the same time, so generate whole slabs of witnesses in ONE launch up front instead.
-  const size_t sb = (size_t)choose_sub_batch(ctx, pk, n);
-  if (gen_inside(ctx, pk, n, sb)) {
-    WithdrawGen gen{depth, n_pad3, n_pad2, inputs_d};
-    return prove_batch_impl(ctx, pk, nullptr, n, rs, proofs, nullptr, &gen, pub_out);
-  }
-  const size_t slab = std::max<size_t>(1, std::min<size_t>(n, ((size_t)16 << 30) / (pk->m * 32)));
-  uint8_t* z_d = nullptr;
-  OG_TRY(arena_get(ctx, "g16.zall", std::min(slab, (size_t)65535) * pk->m * 32, (void**)&z_d));
-  for (size_t g0 = 0; g0 < n;) {
-    const size_t cnt = std::min(std::min(slab, (size_t)65535), n - g0);
-    OG_TRY(withdraw_records_ok(ctx, depth, inputs_d + g0 * (size_t)(8 + depth) * 32, cnt, g0));
-    OG_TRY(withdraw_witness(ctx, depth, n_pad3, n_pad2, inputs_d + g0 * (size_t)(8 + depth) * 32, cnt, z_d));
-    OG_HIP(hipStreamSynchronize(ctx->stream));  // both lanes read the slab
-    size_t bad = 0;
-    int r = prove_batch_impl(ctx, pk, z_d, cnt, rs + g0 * 64, proofs + g0 * 256, &bad, nullptr,
-                             pub_out ? pub_out + g0 * pk->n_pub * 32 : nullptr, true);  // (our own generator's wires are canonical)
-    if (r == OG_ERR_UNSATISFIED)
-      set_error("og_prove: witness " + std::to_string(g0 + bad) + " does not satisfy the circuit (a row has a*b != c, or wire 0 is not 1)");
-    if (r != OG_OK) return r;
-    g0 += cnt;
-  }
-  return OG_OK;
-}
-
-// deposit records (nullifier | secret | depositor) -> proofs of the deposit statement (witness.hip, oracle/py/deposit.py): a small
-// circuit, so whole slabs of witnesses in one launch, then the ordinary batched prover
-int deposit_prove_batch(og_ctx* ctx, const og_pk* pk, const uint8_t* inputs_d, size_t n, const uint8_t* rs, uint8_t* proofs, uint8_t* pub_out) {
-  uint64_t shp[3];
-  OG_TRY(deposit_shape_query(shp));
-  OG_REQUIRE(shp[0] == pk->m && shp[2] == pk->n_pub, "og_deposit_prove_batch_d: the key is not for the deposit statement");
-  uint8_t* z_d = nullptr;
-  const size_t slab = std::min<size_t>(n, 65535);
-  OG_TRY(arena_get(ctx, "g16.zall", slab * pk->m * 32, (void**)&z_d));
-  for (size_t g0 = 0; g0 < n;) {
-    const size_t cnt = std::min(slab, n - g0);
-    OG_TRY(deposit_records_ok(ctx, inputs_d + g0 * 96, cnt, g0));
-    OG_TRY(deposit_witness(ctx, inputs_d + g0 * 96, cnt, z_d));
-    OG_HIP(hipStreamSynchronize(ctx->stream));  // both lanes read the slab
-    size_t bad = 0;
-    int r = prove_batch_impl(ctx, pk, z_d, cnt, rs + g0 * 64, proofs + g0 * 256, &bad, nullptr, pub_out ? pub_out + g0 * pk->n_pub * 32 : nullptr, true);
-    if (r == OG_ERR_UNSATISFIED)
-      set_error("og_prove: witness " + std::to_string(g0 + bad) + " does not satisfy the circuit (a row has a*b != c, or wire 0 is not 1)");
-    if (r != OG_OK) return r;
-    g0 += cnt;
-  }
-  return OG_OK;
-}
-
-// records -> proofs for the record statements (statements.h: split, join, transfer): per slab -- sized as the small-circuit branch of
-// withdraw_prove_batch -- check the records, generate the witnesses in one launch, then the ordinary batched prover.  For join, the
-// prover's row check is what answers OG_ERR_UNSATISFIED for two notes under different roots: the witness carries note a's root in wire 1
-int records_prove_batch(const RecordStatement& st, og_ctx* ctx, const og_pk* pk, int depth, const uint8_t* inputs_d, size_t n, const uint8_t* rs,
-                        uint8_t* proofs, uint8_t* pub_out) {
-  uint64_t shp[3];
-  OG_TRY(records_shape_query(st, depth, shp));
-  OG_REQUIRE(shp[0] == pk->m && shp[2] == pk->n_pub,
-             "og_" + std::string(st.name) + "_prove_batch_d: the key is not for this " + st.name + "-statement shape");
-  const size_t rec = record_bytes(st, depth);
-  const size_t slab = std::min<size_t>(65535, std::max<size_t>(1, std::min<size_t>(n, ((size_t)16 << 30) / (pk->m * 32))));
-  uint8_t* z_d = nullptr;
-  OG_TRY(arena_get(ctx, "g16.zall", slab * pk->m * 32, (void**)&z_d));
-  for (size_t g0 = 0; g0 < n;) {
-    const size_t cnt = std::min(slab, n - g0);
-    OG_TRY(records_ok(st, ctx, depth, inputs_d + g0 * rec, cnt, g0));
-    OG_TRY(records_witness(st, ctx, depth, inputs_d + g0 * rec, cnt, z_d));
-    OG_HIP(hipStreamSynchronize(ctx->stream));  // both streams of the prover read the slab
-    size_t bad = 0;
-    int r = prove_batch_impl(ctx, pk, z_d, cnt, rs + g0 * 64, proofs + g0 * 256, &bad, nullptr, pub_out ? pub_out + g0 * pk->n_pub * 32 : nullptr, true);
-    if (r == OG_ERR_UNSATISFIED)
-      set_error("og_prove: witness " + std::to_string(g0 + bad) + " does not satisfy the circuit (a row has a*b != c, or wire 0 is not 1)");
-    if (r != OG_OK) return r;
-    g0 += cnt;
-  }
-  return OG_OK;
-}
-
 // ---- window-sharded proving: the two halves (WinShard above) -------------------------------------------------------------------
 // Front half, enqueue only: this rank's partial sums of the five queries of n proofs into partials_d (n x PARTIAL_BYTES, device,
 // the caller's), everything left running on the context's streams; the job carries the boundary flags and the public inputs
 // (og_job_wait semantics: prove_finish reports a malformed record / an unsatisfied witness exactly as the unsharded call does).
-int withdraw_prove_partials_enqueue(og_ctx* ctx, const og_pk* pk, int depth, uint64_t n_pad3, uint64_t n_pad2, const uint8_t* inputs_d,
-                                    size_t n, int win_rank, int win_world, uint8_t* partials_d, uint8_t* pub_out, og_job** job_out) {
+int withdraw_prove_partials_enqueue(og_ctx* ctx, const og_pk* pk, const StatementArgs& a, const uint8_t* inputs_d, size_t n, int win_rank,
+                                    int win_world, uint8_t* partials_d, uint8_t* pub_out, og_job** job_out) {
   *job_out = nullptr;
-  uint64_t shp[3];
-  OG_TRY(withdraw_shape_query(depth, n_pad3, n_pad2, shp));
-  OG_REQUIRE(shp[0] == pk->m && shp[2] == pk->n_pub, "og_withdraw_prove_partials: the key is not for this withdraw-circuit shape");
+  OG_TRY(statement_key_ok(ST_WITHDRAW, a, pk, "prove_partials"));
   OG_REQUIRE(n >= 1, "og_withdraw_prove_partials: empty batch");
   OG_REQUIRE(win_world >= 1 && win_world <= pk->a->nwin && win_rank >= 0 && win_rank < win_world,
              "og_withdraw_prove_partials: bad window shard (rank, world): at most one rank per window");
   const WinShard sh{win_rank, win_world, partials_d};
-  const size_t sb = (size_t)choose_sub_batch(ctx, pk, n);
-  if (gen_inside(ctx, pk, n, sb)) {
-    WithdrawGen gen{depth, n_pad3, n_pad2, inputs_d};
+  if (gen_inside(ctx, pk, n, (size_t)choose_sub_batch(ctx, pk, n))) {
+    const StatementGen gen{&ST_WITHDRAW, a, inputs_d};
     return prove_enqueue(ctx, pk, nullptr, n, nullptr, nullptr, &gen, pub_out, job_out, nullptr, false, &sh);
   }
-  // small statements: the whole call's witnesses in one launch up front (withdraw_prove_batch); a sharded call is one slab
-  const size_t slab = std::min<size_t>(65535, std::max<size_t>(1, ((size_t)16 << 30) / (pk->m * 32)));
+  // small statements: the whole call's witnesses in one launch up front (prove_slabs); a sharded call is one slab
+  const size_t slab = slab_limit(pk);
   OG_REQUIRE(n <= slab, "og_withdraw_prove_partials: at most " + std::to_string(slab) + " proofs of this statement per window-sharded call");
   uint8_t* z_d = nullptr;
   OG_TRY(arena_get(ctx, "g16.zall", n * pk->m * 32, (void**)&z_d));
-  OG_TRY(withdraw_records_ok(ctx, depth, inputs_d, n, 0));
-  OG_TRY(withdraw_witness(ctx, depth, n_pad3, n_pad2, inputs_d, n, z_d));
-  OG_HIP(hipStreamSynchronize(ctx->stream));  // every stream of the call reads the slab
+  OG_TRY(slab_witnesses(ST_WITHDRAW, ctx, a, inputs_d, n, 0, z_d));
   return prove_enqueue(ctx, pk, z_d, n, nullptr, nullptr, nullptr, pub_out, job_out, nullptr, true, &sh);
 }
 

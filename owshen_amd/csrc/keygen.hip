@@ -183,7 +183,7 @@ constexpr uint32_t K_PAD_SEGMENT = 64;
 
 static int withdraw_r1cs_build(const uint8_t* mimc_consts, int depth, uint64_t n_pad3, uint64_t n_pad2, int dense, og_r1cs* r) {
   uint64_t shp[3];
-  OG_TRY(withdraw_shape_query(depth, n_pad3, n_pad2, shp));
+  OG_TRY(records_shape_query(ST_WITHDRAW, {depth, n_pad3, n_pad2}, shp));
   OG_REQUIRE(n_pad3 < (1ull << 30) && n_pad2 < (1ull << 30), "og_withdraw_r1cs: too many padding gates");
   OG_TRY(r1cs_begin(r, shp, 6, "og_withdraw_r1cs"));
   R1csBuilder b{r, 0, mimc_consts};
@@ -218,7 +218,7 @@ static int withdraw_r1cs_build(const uint8_t* mimc_consts, int depth, uint64_t n
 // the deposit statement (oracle/py/deposit.py; witness.hip k_deposit_witness): 735 wires, 731 rows
 static int deposit_r1cs_build(const uint8_t* mimc_consts, og_r1cs* r) {
   uint64_t shp[3];
-  OG_TRY(deposit_shape_query(shp));
+  OG_TRY(records_shape_query(ST_DEPOSIT, {}, shp));
   r->n_wires = shp[0];
   r->n_pub = shp[2];
   for (int k = 0; k < 3; k++) r->ptr[k].assign(1, 0u);
@@ -290,10 +290,10 @@ void transfer_r1cs_rows(R1csBuilder& b, int depth) {
   b.hash2(R1csBuilder::one(TW_CHANGE_COMMITMENT), R1csBuilder::one(change_asset), (int)TW_CHANGE_LEAF);
 }
 
-static int records_r1cs_build(const RecordStatement& st, const uint8_t* mimc_consts, int depth, og_r1cs* r) {
+static int records_r1cs_build(const Statement& st, const uint8_t* mimc_consts, int depth, og_r1cs* r) {
   const std::string who = "og_" + std::string(st.name) + "_r1cs";
   uint64_t shp[3];
-  OG_TRY(records_shape_query(st, depth, shp));
+  OG_TRY(records_shape_query(st, {depth}, shp));
   OG_TRY(r1cs_begin(r, shp, (uint64_t)st.n_pub, who));
   R1csBuilder b{r, 0, mimc_consts};
   st.r1cs_rows(b, depth);
@@ -496,7 +496,7 @@ static int keygen_setup(og_ctx* ctx, const og_r1cs* r, const uint8_t toxic[160],
 using namespace og;
 
 // the body behind og_<statement>_r1cs of the record statements (statements.h)
-static int record_r1cs(const RecordStatement& st, og_ctx* ctx, int depth, og_r1cs** out) {
+static int record_r1cs(const Statement& st, og_ctx* ctx, int depth, og_r1cs** out) {
   return guarded([&]() -> int {
     OG_REQUIRE(ctx != nullptr && out != nullptr, "og_" + std::string(st.name) + "_r1cs: null argument");
     *out = nullptr;

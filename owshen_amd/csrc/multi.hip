@@ -261,7 +261,7 @@ static int multi_withdraw_prove_batch(og_multi* m, og_pk* const* pks, int depth,
   uint64_t info[4];
   OG_TRY(og_pk_info(pks[0], info));
   const size_t pub_bytes = (size_t)info[1] * 32;
-  const size_t rec = (size_t)(8 + depth) * 32;
+  const size_t rec = record_bytes(ST_WITHDRAW, depth);
   return for_each_device(m, [&](int r) -> int {
     size_t lo, hi;
     slice_of(n, m->n, r, &lo, &hi);
@@ -272,7 +272,7 @@ static int multi_withdraw_prove_batch(og_multi* m, og_pk* const* pks, int depth,
     OG_TRY(arena_get(c, "multi.inputs", (hi - lo) * rec, (void**)&in_d));
     OG_HIP(hipMemcpyAsync(in_d, inputs + lo * rec, (hi - lo) * rec, hipMemcpyHostToDevice, c->stream));
     OG_HIP(hipStreamSynchronize(c->stream));
-    return withdraw_prove_batch(c, pks[r], depth, n_pad3, n_pad2, in_d, hi - lo, rs + lo * 64, proofs_out + lo * 256,
+    return withdraw_prove_batch(c, pks[r], {depth, n_pad3, n_pad2}, in_d, hi - lo, rs + lo * 64, proofs_out + lo * 256,
                                 public_out ? public_out + lo * pub_bytes : nullptr);
   }, "withdraw");
 }
@@ -289,7 +289,7 @@ static int multi_prove_sharded(og_multi* m, og_pk* const* pks, int depth, uint64
                         const uint8_t* witnesses, size_t wit_bytes, size_t n, const uint8_t* rs, uint8_t* proofs_out, uint8_t* public_out) {
   const int G = m->n;
   const size_t pbytes = n * (size_t)OG_PARTIAL_BYTES;
-  const size_t rec = (size_t)(8 + depth) * 32;
+  const size_t rec = record_bytes(ST_WITHDRAW, depth);
   std::vector<uint8_t*> part_d(G, nullptr), gath_d(G, nullptr);
   std::vector<og_job*> jobs(G, nullptr);
   auto abandon_all = [&]() {
@@ -314,7 +314,7 @@ static int multi_prove_sharded(og_multi* m, og_pk* const* pks, int depth, uint64
     OG_HIP(hipMemcpyAsync(in_d, inputs ? inputs : witnesses, in_bytes, hipMemcpyHostToDevice, c->stream));
     OG_HIP(hipStreamSynchronize(c->stream));
     if (inputs)
-      OG_TRY(withdraw_prove_partials_enqueue(c, pks[r], depth, n_pad3, n_pad2, in_d, n, r, G, part_d[r], r == 0 ? public_out : nullptr, &jobs[r]));
+      OG_TRY(withdraw_prove_partials_enqueue(c, pks[r], {depth, n_pad3, n_pad2}, in_d, n, r, G, part_d[r], r == 0 ? public_out : nullptr, &jobs[r]));
     else
       OG_TRY(prove_partials_enqueue(c, pks[r], in_d, n, r, G, part_d[r], &jobs[r]));
     return job_join_stream(jobs[r], c->lanes[0]);  // the exchange below is stream-ordered behind the whole front half

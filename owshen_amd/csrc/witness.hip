@@ -43,6 +43,8 @@ __device__ __forceinline__ Fr lds_get9(const uint32_t* p) {
 
 constexpr int W_PUB = 6;
 constexpr int W_REC = 8;  // fields of an input record before the siblings
+// byte offsets of the record's fields
+constexpr int W_NULLIFIER = 0, W_SECRET = 32, W_AMOUNT = 64, W_RECIPIENT = 96, W_PAD_SEED = 128, W_INDEX = 160, W_TOKEN = 192, W_CHAIN = 224;
 constexpr int PAD_SEGMENT = 64;
 
 struct WithdrawShape {
@@ -91,13 +93,13 @@ __global__ void __launch_bounds__(64) k_withdraw_core(const uint32_t* __restrict
   if (g >= n) return;
   const uint8_t* in = inputs + g * (size_t)(W_REC + depth) * 32;
   WireWriterT<false> ww{out + g * n_wires * 32, first_gadget_wire};
-  const Fr nullifier = fe_to_mont(fe_load<FrParams>(in));
-  const Fr secret = fe_to_mont(fe_load<FrParams>(in + 32));
-  const Fr amount = fe_to_mont(fe_load<FrParams>(in + 64));
-  const Fr recipient = fe_to_mont(fe_load<FrParams>(in + 96));
-  const uint64_t index = *reinterpret_cast<const uint64_t*>(in + 160);
-  const Fr token = fe_to_mont(fe_load<FrParams>(in + 192));
-  const Fr chain_id = fe_to_mont(fe_load<FrParams>(in + 224));
+  const Fr nullifier = fe_to_mont(fe_load<FrParams>(in + W_NULLIFIER));
+  const Fr secret = fe_to_mont(fe_load<FrParams>(in + W_SECRET));
+  const Fr amount = fe_to_mont(fe_load<FrParams>(in + W_AMOUNT));
+  const Fr recipient = fe_to_mont(fe_load<FrParams>(in + W_RECIPIENT));
+  const uint64_t index = *reinterpret_cast<const uint64_t*>(in + W_INDEX);
+  const Fr token = fe_to_mont(fe_load<FrParams>(in + W_TOKEN));
+  const Fr chain_id = fe_to_mont(fe_load<FrParams>(in + W_CHAIN));
   ww.put_if(even, 0, Fr::one());
   ww.put_if(even, 3, recipient);
   ww.put_if(even, 4, amount);
@@ -204,7 +206,7 @@ __global__ void __launch_bounds__(64) k_withdraw_core_lat(const uint32_t* __rest
   const uint8_t* in = inputs + g * (size_t)(W_REC + depth) * 32;
   uint8_t* z = out + g * n_wires * 32;
   auto put = [&](bool mine, uint32_t wire, const Fr& v) { if (mine) fe_store(z + (size_t)wire * 32, v); };
-  const uint64_t index = *reinterpret_cast<const uint64_t*>(in + 160);
+  const uint64_t index = *reinterpret_cast<const uint64_t*>(in + W_INDEX);
   // wire layout of a gadget (oracle/py/withdraw.py): [selector (path levels only)] | 364 wires of E_0 | k1 | 364 wires of E_k1 | out
   // gadgets 0..2 take 730 wires, nullifier_hash 729 (its output is a public wire), a path level 731 (the selector in front)
   auto gadget_base = [&](int h) -> uint32_t { return first_gadget_wire + (h < 4 ? (uint32_t)h * 730u : 2919u + 731u * (uint32_t)(h - 4)); };
@@ -242,9 +244,9 @@ __global__ void __launch_bounds__(64) k_withdraw_core_lat(const uint32_t* __rest
     return x;
   };
   const Fr zero = Fr::zero();
-  const Fr nullifier = fe_to_mont(fe_load<FrParams>(in)), secret = fe_to_mont(fe_load<FrParams>(in + 32));
-  const Fr amount = fe_to_mont(fe_load<FrParams>(in + 64)), recipient = fe_to_mont(fe_load<FrParams>(in + 96));
-  const Fr token = fe_to_mont(fe_load<FrParams>(in + 192)), chain_id = fe_to_mont(fe_load<FrParams>(in + 224));
+  const Fr nullifier = fe_to_mont(fe_load<FrParams>(in + W_NULLIFIER)), secret = fe_to_mont(fe_load<FrParams>(in + W_SECRET));
+  const Fr amount = fe_to_mont(fe_load<FrParams>(in + W_AMOUNT)), recipient = fe_to_mont(fe_load<FrParams>(in + W_RECIPIENT));
+  const Fr token = fe_to_mont(fe_load<FrParams>(in + W_TOKEN)), chain_id = fe_to_mont(fe_load<FrParams>(in + W_CHAIN));
   if (pair == 0) {  // the wires that are inputs or squares of inputs
     put(even, 0, Fr::one()); put(even, 3, recipient); put(even, 4, amount); put(even, 5, token); put(even, 6, chain_id);
     put(even, 7, nullifier); put(even, 8, secret);
@@ -417,17 +419,17 @@ __global__ void __launch_bounds__(64) k_w9_first(const uint32_t* __restrict__ co
   const uint8_t* in = inputs + g * (size_t)(W_REC + depth) * 32;
   uint32_t* wl = wl_all + g * n_core * 9;
   uint32_t* xch = xch_all + g * (size_t)(depth + W9_XCH) * 9;
-  const uint64_t index = *reinterpret_cast<const uint64_t*>(in + 160);
+  const uint64_t index = *reinterpret_cast<const uint64_t*>(in + W_INDEX);
   if (job == 2 + depth) {  // the wires that are inputs or squares of inputs: lane-local values, a lane per wire
     const int lane = tid;
-    const Fr recipient = fe_to_mont(fe_load<FrParams>(in + 96)), chain_id = fe_to_mont(fe_load<FrParams>(in + 224));
+    const Fr recipient = fe_to_mont(fe_load<FrParams>(in + W_RECIPIENT)), chain_id = fe_to_mont(fe_load<FrParams>(in + W_CHAIN));
     if (lane == 0) w9_put_fe(wl, 0, Fr::one());
     if (lane == 1) w9_put_fe(wl, 3, recipient);
-    if (lane == 2) w9_put_fe(wl, 4, fe_to_mont(fe_load<FrParams>(in + 64)));
-    if (lane == 3) w9_put_fe(wl, 5, fe_to_mont(fe_load<FrParams>(in + 192)));
+    if (lane == 2) w9_put_fe(wl, 4, fe_to_mont(fe_load<FrParams>(in + W_AMOUNT)));
+    if (lane == 3) w9_put_fe(wl, 5, fe_to_mont(fe_load<FrParams>(in + W_TOKEN)));
     if (lane == 4) w9_put_fe(wl, 6, chain_id);
-    if (lane == 5) w9_put_fe(wl, 7, fe_to_mont(fe_load<FrParams>(in)));
-    if (lane == 6) w9_put_fe(wl, 8, fe_to_mont(fe_load<FrParams>(in + 32)));
+    if (lane == 5) w9_put_fe(wl, 7, fe_to_mont(fe_load<FrParams>(in + W_NULLIFIER)));
+    if (lane == 6) w9_put_fe(wl, 8, fe_to_mont(fe_load<FrParams>(in + W_SECRET)));
     if (lane == 7) w9_put_fe(wl, 9 + 2 * depth, fe_sqr(recipient));
     if (lane == 8) w9_put_fe(wl, 10 + 2 * depth, fe_sqr(chain_id));
     for (int l = lane; l < depth; l += 64) {
@@ -437,10 +439,10 @@ __global__ void __launch_bounds__(64) k_w9_first(const uint32_t* __restrict__ co
     return;
   }
   const uint32_t nj = w9_modulus_limb<FrParams>(lane);
-  const uint8_t* src = in;  // job 0: nullifier
+  const uint8_t* src = in + W_NULLIFIER;  // job 0
   uint32_t wbase = w9_gadget_base(fgw, 0), dup = w9_gadget_base(fgw, 3);
   int slot = depth;
-  if (job == 1) { src = in + 64; wbase = w9_gadget_base(fgw, 1); dup = 0; slot = depth + 1; }
+  if (job == 1) { src = in + W_AMOUNT; wbase = w9_gadget_base(fgw, 1); dup = 0; slot = depth + 1; }
   if (job >= 2) {
     const int lvl = job - 2;
     if (!((index >> lvl) & 1)) return;  // the path node is the LEFT input of this level: its first permutation is the chain's
@@ -472,8 +474,8 @@ __global__ void __launch_bounds__(64) k_w9_second(const uint32_t* __restrict__ c
   const uint32_t nj = w9_modulus_limb<FrParams>(lane);
   const uint32_t k1 = w9_load(xch + (size_t)(depth + (job == 1 ? 1 : 0)) * 9, lane);
   uint32_t r_in = 0;
-  if (job == 0) r_in = w9_spread(fe_to_mont(fe_load<FrParams>(in + 32)), lane);   // secret
-  if (job == 1) r_in = w9_spread(fe_to_mont(fe_load<FrParams>(in + 192)), lane);  // token
+  if (job == 0) r_in = w9_spread(fe_to_mont(fe_load<FrParams>(in + W_SECRET)), lane);
+  if (job == 1) r_in = w9_spread(fe_to_mont(fe_load<FrParams>(in + W_TOKEN)), lane);
   const uint32_t base = w9_gadget_base(fgw, job == 2 ? 3 : job);
   const uint32_t xr = w9_permute<FORM, false>(consts9, r_in, k1, nj, tid, lane, wl, base + 365, 0u, xch + (size_t)(depth + 4) * 9);
   const uint32_t hout = w9_renorm(2u * k1 + r_in + xr, nj, lane);
@@ -493,7 +495,7 @@ __global__ void __launch_bounds__(64) k_w9_chain(const uint32_t* __restrict__ co
   uint32_t* xch = xch_all + g * (size_t)(depth + W9_XCH) * 9;
   uint32_t* dump = xch + (size_t)(depth + 4) * 9;
   const uint32_t nj = w9_modulus_limb<FrParams>(lane);
-  const uint64_t index = *reinterpret_cast<const uint64_t*>(in + 160);
+  const uint64_t index = *reinterpret_cast<const uint64_t*>(in + W_INDEX);
   // H(l, r) from its first permutation on (have_k1: that one is already there), wires at base; the output below 2 N
   auto hash_rest = [&](uint32_t l_in, uint32_t r_in, bool have_k1, uint32_t k1, uint32_t base, int out_wire) -> uint32_t {
     if (!have_k1) {
@@ -565,7 +567,7 @@ __global__ void __launch_bounds__(256) k_withdraw_pad(const uint8_t* __restrict_
   const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
   if (u >= n_pad3 + n_seg) return;
   const size_t g = blockIdx.y;
-  const Fr seed = fe_load<FrParams>(inputs + g * (size_t)(W_REC + depth) * 32 + 128);
+  const Fr seed = fe_load<FrParams>(inputs + g * (size_t)(W_REC + depth) * 32 + W_PAD_SEED);
   WireWriter ww{out + g * n_wires * 32, 0};
   const Fr one = Fr::one(), two = fe_dbl(one);
   if (u < n_pad3) {
@@ -622,26 +624,14 @@ __global__ void __launch_bounds__(64) k_check_records(const uint8_t* __restrict_
   if (!ok) atomicMin(&bad[g], f);
 }
 
-const char* withdraw_field_name(uint32_t f) {
-  static const char* names[W_REC] = {"nullifier", "secret", "amount", "recipient", "pad_seed", "index", "token", "chain_id"};
-  return f < (uint32_t)W_REC ? names[f] : "sibling";
+static void withdraw_launch_check(og_ctx* ctx, const StatementArgs& a, const uint8_t* inputs_d, size_t n, uint32_t* bad_d) {
+  hipLaunchKernelGGL(k_check_records, dim3(grid_for(W_REC + a.depth, 64), (unsigned)n), dim3(64), 0, ctx->stream, inputs_d, a.depth, n, bad_d);
 }
 
-int withdraw_check_records(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, uint32_t* bad_d) {
-  OG_REQUIRE(depth >= 1 && depth <= 64, "withdraw: depth must be 1..64");
-  OG_REQUIRE(n <= 65535, "withdraw: at most 65535 records per call");  // (the record index is grid.y; checked HERE so that the caller gets this message, not a launch error)
-  if (n == 0) return OG_OK;
-  hipLaunchKernelGGL(k_check_records, dim3(grid_for(W_REC + depth, 64), (unsigned)n), dim3(64), 0, ctx->stream, inputs_d, depth, n, bad_d);
-  OG_HIP(hipGetLastError());
-  return OG_OK;
-}
-
-int withdraw_shape_query(int depth, uint64_t n_pad3, uint64_t n_pad2, uint64_t out[3]) {
-  OG_REQUIRE(depth >= 1 && depth <= 64, "withdraw: depth must be 1..64");
-  WithdrawShape s = withdraw_shape(depth, n_pad3, n_pad2);
-  OG_REQUIRE(s.n_wires < (1ull << 31), "withdraw: too many wires");
-  out[0] = s.n_wires; out[1] = s.n_constraints; out[2] = W_PUB;
-  return OG_OK;
+// the descriptor's view of the shape (statements.h); the witness launches below keep their own
+static RecordShape withdraw_record_shape(const StatementArgs& a) {
+  const WithdrawShape s = withdraw_shape(a.depth, a.n_pad3, a.n_pad2);
+  return RecordShape{s.n_wires, s.n_constraints, 0, s.first_gadget_wire, 0};
 }
 
 // ---- the walk on the HOST (round 6; opt-in: og_set_host_chains) ---------------------------------------------------------------------
@@ -663,10 +653,10 @@ static void withdraw_core_host(const H4* rc, const uint8_t* in, int depth, uint3
   auto put = [&](uint32_t wire, const H4& v) { memcpy(z + (size_t)wire * 32, v.v, 32); };
   auto ld = [&](const uint8_t* p) { return h4_to_mont(f, h4_load(p)); };
   const H4 zero = {{0, 0, 0, 0}};
-  const H4 nullifier = ld(in), secret = ld(in + 32), amount = ld(in + 64), recipient = ld(in + 96);
+  const H4 nullifier = ld(in + W_NULLIFIER), secret = ld(in + W_SECRET), amount = ld(in + W_AMOUNT), recipient = ld(in + W_RECIPIENT);
   uint64_t index = 0;
-  memcpy(&index, in + 160, 8);
-  const H4 token = ld(in + 192), chain_id = ld(in + 224);
+  memcpy(&index, in + W_INDEX, 8);
+  const H4 token = ld(in + W_TOKEN), chain_id = ld(in + W_CHAIN);
   put(0, f.one); put(3, recipient); put(4, amount); put(5, token); put(6, chain_id); put(7, nullifier); put(8, secret);
   for (int l = 0; l < depth; l++) {
     put(9 + l, ld(in + (size_t)(W_REC + l) * 32));
@@ -746,7 +736,9 @@ bool witness_walks_wave_wide(const og_ctx* ctx, size_t n) {
                                       : std::max(n, ctx->call_requests) <= (size_t)OG_HOOK_INT("OG_WITNESS_W9_MAX", 512);
 }
 
-int withdraw_witness(og_ctx* ctx, int depth, uint64_t n_pad3, uint64_t n_pad2, const uint8_t* inputs_d, size_t n, uint8_t* out_d) {
+static int withdraw_witness(const Statement&, og_ctx* ctx, const StatementArgs& a, const uint8_t* inputs_d, size_t n, uint8_t* out_d) {
+  const int depth = a.depth;
+  const uint64_t n_pad3 = a.n_pad3, n_pad2 = a.n_pad2;
   OG_REQUIRE(depth >= 1 && depth <= 64, "withdraw: depth must be 1..64");
   WithdrawShape s = withdraw_shape(depth, n_pad3, n_pad2);
   OG_REQUIRE(s.n_wires < (1ull << 31) && n_pad3 < (1ull << 30) && n_pad2 < (1ull << 30), "withdraw: too many wires");
@@ -869,33 +861,13 @@ __global__ void __launch_bounds__(64) k_check_deposit_records(const uint8_t* __r
   if (!fe_lt_modulus(fe_load<FrParams>(inputs + t * 32))) atomicMin(&bad[g], f);
 }
 
-int deposit_shape_query(uint64_t out[3]) {
-  out[0] = D_WIRES; out[1] = D_CONSTRAINTS; out[2] = D_PUB;
-  return OG_OK;
-}
+static RecordShape deposit_shape(const StatementArgs&) { return RecordShape{D_WIRES, D_CONSTRAINTS, 0, 0, 0}; }
 
-// OG_ERR_INVALID names the first malformed record (`base` = index of record 0 in the caller's batch); blocking
-int deposit_records_ok(og_ctx* ctx, const uint8_t* inputs_d, size_t n, size_t base) {
-  if (n == 0) return OG_OK;
-  uint32_t* bad_d = nullptr;
-  OG_TRY(arena_get(ctx, "dp.bad", n * 4, (void**)&bad_d));
-  OG_HIP(hipMemsetAsync(bad_d, 0xff, n * 4, ctx->stream));
+static void deposit_launch_check(og_ctx* ctx, const StatementArgs&, const uint8_t* inputs_d, size_t n, uint32_t* bad_d) {
   hipLaunchKernelGGL(k_check_deposit_records, dim3(grid_for(n * D_REC, 64)), dim3(64), 0, ctx->stream, inputs_d, n, bad_d);
-  OG_HIP(hipGetLastError());
-  std::vector<uint32_t> b(n);
-  OG_HIP(hipMemcpyAsync(b.data(), bad_d, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-  OG_HIP(hipStreamSynchronize(ctx->stream));
-  static const char* names[D_REC] = {"nullifier", "secret", "depositor"};
-  for (size_t g = 0; g < n; g++)
-    if (b[g] != 0xffffffffu) {
-      set_error("og_deposit: input record " + std::to_string(base + g) + ": field " + std::to_string(b[g]) + " (" + names[b[g] % D_REC] +
-                ") is not a canonical value (>= r)");
-      return OG_ERR_INVALID;
-    }
-  return OG_OK;
 }
 
-int deposit_witness(og_ctx* ctx, const uint8_t* inputs_d, size_t n, uint8_t* out_d) {
+static int deposit_witness(const Statement&, og_ctx* ctx, const StatementArgs&, const uint8_t* inputs_d, size_t n, uint8_t* out_d) {
   OG_REQUIRE(n <= 65535, "deposit: at most 65535 witnesses per call");
   if (n == 0) return OG_OK;
   ProfScope ps(ctx, PROF_WITNESS, (double)n);
@@ -961,8 +933,9 @@ constexpr int S_BITS = 128;
 constexpr int S_NULLIFIER = 0, S_SECRET = 32, S_AMOUNT = 64, S_RECIPIENT = 96, S_AMOUNT_OUT = 128, S_INDEX = 160, S_TOKEN = 192, S_CHAIN = 224,
               S_CHANGE_COMMITMENT = 256;
 
-static RecordShape split_shape(int depth) {
+static RecordShape split_shape(const StatementArgs& a) {
   RecordShape s{};
+  const int depth = a.depth;
   const uint64_t hashes = 6 + (uint64_t)depth;
   s.first_bit_wire = 1 + S_PUB + 5 + 2 * (uint64_t)depth + 2;
   s.first_gadget_wire = s.first_bit_wire + 2 * S_BITS;
@@ -1074,8 +1047,8 @@ __global__ void __launch_bounds__(64) k_check_split_records(const uint8_t* __res
   if (!ok) atomicMin(&bad[g], f);
 }
 
-static void split_launch_check(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, uint32_t* bad_d) {
-  hipLaunchKernelGGL(k_check_split_records, dim3(grid_for(S_REC + depth, 64), (unsigned)n), dim3(64), 0, ctx->stream, inputs_d, depth, n, bad_d);
+static void split_launch_check(og_ctx* ctx, const StatementArgs& a, const uint8_t* inputs_d, size_t n, uint32_t* bad_d) {
+  hipLaunchKernelGGL(k_check_split_records, dim3(grid_for(S_REC + a.depth, 64), (unsigned)n), dim3(64), 0, ctx->stream, inputs_d, a.depth, n, bad_d);
 }
 
 static void split_launch_core(og_ctx* ctx, int depth, const RecordShape& s, const uint8_t* inputs_d, size_t n, uint8_t* out_d) {
@@ -1108,8 +1081,9 @@ constexpr int J_PUB = 5;
 constexpr int J_REC = 11;  // fields of a join record before the siblings
 constexpr int J_BITS = 128;
 
-static RecordShape join_shape(int depth) {
+static RecordShape join_shape(const StatementArgs& a) {
   RecordShape s{};
+  const int depth = a.depth;
   const uint64_t hashes = 10 + 2 * (uint64_t)depth;
   s.first_bit_wire = 1 + J_PUB + 10 + 4 * (uint64_t)depth + 1;
   s.first_gadget_wire = s.first_bit_wire + 3 * J_BITS;
@@ -1280,8 +1254,8 @@ __global__ void __launch_bounds__(64) k_check_join_records(const uint8_t* __rest
   if (!ok) atomicMin(&bad[g], f);
 }
 
-static void join_launch_check(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, uint32_t* bad_d) {
-  hipLaunchKernelGGL(k_check_join_records, dim3(grid_for(J_REC + 2 * depth, 64), (unsigned)n), dim3(64), 0, ctx->stream, inputs_d, depth, n, bad_d);
+static void join_launch_check(og_ctx* ctx, const StatementArgs& a, const uint8_t* inputs_d, size_t n, uint32_t* bad_d) {
+  hipLaunchKernelGGL(k_check_join_records, dim3(grid_for(J_REC + 2 * a.depth, 64), (unsigned)n), dim3(64), 0, ctx->stream, inputs_d, a.depth, n, bad_d);
 }
 
 static void join_launch_core(og_ctx* ctx, int depth, const RecordShape& s, const uint8_t* inputs_d, size_t n, uint8_t* out_d) {
@@ -1315,8 +1289,9 @@ constexpr int T_BITS = 128;
 constexpr int T_NULLIFIER = 0, T_SECRET = 32, T_AMOUNT = 64, T_INDEX = 96, T_TOKEN = 128, T_CHAIN = 160, T_PAY_COMMITMENT = 192, T_PAY_AMOUNT = 224,
               T_CHANGE_COMMITMENT = 256;
 
-static RecordShape transfer_shape(int depth) {
+static RecordShape transfer_shape(const StatementArgs& a) {
   RecordShape s{};
+  const int depth = a.depth;
   const uint64_t hashes = 8 + (uint64_t)depth;
   s.first_bit_wire = 1 + T_PUB + 8 + 2 * (uint64_t)depth + 1;
   s.first_gadget_wire = s.first_bit_wire + 2 * T_BITS;
@@ -1644,8 +1619,8 @@ __global__ void __launch_bounds__(64) k_check_transfer_records(const uint8_t* __
   if (!ok) atomicMin(&bad[g], f);
 }
 
-static void transfer_launch_check(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, uint32_t* bad_d) {
-  hipLaunchKernelGGL(k_check_transfer_records, dim3(grid_for(T_REC + depth, 64), (unsigned)n), dim3(64), 0, ctx->stream, inputs_d, depth, n, bad_d);
+static void transfer_launch_check(og_ctx* ctx, const StatementArgs& a, const uint8_t* inputs_d, size_t n, uint32_t* bad_d) {
+  hipLaunchKernelGGL(k_check_transfer_records, dim3(grid_for(T_REC + a.depth, 64), (unsigned)n), dim3(64), 0, ctx->stream, inputs_d, a.depth, n, bad_d);
 }
 
 static void transfer_launch_core(og_ctx* ctx, int depth, const RecordShape& s, const uint8_t* inputs_d, size_t n, uint8_t* out_d) {
@@ -1985,48 +1960,75 @@ static void join_launch_w9(og_ctx* ctx, int depth, const RecordShape& s, const u
   OG_W9_LAUNCH(k_jw9_chain, w9_rows(), dim3((unsigned)(n * 4)), dim3(64), 0, ctx->stream, c9, inputs_d, depth, (size_t)s.n_wires, fgw, ngw, wl, xch);
 }
 
-// ---- the record statements: one descriptor each, and the host code they share (statements.h) ------------------------------------------
+// ---- the statements: one descriptor each, and the host code they share (statements.h) --------------------------------------------------
+static const char* const WITHDRAW_FIELDS[W_REC] = {"nullifier", "secret", "amount", "recipient", "pad_seed", "index", "token", "chain_id"};
+static const char* const DEPOSIT_FIELDS[D_REC] = {"nullifier", "secret", "depositor"};
 static const char* const SPLIT_FIELDS[S_REC] = {"nullifier", "secret", "amount", "recipient", "amount_out", "index", "token", "chain_id", "change_commitment"};
 static const char* const JOIN_FIELDS[J_REC] = {"nullifier_a", "secret_a", "amount_a", "index_a", "nullifier_b", "secret_b", "amount_b", "index_b",
                                                "token", "chain_id", "out_commitment"};
 static const char* const TRANSFER_FIELDS[T_REC] = {"nullifier", "secret", "amount", "index", "token", "chain_id", "pay_commitment", "pay_amount",
                                                    "change_commitment"};
+#define OG_RECORD_TAIL(what) "is not a valid value (>= r, an index outside the tree, an amount >= 2^128, " what ")"
 #ifndef __HIP_DEVICE_COMPILE__  // (host data: the device pass would emit the tables too, and has none of the functions they name)
-const RecordStatement ST_SPLIT = {"split", S_PUB, S_REC, 1, SPLIT_FIELDS, "or amount_out > amount", SW9_XCH, split_shape,
-                                  split_launch_check, split_launch_core, split_launch_w9, split_r1cs_rows};
-const RecordStatement ST_JOIN = {"join", J_PUB, J_REC, 2, JOIN_FIELDS, "amount_a + amount_b >= 2^128, or nullifier_b = nullifier_a", JW9_XCH, join_shape,
-                                 join_launch_check, join_launch_core, join_launch_w9, join_r1cs_rows};
-const RecordStatement ST_TRANSFER = {"transfer", T_PUB, T_REC, 1, TRANSFER_FIELDS, "or pay_amount > amount", TW9_XCH, transfer_shape,
-                                     transfer_launch_check, transfer_launch_core, transfer_launch_w9, transfer_r1cs_rows};
+const Statement ST_WITHDRAW = {"withdraw", W_PUB, W_REC, 1, WITHDRAW_FIELDS, "is not a canonical value (>= r, or an index outside the tree)",
+                               "this withdraw-circuit shape", withdraw_record_shape, withdraw_launch_check, withdraw_witness};
+const Statement ST_DEPOSIT = {"deposit", D_PUB, D_REC, 0, DEPOSIT_FIELDS, "is not a canonical value (>= r)", "the deposit statement",
+                              deposit_shape, deposit_launch_check, deposit_witness};
+const Statement ST_SPLIT = {"split", S_PUB, S_REC, 1, SPLIT_FIELDS, OG_RECORD_TAIL("or amount_out > amount"), "this split-statement shape", split_shape,
+                            split_launch_check, records_witness, SW9_XCH, split_launch_core, split_launch_w9, split_r1cs_rows};
+const Statement ST_JOIN = {"join", J_PUB, J_REC, 2, JOIN_FIELDS, OG_RECORD_TAIL("amount_a + amount_b >= 2^128, or nullifier_b = nullifier_a"),
+                           "this join-statement shape", join_shape, join_launch_check, records_witness, JW9_XCH, join_launch_core, join_launch_w9,
+                           join_r1cs_rows};
+const Statement ST_TRANSFER = {"transfer", T_PUB, T_REC, 1, TRANSFER_FIELDS, OG_RECORD_TAIL("or pay_amount > amount"), "this transfer-statement shape",
+                               transfer_shape, transfer_launch_check, records_witness, TW9_XCH, transfer_launch_core, transfer_launch_w9,
+                               transfer_r1cs_rows};
 #endif
 
-int records_shape_query(const RecordStatement& st, int depth, uint64_t out[3]) {
-  OG_REQUIRE(depth >= 1 && depth <= 64, std::string(st.name) + ": depth must be 1..64");
-  const RecordShape s = st.shape(depth);
+// the argument checks every call of a statement with a path makes (deposit has neither a depth nor a bound on its flat check grid)
+static int statement_args_ok(const Statement& st, const StatementArgs& a) {
+  OG_REQUIRE(st.paths == 0 || (a.depth >= 1 && a.depth <= 64), std::string(st.name) + ": depth must be 1..64");
+  return OG_OK;
+}
+
+int records_shape_query(const Statement& st, const StatementArgs& a, uint64_t out[3]) {
+  OG_TRY(statement_args_ok(st, a));
+  const RecordShape s = st.shape(a);
+  OG_REQUIRE(s.n_wires < (1ull << 31), std::string(st.name) + ": too many wires");  // (withdraw's padding alone can get there)
   out[0] = s.n_wires; out[1] = s.n_constraints; out[2] = (uint64_t)st.n_pub;
   return OG_OK;
 }
 
-int records_ok(const RecordStatement& st, og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, size_t base) {
-  OG_REQUIRE(depth >= 1 && depth <= 64, std::string(st.name) + ": depth must be 1..64");
-  OG_REQUIRE(n <= 65535, std::string(st.name) + ": at most 65535 records per call");  // (the record index is grid.y)
+int records_check_enqueue(const Statement& st, og_ctx* ctx, const StatementArgs& a, const uint8_t* inputs_d, size_t n, uint32_t* bad_d) {
+  OG_TRY(statement_args_ok(st, a));
+  // (the record index is grid.y; checked HERE so that the caller gets this message, not a launch error)
+  OG_REQUIRE(st.paths == 0 || n <= 65535, std::string(st.name) + ": at most 65535 records per call");
   if (n == 0) return OG_OK;
+  st.launch_check(ctx, a, inputs_d, n, bad_d);
+  OG_HIP(hipGetLastError());
+  return OG_OK;
+}
+
+// a sibling is named by its level, and with two paths by its path too: `sibling L`, or `sibling a L` / `sibling b L`
+std::string invalid_record_message(const Statement& st, const std::string& who, int depth, size_t g, uint32_t f) {
+  const uint32_t sib = f - (uint32_t)st.n_rec;
+  const std::string name = f < (uint32_t)st.n_rec ? std::string(st.field_names[f])
+                           : st.paths <= 1        ? "sibling " + std::to_string(sib)  // (no path: no division by a depth of 0)
+                                                  : std::string("sibling ") + (char)('a' + sib / depth) + " " + std::to_string(sib % depth);
+  return who + ": input record " + std::to_string(g) + ": field " + std::to_string(f) + " (" + name + ") " + st.invalid_tail;
+}
+
+int records_ok(const Statement& st, og_ctx* ctx, const StatementArgs& a, const uint8_t* inputs_d, size_t n, size_t base) {
+  if (n == 0) return OG_OK;  // (the witness entry that follows names a bad depth)
   uint32_t* bad_d = nullptr;
   OG_TRY(arena_get(ctx, "rec.bad", n * 4, (void**)&bad_d));
   OG_HIP(hipMemsetAsync(bad_d, 0xff, n * 4, ctx->stream));
-  st.launch_check(ctx, depth, inputs_d, n, bad_d);
-  OG_HIP(hipGetLastError());
+  OG_TRY(records_check_enqueue(st, ctx, a, inputs_d, n, bad_d));
   std::vector<uint32_t> bad(n);
   OG_HIP(hipMemcpyAsync(bad.data(), bad_d, n * 4, hipMemcpyDeviceToHost, ctx->stream));
   OG_HIP(hipStreamSynchronize(ctx->stream));
   for (size_t g = 0; g < n; g++)
     if (bad[g] != 0xffffffffu) {
-      const uint32_t f = bad[g], sib = f - (uint32_t)st.n_rec;  // (a sibling: path sib / depth, level sib % depth)
-      const std::string name = f < (uint32_t)st.n_rec ? std::string(st.field_names[f])
-                               : st.paths == 1        ? "sibling " + std::to_string(sib)
-                                                      : std::string("sibling ") + (char)('a' + sib / depth) + " " + std::to_string(sib % depth);
-      set_error("og_" + std::string(st.name) + ": input record " + std::to_string(base + g) + ": field " + std::to_string(f) + " (" + name +
-                ") is not a valid value (>= r, an index outside the tree, an amount >= 2^128, " + st.invalid_tail + ")");
+      set_error(invalid_record_message(st, "og_" + std::string(st.name), a.depth, base + g, bad[g]));
       return OG_ERR_INVALID;
     }
   return OG_OK;
@@ -2034,11 +2036,12 @@ int records_ok(const RecordStatement& st, og_ctx* ctx, int depth, const uint8_t*
 
 // The wave-wide walk for the calls witness_walks_wave_wide names -- its limb buffer is n x n_wires x 36 B from the arena --, the lane-local
 // kernel for batches: there a wave per permutation would be paid out of the prover's accumulations
-int records_witness(const RecordStatement& st, og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, uint8_t* out_d) {
-  OG_REQUIRE(depth >= 1 && depth <= 64, std::string(st.name) + ": depth must be 1..64");
+int records_witness(const Statement& st, og_ctx* ctx, const StatementArgs& a, const uint8_t* inputs_d, size_t n, uint8_t* out_d) {
+  OG_TRY(statement_args_ok(st, a));
   OG_REQUIRE(n <= 65535, std::string(st.name) + ": at most 65535 witnesses per call");
   if (n == 0) return OG_OK;
-  const RecordShape s = st.shape(depth);
+  const int depth = a.depth;
+  const RecordShape s = st.shape(a);
   ProfScope ps(ctx, PROF_WITNESS, (double)n);
   if (witness_walks_wave_wide(ctx, n)) {
     uint32_t *wl = nullptr, *xch = nullptr;
