@@ -40,6 +40,9 @@ extern "C" {
     fn og_shutdown(ctx: *mut og_ctx);
     fn og_last_error() -> *const c_char;
     fn og_pk_load(ctx: *mut og_ctx, blob: *const u8, len: usize, out: *mut *mut og_pk) -> c_int;
+    // the key with its OWPR0001 row-basis extension (include/owshen_gpu.h): the A / B queries over the QAP rows where that pays
+    fn og_pk_load_rows(ctx: *mut og_ctx, blob: *const u8, len: usize, rows: *const u8, rows_len: usize, out: *mut *mut og_pk) -> c_int;
+    fn og_pk_query_form(pk: *const og_pk, out: *mut u64) -> c_int;
     fn og_pk_free(pk: *mut og_pk);
     fn og_pk_info(pk: *const og_pk, info: *mut u64) -> c_int;
     fn og_pk_windows(pk: *const og_pk, out: *mut u64) -> c_int;
@@ -111,6 +114,17 @@ extern "C" {
         pk_len: *mut usize,
         vk_out: *mut *mut u8,
         vk_len: *mut usize,
+    ) -> c_int;
+    fn og_setup_rows(
+        ctx: *mut og_ctx,
+        r1cs: *const og_r1cs,
+        toxic: *const u8,
+        pk_out: *mut *mut u8,
+        pk_len: *mut usize,
+        vk_out: *mut *mut u8,
+        vk_len: *mut usize,
+        rows_out: *mut *mut u8,
+        rows_len: *mut usize,
     ) -> c_int;
     fn og_blob_free(blob: *mut u8);
     // the commitment tree fed by mint_tx (src/blockchain/tx/mint_tx.rs:11-49)

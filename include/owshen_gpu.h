@@ -272,6 +272,29 @@ int og_pk_density(const og_pk* pk, uint64_t out[4]);
 /* Window bits of the A, B, L and H queries' precomputed tables: a query of n points costs n x ceil(255 / bits) bucket
  * additions per proof (16 bits from 8 k points on, 17 bits from 160 k points on: owshen_amd/csrc/msm.hip). */
 int og_pk_windows(const og_pk* pk, uint64_t out[4]);
+/* The row-basis extension, "OWPR0001": key material BESIDE an OWPK0001 blob (the blob itself never changes), little-endian:
+ *   u64 x 4 : "OWPR0001", n_rows, log_d, 0
+ *   32 B    : Keccak-256 of the OWPK0001 blob it belongs to
+ *   [L_j(tau)]_1 for j < n_rows (64 B each) | [L_j(tau)]_2 for j < n_rows (128 B each), canonical affine
+ * L_j: the Lagrange basis of the key's domain.  With a_i(x) = sum_j A[j,i] L_j(x), sum_i z_i [a_i(tau)] = sum_j (A z)_j [L_j(tau)]
+ * -- the same group element, so the same proof bytes -- and the prover already has A z and B z for the quotient.  With the
+ * extension og_pk_load_rows decides per query, at load: the A query (and, once for its G1 and G2 copies, the B query) runs
+ * over the rows with an entry in its matrix when   rows x windows(rows) <= 0.8 x wires x windows(wires)
+ * (additions against additions; near-ties stay on the wires).  The L and H queries never change.  A key whose A / B queries
+ * hold clearly more wire bases than its matrices have non-empty rows gains; every other key loads exactly as og_pk_load
+ * loads it.  rows == NULL / rows_len == 0: og_pk_load.
+ * A wrong extension is refused, OG_ERR_INVALID, og_last_error naming the cause: its length or header, a digest that is not
+ * this blob's, and -- for an extension that will be used -- a coordinate >= q, a point off its curve, or points that do not
+ * reproduce the blob's own queries (one multi-scalar multiplication in each form per query and group, over a vector derived
+ * from the digest).  Uses the context's scratch: OG_ERR_INVALID while a submitted call is in flight.
+ *   og_setup_rows     og_setup, and the key's extension in *rows_out (malloc'd; og_blob_free) -- or NULL / 0 when the rule
+ *                     would keep both queries of this circuit on the wires.  og_setup_ptau and og_zkey_import make none.
+ *   og_pk_query_form  what the five queries A | B (G1) | B (G2) | L | H run, four words each: form (0 over the wires, 1 over the
+ *                     QAP rows), points (entries of its digit sort = points of its table), window bits, table (queries with
+ *                     the same number share one set of window tables: A and B (G1) in row form).  og_pk_density and
+ *                     og_pk_windows keep describing the blob's wire queries. */
+int og_pk_load_rows(og_ctx* ctx, const uint8_t* blob, size_t len, const uint8_t* rows, size_t rows_len, og_pk** out);
+int og_pk_query_form(const og_pk* pk, uint64_t out[20]);
 /* Witnesses in HOST memory (n x n_wires x 32 B; pageable is fine): each sub-batch is copied to the device inside the
  * prover's stage pipeline, under the accumulations of the sub-batch before it -- measured 510 proofs/s against 519 with
  * the same 2^18-wire witnesses already resident (og_prove_batch_d), 8.4 MB per proof over PCIe. */
@@ -616,6 +639,9 @@ int og_r1cs_info(const og_r1cs* r1cs, uint64_t info[6]);
 int og_r1cs_export(const og_r1cs* r1cs, int matrix, uint32_t* ptr_out, uint32_t* col_out, uint8_t* val_out);
 int og_setup(og_ctx* ctx, const og_r1cs* r1cs, const uint8_t toxic[160], uint8_t** pk_out, size_t* pk_len, uint8_t** vk_out,
              size_t* vk_len);
+/* og_setup plus the OWPR0001 row-basis extension of the key (see og_pk_load_rows) */
+int og_setup_rows(og_ctx* ctx, const og_r1cs* r1cs, const uint8_t toxic[160], uint8_t** pk_out, size_t* pk_len, uint8_t** vk_out,
+                  size_t* vk_len, uint8_t** rows_out, size_t* rows_len);
 void og_blob_free(uint8_t* blob);
 
 /* ---- snarkjs' files at the boundary (owshen_amd/csrc/zkey.hip; oracle/py/zkey.py restates the formats and is the oracle) ----

@@ -482,7 +482,29 @@ int og_pk_load(og_ctx* ctx, const uint8_t* blob, size_t len, og_pk** out) {
     *out = nullptr;
     LOCKED(ctx);
     OG_HIP(hipSetDevice(ctx->device));
-    return pk_load(ctx, blob, len, out);
+    return pk_load(ctx, blob, len, nullptr, 0, out);
+  });
+}
+
+int og_pk_load_rows(og_ctx* ctx, const uint8_t* blob, size_t len, const uint8_t* rows, size_t rows_len, og_pk** out) {
+  return guarded([&]() -> int {
+    CTX_OK(ctx);
+    OG_REQUIRE(blob != nullptr && out != nullptr, "og_pk_load_rows: null argument");
+    OG_REQUIRE(rows != nullptr || rows_len == 0, "og_pk_load_rows: null extension with a length");
+    *out = nullptr;
+    LOCKED(ctx);
+    OG_REQUIRE(ctx->jobs[0] == nullptr && ctx->jobs[1] == nullptr, "og_pk_load_rows: a submitted prove call has not been waited for (og_job_wait) -- its scratch is in use");
+    ctx->lane = 0;
+    ctx->stream = ctx->lanes[0];
+    return pk_load(ctx, blob, len, rows_len ? rows : nullptr, rows_len, out);
+  });
+}
+
+int og_pk_query_form(const og_pk* pk, uint64_t out[20]) {
+  return guarded([&]() -> int {
+    OG_REQUIRE(pk != nullptr && out != nullptr, "og_pk_query_form: null argument");
+    pk_query_form(pk, out);
+    return OG_OK;
   });
 }
 

@@ -15,6 +15,9 @@
 //   msm_digit_sort   signed 16-bit digits of z, counting-sorted once per DENSITY MAP: the A query, the B query
 //                    (its G1 and G2 copies share the sort) and the L query each keep only the wires whose
 //                    base is not the point at infinity (bellman's "query density")
+//                    A key loaded with its row-basis extension (og_pk_load_rows, key_blob.h) may run the A and / or the B query
+//                    over the QAP ROWS instead -- sum_j (A z)_j [L_j(tau)], the same group element: then that query's scalars
+//                    are the canonical copy of A z / B z that k_spmv leaves, sorted over the row map (og_pk::row, "the rule")
 //   msm_run x4       bucket accumulate + reduce over the compacted, precomputed window tables
 //   msm_digit_sort + msm_run   the H query over the quotient coefficients
 //   k_assemble_*     r/s blinding (s delta2 from a fixed-base table), final sums, affine conversion, 256 B proofs
@@ -50,6 +53,16 @@ struct og_pk {
   size_t n_dense[3] = {0, 0, 0};  // entries of the compact wire list (what the digit sort and the table hold)
   size_t n_real[3] = {0, 0, 0};   // ... of which bases that are not the point at infinity (og_pk_density)
   int sort_src[3] = {0, 1, 2};    // sort_src[q] = p < q: query q's wire list is query p's, and it reuses p's digit sort
+  // Row form (pk_load_impl, "the rule"): query q in {0 A, 1 B} runs over the QAP rows, sum_j (M z)_j [L_j(tau)], instead of the
+  // wires.  Then a / b1 (b2) ALIAS lag1 (lag2), the tables over the Lagrange points of the rows in `rmap` -- the rows with an
+  // entry in a matrix that runs in row form; a row that one of two such matrices lacks has (M z)_j = 0 there, no digit, and is
+  // never accumulated -- and map[q] aliases rmap.  The wire-form tables of such a query are not built.
+  bool row[3] = {false, false, false};
+  og_bases *lag1 = nullptr, *lag2 = nullptr;
+  uint32_t* rmap = nullptr;
+  size_t n_rowpts = 0;           // entries of rmap
+  size_t rows_q[2] = {0, 0};     // rows with an entry in A | B
+  int c_wire[3] = {0, 0, 0};     // window bits of the wire-form tables of A, B, L (og_pk_windows), built or not
   bool merge_lh = false;          // the L and H queries share one bucket set per proof (same window bits): C = sum z L + sum h H is ONE MSM
   bool c_is_ab = false;           // header flag 1 (an imported snarkjs key, zkey.hip): no C matrix, C z := (A z) o (B z) on the domain
   uint8_t* consts1 = nullptr;  // alpha1 | beta1 | delta1, affine Montgomery (3 x 64 B)
@@ -69,11 +82,14 @@ namespace og {
 // ---- sparse matrix x witness ---------------------------------------------------------
 // out[g][row] = sum_k val[k] * x[g][col[k]] for row < n_rows, 0 for n_rows <= row < n_out.
 // val_mont: values are in Montgomery form (product of a Montgomery value and a canonical x is
-// canonical); out_mont: convert the row sum to Montgomery form before storing.
+// canonical); out_mont: convert the row sum to Montgomery form before storing.  canon (optional): the sums of the rows < n_rows
+// once more, canonical, at canon[g][row] (canon_stride per g) -- the scalars of a query that runs over the rows (og_pk::row): the
+// digit sort wants canonical scalars, and the quotient destroys `out`.
 __global__ void __launch_bounds__(256) k_spmv(const uint32_t* __restrict__ ptr, const uint32_t* __restrict__ col,
                                              const uint8_t* __restrict__ val, size_t n_rows, size_t n_out,
                                              const uint8_t* __restrict__ x, size_t x_stride, uint8_t* __restrict__ out,
-                                             size_t out_stride, int val_mont, int out_mont, uint32_t long_row) {
+                                             size_t out_stride, int val_mont, int out_mont, uint32_t long_row,
+                                             uint8_t* __restrict__ canon, size_t canon_stride) {
   OG_FILLER_PRIO();
   size_t row = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (row >= n_out) return;
@@ -87,6 +103,7 @@ __global__ void __launch_bounds__(256) k_spmv(const uint32_t* __restrict__ ptr, 
       if (!val_mont) v = fe_to_mont(v);
       acc = fe_add(acc, fe_mul(v, fe_load<FrParams>(xg + (size_t)col[k] * 32)));
     }
+    if (canon) fe_store(canon + (size_t)g * canon_stride + row * 32, fe_canon(acc));
     acc = out_mont ? fe_to_mont(acc) : fe_canon(acc);
   }
   fe_store(out + (size_t)g * out_stride + row * 32, acc);
@@ -98,7 +115,8 @@ constexpr uint32_t SPMV_LONG = 2048;
 __global__ void __launch_bounds__(256) k_spmv_long(const uint32_t* __restrict__ rows, const uint32_t* __restrict__ ptr,
                                                   const uint32_t* __restrict__ col, const uint8_t* __restrict__ val,
                                                   const uint8_t* __restrict__ x, size_t x_stride, uint8_t* __restrict__ out,
-                                                  size_t out_stride, int val_mont, int out_mont) {
+                                                  size_t out_stride, int val_mont, int out_mont, uint8_t* __restrict__ canon,
+                                                  size_t canon_stride) {
   OG_FILLER_PRIO();
   __shared__ __align__(16) uint32_t part[256 * 8];
   const uint32_t row = rows[blockIdx.x];
@@ -119,6 +137,7 @@ __global__ void __launch_bounds__(256) k_spmv_long(const uint32_t* __restrict__ 
   }
   if (threadIdx.x == 0) {
     acc = fe_load<FrParams>(&part[0]);
+    if (canon) fe_store(canon + (size_t)g * canon_stride + (size_t)row * 32, fe_canon(acc));
     fe_store(out + (size_t)g * out_stride + (size_t)row * 32, out_mont ? fe_to_mont(acc) : fe_canon(acc));
   }
 }
@@ -195,7 +214,7 @@ int spmv_canonical(og_ctx* ctx, const uint32_t* ptr_d, const uint32_t* col_d, co
                    const uint8_t* x_d, uint8_t* out_d) {
   if (n_rows == 0) return OG_OK;
   hipLaunchKernelGGL(k_spmv, dim3(grid_for(n_rows, 256), 1), dim3(256), 0, ctx->stream, ptr_d, col_d, val_d, n_rows, n_rows, x_d,
-                     (size_t)0, out_d, (size_t)0, 0, 0, 0xffffffffu);
+                     (size_t)0, out_d, (size_t)0, 0, 0, 0xffffffffu, (uint8_t*)nullptr, (size_t)0);
   OG_HIP(hipGetLastError());
   return OG_OK;
 }
@@ -250,19 +269,93 @@ void pk_destroy(og_pk* pk) {
     if (pk->val[k]) (void)hipFree(pk->val[k]);
     if (pk->long_rows[k]) (void)hipFree(pk->long_rows[k]);
   }
-  bases_destroy(pk->a); bases_destroy(pk->b1); bases_destroy(pk->b2); bases_destroy(pk->l); bases_destroy(pk->h);
+  for (og_bases* q : {pk->a, pk->b1, pk->b2})
+    if (q != pk->lag1 && q != pk->lag2) bases_destroy(q);  // (a query in row form aliases the Lagrange tables)
+  bases_destroy(pk->lag1); bases_destroy(pk->lag2); bases_destroy(pk->l); bases_destroy(pk->h);
   for (int k = 0; k < 3; k++)
-    if (pk->map[k]) (void)hipFree(pk->map[k]);
+    if (pk->map[k] && pk->map[k] != pk->rmap) (void)hipFree(pk->map[k]);
+  if (pk->rmap) (void)hipFree(pk->rmap);
   if (pk->consts1) (void)hipFree(pk->consts1);
   if (pk->consts2) (void)hipFree(pk->consts2);
   if (pk->fb_delta2) (void)hipFree(pk->fb_delta2);
   delete pk;
 }
 
-static int pk_load_impl(og_ctx* ctx, const uint8_t* blob, size_t len, og_pk* pk) {
-  const std::string who = "og_pk_load";
+// The rule: a query runs over the rows when rows_q x windows(rows_q) <= 0.8 x wires_q x windows(wires_q) -- additions against
+// additions.  The 0.8 keeps near-ties on the wires: the wire form shares one digit sort of z with the L query (sort_src) and a
+// wire that holds 0 or 1 costs it none or one addition, a row sum is a full-width scalar in every window.
+bool row_form_pays(size_t rows_q, size_t wires_q) {
+  if (rows_q == 0 || wires_q == 0) return false;
+  const double row_adds = (double)rows_q * msm_nwin((int)msm_pick_query_c(rows_q));
+  const double wire_adds = (double)wires_q * msm_nwin((int)msm_pick_query_c(wires_q));
+  return row_adds <= 0.8 * wire_adds;
+}
+
+// Row form against wire form on the key's own points, once per load: for a pseudo-random vector rho (from the extension's digest;
+// the identity sum_i rho_i [m_i(tau)] = sum_j (M rho)_j [L_j(tau)] holds for EVERY rho) the query over the Lagrange tables
+// must give the point the blob's own query gives -- for each query that will run in row form, in each of its groups.  An
+// extension made for other points (a flipped bit that stays on the curve, another tau) fails here.
+static int rows_check(og_ctx* ctx, const og_pk* pk, const PkView& v, const RowsView& rv, uint8_t* stage, const std::string& who) {
+  const size_t m = pk->m, nr = pk->n_rows;
+  std::vector<uint8_t> rho(m * 32);
+  uint64_t x = rd64(rv.digest) ^ rd64(rv.digest + 8) ^ rd64(rv.digest + 16) ^ rd64(rv.digest + 24);
+  for (size_t i = 0; i < m * 4; i++) {  // splitmix64; the top word keeps 60 bits: < 2^252 < r, canonical
+    x += 0x9e3779b97f4a7c15ull;
+    uint64_t z = x;
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+    z ^= z >> 31;
+    if ((i & 3) == 3) z &= (1ull << 60) - 1;
+    memcpy(&rho[i * 8], &z, 8);
+  }
+  uint8_t *rho_d, *ev_d, *res_d, *aff_d;
+  OG_TRY(arena_get(ctx, "g16.chk.rho", m * 32, (void**)&rho_d));
+  OG_TRY(arena_get(ctx, "g16.chk.ev", nr * 32, (void**)&ev_d));
+  OG_TRY(arena_get(ctx, "g16.chk.res", 512, (void**)&res_d));
+  OG_TRY(arena_get(ctx, "g16.chk.aff", 256, (void**)&aff_d));
+  OG_HIP(hipMemcpyAsync(rho_d, rho.data(), m * 32, hipMemcpyHostToDevice, ctx->stream));
+  const int cw = (int)msm_pick_c(m);
+  struct Pair { int q, src, is_g2; const char* name; };
+  const Pair pairs[3] = {{0, 0, 0, "A"}, {1, 1, 0, "B (G1)"}, {1, 2, 1, "B (G2)"}};
+  for (const Pair& p : pairs) {
+    if (!pk->row[p.q]) continue;
+    const size_t pb = p.is_g2 ? 128 : 64;
+    hipLaunchKernelGGL(k_spmv, dim3(grid_for(nr, 256), 1), dim3(256), 0, ctx->stream, pk->ptr[p.q], pk->col[p.q], pk->val[p.q], nr, nr, rho_d,
+                       (size_t)0, ev_d, (size_t)0, 1, 0, SPMV_LONG, (uint8_t*)nullptr, (size_t)0);
+    OG_HIP(hipGetLastError());
+    if (pk->n_long[p.q]) {
+      hipLaunchKernelGGL(k_spmv_long, dim3(pk->n_long[p.q], 1), dim3(256), 0, ctx->stream, pk->long_rows[p.q], pk->ptr[p.q], pk->col[p.q],
+                         pk->val[p.q], rho_d, (size_t)0, ev_d, (size_t)0, 1, 0, (uint8_t*)nullptr, (size_t)0);
+      OG_HIP(hipGetLastError());
+    }
+    // the blob's query over every wire, as plain bases (a wire without a base is all zeros: infinity, skipped)
+    OG_HIP(hipMemcpyAsync(stage, v.query[p.src], m * pb, hipMemcpyHostToDevice, ctx->stream));
+    og_bases* wb = nullptr;
+    OG_TRY(bases_create(ctx, p.is_g2, stage, m, cw, 0, &wb));
+    struct Drop { og_bases* b; ~Drop() { bases_destroy(b); } } drop{wb};
+    DigitSort dw, dr;
+    OG_TRY(msm_digit_sort(ctx, 0, rho_d, m * 32, m, nullptr, 1, cw, 0, &dw));
+    OG_TRY(msm_run(ctx, wb, dw, res_d));
+    const og_bases* lag = p.is_g2 ? pk->lag2 : pk->lag1;
+    OG_TRY(msm_digit_sort(ctx, 1, ev_d, nr * 32, pk->n_rowpts, pk->rmap, 1, lag->c, 1, &dr));
+    OG_TRY(msm_run(ctx, lag, dr, res_d + 256));
+    OG_TRY(xyzz_to_affine_bytes(ctx, p.is_g2, res_d, aff_d, 1));
+    OG_TRY(xyzz_to_affine_bytes(ctx, p.is_g2, res_d + 256, aff_d + 128, 1));
+    uint8_t got[256];
+    OG_HIP(hipMemcpyAsync(got, aff_d, 256, hipMemcpyDeviceToHost, ctx->stream));
+    OG_HIP(hipStreamSynchronize(ctx->stream));  // (also: wb is idle before it is dropped)
+    OG_REQUIRE(memcmp(got, got + 128, pb) == 0,
+               who + ": row-basis extension: its points do not reproduce the key's " + p.name + " query (not the Lagrange basis of this key's tau)");
+  }
+  return OG_OK;
+}
+
+static int pk_load_impl(og_ctx* ctx, const uint8_t* blob, size_t len, const uint8_t* rows, size_t rows_len, og_pk* pk) {
+  const std::string who = rows ? "og_pk_load_rows" : "og_pk_load";
   PkView v;
   OG_TRY(pk_view(blob, len, who, &v));
+  RowsView rv{};
+  if (rows) OG_TRY(rows_view(rows, rows_len, v, who, &rv));  // (length, header, digest: before anything is allocated)
   OG_REQUIRE(v.flags <= 1 && v.word9 == 0, who + ": unknown header flags");
   OG_REQUIRE(!(v.flags & 1) || v.nnz[2] == 0, who + ": a key with the C = A o B flag carries no C matrix");
   OG_TRY(pk_csr_check(v, 3, who));  // (cheap, and a malformed key must never index out of bounds on the GPU)
@@ -296,7 +389,7 @@ static int pk_load_impl(og_ctx* ctx, const uint8_t* blob, size_t len, og_pk* pk)
   }
   // constants -> affine Montgomery
   uint8_t* stage = nullptr;
-  const size_t stage_bytes = std::max<size_t>(std::max<size_t>(512, m * 128), nh * 64);
+  const size_t stage_bytes = std::max<size_t>(std::max<size_t>(std::max<size_t>(512, m * 128), nh * 64), rows ? pk->n_rows * 128 : 0);
   OG_HIP(hipMalloc((void**)&stage, stage_bytes));
   struct Guard { uint8_t* p; ~Guard() { if (p) (void)hipFree(p); } } guard{stage};
   OG_HIP(hipMalloc((void**)&pk->consts1, 256));
@@ -330,8 +423,22 @@ static int pk_load_impl(og_ctx* ctx, const uint8_t* blob, size_t len, og_pk* pk)
   // the 7 public ones -> one sort instead of three (the three read and decompose the same witness).  The padding as built
   // (131 k | 117 k | 262 k wires) shares nothing; the natural statement shares A with L.
   for (int k = 0; k < 3; k++) pk->n_real[k] = wire[k].size();
+  // Wires or rows (row_form_pays), per query: A decides alone, B once for its two groups.  Hooks builds: OG_ROW_FORM=0|1 forces
+  // either form on every query the extension could serve (A/B runs).  L and H never change.
+  std::vector<uint32_t> rlist;
+  if (rows) {
+    const long long force = OG_HOOK_INT("OG_ROW_FORM", -1);
+    for (int q = 0; q < 2; q++) {
+      for (size_t r = 0; r < pk->n_rows; r++) pk->rows_q[q] += rd32(v.ptr[q] + (r + 1) * 4) > rd32(v.ptr[q] + r * 4);
+      pk->row[q] = pk->rows_q[q] > 0 && !wire[q].empty() && force != 0 && (force == 1 || row_form_pays(pk->rows_q[q], wire[q].size()));
+    }
+    for (size_t r = 0; r < pk->n_rows; r++)
+      if ((pk->row[0] && rd32(v.ptr[0] + (r + 1) * 4) > rd32(v.ptr[0] + r * 4)) || (pk->row[1] && rd32(v.ptr[1] + (r + 1) * 4) > rd32(v.ptr[1] + r * 4)))
+        rlist.push_back((uint32_t)r);
+  }
   for (int q = 1; q < 3; q++)
     for (int p0 = 0; p0 < q; p0++) {
+      if (pk->row[q] || pk->row[p0]) continue;  // a query over the rows has scalars of its own
       if (pk->sort_src[p0] != p0) continue;
       std::vector<uint32_t> u;
       std::set_union(wire[p0].begin(), wire[p0].end(), wire[q].begin(), wire[q].end(), std::back_inserter(u));
@@ -343,16 +450,45 @@ static int pk_load_impl(og_ctx* ctx, const uint8_t* blob, size_t len, og_pk* pk)
       pk->sort_src[q] = p0;
       break;
     }
+  pk->n_rowpts = rlist.size();
+  if (!rlist.empty()) {
+    OG_HIP(hipMalloc((void**)&pk->rmap, rlist.size() * 4 + 4));
+    OG_HIP(hipMemcpyAsync(pk->rmap, rlist.data(), rlist.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+  }
   for (int k = 0; k < 3; k++) {
+    pk->c_wire[k] = (int)msm_pick_query_c(wire[k].size());
+    if (pk->row[k]) {  // the row map; the wire list is not kept
+      pk->n_dense[k] = rlist.size();
+      pk->map[k] = pk->rmap;
+      continue;
+    }
     pk->n_dense[k] = wire[k].size();
     OG_HIP(hipMalloc((void**)&pk->map[k], wire[k].size() * 4 + 4));
     OG_HIP(hipMemcpyAsync(pk->map[k], wire[k].data(), wire[k].size() * 4, hipMemcpyHostToDevice, ctx->stream));
   }
   OG_HIP(hipStreamSynchronize(ctx->stream));
-  std::vector<uint8_t> host(std::max<size_t>(std::max<size_t>(1, m * 128), nh * 64));
+  std::vector<uint8_t> host(std::max<size_t>(std::max<size_t>(std::max<size_t>(1, m * 128), nh * 64), rlist.size() * 128));
+  if (!rlist.empty()) {
+    // ONE table per group over the Lagrange points of the rows in rlist: A and B1 share the G1 one.  The points are checked
+    // first -- every coordinate below q, every point on its curve -- and against the key's own queries below (rows_check).
+    for (int g2 = 0; g2 < (pk->row[1] ? 2 : 1); g2++) {
+      const size_t pb = g2 ? 128 : 64;
+      uint32_t flags = 0;
+      OG_TRY(points_on_curve(ctx, g2, g2 ? rv.g2 : rv.g1, pk->n_rows, &flags));
+      OG_REQUIRE(!(flags & 1), who + ": row-basis extension: a coordinate of a " + (g2 ? "G2" : "G1") + " point is not below the base-field modulus");
+      OG_REQUIRE(!(flags & 2), who + ": row-basis extension: a " + (g2 ? "G2" : "G1") + " point is not on its curve");
+      for (size_t k = 0; k < rlist.size(); k++) memcpy(host.data() + k * pb, (g2 ? rv.g2 : rv.g1) + (size_t)rlist[k] * pb, pb);
+      OG_HIP(hipMemcpyAsync(stage, host.data(), rlist.size() * pb, hipMemcpyHostToDevice, ctx->stream));
+      OG_TRY(bases_create(ctx, g2, stage, rlist.size(), (int)msm_pick_query_c(rlist.size()), 1, g2 ? &pk->lag2 : &pk->lag1));  // synchronises
+    }
+    if (pk->row[0]) pk->a = pk->lag1;
+    if (pk->row[1]) { pk->b1 = pk->lag1; pk->b2 = pk->lag2; }
+    OG_TRY(rows_check(ctx, pk, v, rv, stage, who));
+  }
   struct QSpec { int src, mapk, is_g2; og_bases** dst; };
   const QSpec qs[4] = {{0, 0, 0, &pk->a}, {1, 1, 0, &pk->b1}, {2, 1, 1, &pk->b2}, {3, 2, 0, &pk->l}};
   for (const QSpec& q : qs) {
+    if (pk->row[q.mapk]) continue;  // runs over the rows: no wire-form table
     const size_t pb = q.is_g2 ? 128 : 64;
     const std::vector<uint32_t>& w = wire[q.mapk];
     const size_t shift = q.src == 3 ? pk->n_pub + 1 : 0;  // l_query is indexed from wire n_pub + 1
@@ -393,10 +529,25 @@ void pk_info(const og_pk* pk, uint64_t out[4]) {
 
 // out[0..3] = window bits of the A, B (G1 and G2 copies), L and H queries' precomputed tables (msm_pick_query_c)
 void pk_windows(const og_pk* pk, uint64_t out[4]) {
-  out[0] = pk->a->c;
-  out[1] = pk->b1->c;
-  out[2] = pk->l->c;
+  for (int k = 0; k < 3; k++) out[k] = (uint64_t)pk->c_wire[k];  // (the blob's wire queries, also where one runs over the rows: pk_query_form)
   out[3] = pk->h->c;
+}
+
+// What each of the five queries A | B1 | B2 | L | H actually runs, four words each: form (0 over the wires, 1 over the QAP rows;
+// H: 0, over the quotient), points (the entries its digit sort visits and its table holds), window bits, table (queries with the
+// same number share ONE set of window tables: A and B1 in row form)
+void pk_query_form(const og_pk* pk, uint64_t out[20]) {
+  const og_bases* q[5] = {pk->a, pk->b1, pk->b2, pk->l, pk->h};
+  const int mapk[5] = {0, 1, 1, 2, -1};
+  for (int k = 0; k < 5; k++) {
+    out[4 * k + 0] = mapk[k] >= 0 && pk->row[mapk[k]] ? 1 : 0;
+    out[4 * k + 1] = q[k]->n;
+    out[4 * k + 2] = (uint64_t)q[k]->c;
+    int first = k;
+    for (int j = k - 1; j >= 0; j--)
+      if (q[j] == q[k]) first = j;
+    out[4 * k + 3] = (uint64_t)first;
+  }
 }
 
 // out[0..2] = bases kept by the A, B (G1 and G2 copies) and L queries after density compaction; out[3] = the H query's d - 1
@@ -408,16 +559,23 @@ void pk_density(const og_pk* pk, uint64_t out[4]) {
 // HBM bytes of the resident key: CSR matrices, the five queries' per-window tables, wire maps, constants
 uint64_t pk_bytes(const og_pk* pk) {
   uint64_t b = 0;
-  for (int k = 0; k < 3; k++) b += (pk->n_rows + 1) * 4 + pk->nnz[k] * 36 + 36 + (uint64_t)pk->n_long[k] * 4 + pk->n_dense[k] * 4 + 4;
-  for (const og_bases* q : {pk->a, pk->b1, pk->b2, pk->l, pk->h})
-    if (q) b += (uint64_t)(q->n ? q->n : 1) * (q->precomp ? q->nwin : 1) * (q->is_g2 ? 128 : 64);
+  for (int k = 0; k < 3; k++)
+    b += (pk->n_rows + 1) * 4 + pk->nnz[k] * 36 + 36 + (uint64_t)pk->n_long[k] * 4 + (pk->row[k] ? 0 : pk->n_dense[k] * 4 + 4);
+  if (pk->rmap) b += pk->n_rowpts * 4 + 4;
+  const og_bases* qs[5] = {pk->a, pk->b1, pk->b2, pk->l, pk->h};
+  for (int k = 0; k < 5; k++) {
+    const og_bases* q = qs[k];
+    if (!q || std::find(qs, qs + k, q) != qs + k) continue;  // (a shared table -- A and B1 over the rows -- counts once)
+    b += (uint64_t)(q->n ? q->n : 1) * (q->precomp ? q->nwin : 1) * (q->is_g2 ? 128 : 64);
+  }
   return b + 256 + 256 + 64 * 16 * 128;
 }
 
-int pk_load(og_ctx* ctx, const uint8_t* blob, size_t len, og_pk** out) {
+// rows (optional): the key's OWPR0001 row-basis extension (key_blob.h); a wrong one is refused, OG_ERR_INVALID
+int pk_load(og_ctx* ctx, const uint8_t* blob, size_t len, const uint8_t* rows, size_t rows_len, og_pk** out) {
   og_pk* pk = new og_pk();
   pk->device = ctx->device;
-  int r = pk_load_impl(ctx, blob, len, pk);
+  int r = pk_load_impl(ctx, blob, len, rows, rows_len, pk);
   if (r != OG_OK) {
     (void)hipStreamSynchronize(ctx->stream);
     pk_destroy(pk);
@@ -459,10 +617,22 @@ static int choose_sub_batch(og_ctx* ctx, const og_pk* pk, size_t n) {
   // the 288 GB -- the 2^18-wire circuit with 17-bit windows (2^16 buckets per set) is ~230 MB per proof, and 256 proofs per
   // sub-batch still fit -- and to what the device has left: (free memory + what this context's arena already holds) x 0.85
   // over the slots, so a GPU shared with other work gets smaller sub-batches instead of a failed allocation.
-  size_t pts = pk->d;
-  for (int q = 0; q < 3; q++)
-    if (pk->sort_src[q] == q) pts += pk->n_dense[q];
-  const size_t per = (size_t)pk->l->nwin * pts * 4 * 2 + pk->d * 32 * 5 + pk->m * 32 + ((size_t)1 << (pk->l->c - 1)) * (4 * 128 + 256) * 2;
+  // A query in row form sorts its own scalars at its own window count (the entries of rmap), keeps a canonical copy of its row
+  // sums (SubBatch::evc) and has the bucket set of ITS window bits.
+  size_t pts = pk->d, row_entries = 0, evc = 0;
+  const og_bases* wq[3] = {pk->a, pk->b1, pk->l};
+  int c_max = pk->l->c;
+  for (int q = 0; q < 3; q++) {
+    if (pk->row[q]) {
+      row_entries += (size_t)wq[q]->nwin * pk->n_dense[q];
+      evc += pk->n_rows * 32;
+      c_max = std::max(c_max, wq[q]->c);
+    } else if (pk->sort_src[q] == q) {
+      pts += pk->n_dense[q];
+    }
+  }
+  const size_t entries = (size_t)pk->l->nwin * pts + row_entries;
+  const size_t per = entries * 4 * 2 + pk->d * 32 * 5 + pk->m * 32 + evc + ((size_t)1 << (c_max - 1)) * (4 * 128 + 256) * 2;
   size_t budget = (size_t)64 << 30, free_b = 0, total_b = 0;
   if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && total_b) {
     size_t mine = 0;
@@ -758,6 +928,7 @@ struct SubBatch {
   int sb, slot;  // proofs; scratch namespace (ctx->lane) and, in the stage pipeline, event set
   const uint8_t* zs;
   uint8_t *ev[3], *tmp, *h;  // A z | B z | C z, quotient scratch, h
+  uint8_t* evc[2];           // A z | B z over the rows < n_rows once more, canonical (sub_rows): the scalars of a query in row form
   uint8_t* res(const ProveCall& c, int k) const { return c.res[k] + g0 * (k == 2 ? 256 : 128); }
   uint8_t* asm_tmp(const ProveCall& c) const { return c.asm_tmp + g0 * c.asm_lanes * 128 * 17; }  // (its products and tables: its own region)
   const uint8_t* glv(const ProveCall& c) const { return c.glv_d ? c.glv_d + g0 * 128 : nullptr; }
@@ -767,7 +938,12 @@ struct SubBatch {
 // slot 2; a sharded front sorts only this rank's windows k = rank (mod world)
 static int sub_sort(const ProveCall& c, const SubBatch& s, int slot, int q, DigitSort* out) {
   const og_pk* pk = c.pk;
-  return msm_digit_sort_windows(c.ctx, slot, s.zs, pk->m * 32, pk->n_dense[q], pk->map[q], s.sb, (q == 0 ? pk->a : q == 1 ? pk->b1 : pk->l)->c,
+  // the scalars: the witness through the query's wire map, or -- row form -- (A z) / (B z) through the row map.  The canonical
+  // copy sub_rows left, not ev[]: that one is in Montgomery form and the quotient destroys it, on another stream in two of the
+  // three schedules.  So the only order a row-form sort needs is "after sub_rows", and sub_rows is on its stream or behind ev0.
+  const uint8_t* scalars = q < 2 && pk->row[q] ? s.evc[q] : s.zs;
+  const size_t stride = q < 2 && pk->row[q] ? (size_t)pk->n_rows * 32 : pk->m * 32;
+  return msm_digit_sort_windows(c.ctx, slot, scalars, stride, pk->n_dense[q], pk->map[q], s.sb, (q == 0 ? pk->a : q == 1 ? pk->b1 : pk->l)->c,
                                 1, c.sh ? c.sh->rank : 0, c.sh ? c.sh->world : 1, out);
 }
 static int sub_sort_h(const ProveCall& c, const SubBatch& s, DigitSort* out) {
@@ -825,6 +1001,11 @@ static int sub_front(const ProveCall& c, SubBatch& s) {
   const size_t m = pk->m, d = pk->d, g0 = s.g0, sb_max = (size_t)c.plan.sb_max;
   const char* evn[3] = {"g16.eva", "g16.evb", "g16.evc"};
   for (int k = 0; k < 3; k++) OG_TRY(arena_get(ctx, evn[k], sb_max * d * 32, (void**)&s.ev[k]));
+  const char* evcn[2] = {"g16.eva.c", "g16.evb.c"};
+  for (int k = 0; k < 2; k++) {
+    s.evc[k] = nullptr;
+    if (pk->row[k]) OG_TRY(arena_get(ctx, evcn[k], sb_max * pk->n_rows * 32, (void**)&s.evc[k]));
+  }
   OG_TRY(arena_get(ctx, "g16.tmp", 32, (void**)&s.tmp));
   OG_TRY(arena_get(ctx, "g16.h", sb_max * d * 32, (void**)&s.h));
   s.zs = c.z_d ? c.z_d + g0 * m * 32 : nullptr;
@@ -867,12 +1048,13 @@ static int sub_rows(const ProveCall& c, const SubBatch& s) {
       OG_HIP(hipGetLastError());
       continue;
     }
+    uint8_t* canon = k < 2 && pk->row[k] ? s.evc[k] : nullptr;  // a query over the rows: its scalars, out of the quotient's way
     hipLaunchKernelGGL(k_spmv, dim3(grid_for(d, 256), sb), dim3(256), 0, ctx->stream, pk->ptr[k], pk->col[k], pk->val[k],
-                       (size_t)pk->n_rows, d, s.zs, m * 32, s.ev[k], d * 32, 1, 1, SPMV_LONG);
+                       (size_t)pk->n_rows, d, s.zs, m * 32, s.ev[k], d * 32, 1, 1, SPMV_LONG, canon, (size_t)pk->n_rows * 32);
     OG_HIP(hipGetLastError());
     if (pk->n_long[k]) {
       hipLaunchKernelGGL(k_spmv_long, dim3(pk->n_long[k], sb), dim3(256), 0, ctx->stream, pk->long_rows[k], pk->ptr[k], pk->col[k],
-                         pk->val[k], s.zs, m * 32, s.ev[k], d * 32, 1, 1);
+                         pk->val[k], s.zs, m * 32, s.ev[k], d * 32, 1, 1, canon, (size_t)pk->n_rows * 32);
       OG_HIP(hipGetLastError());
     }
   }
@@ -944,6 +1126,10 @@ static int issue_fan_out(const ProveCall& c, SubBatch& s) {
   ctx->lane = s.slot;
   ctx->stream = s0;
   OG_TRY(sub_front(c, s));
+  // a key with a query in row form: that query's scalars are A z / B z, so the sparse products come BEFORE the fan-out and ev0
+  // says "the witness and the row sums are complete" (the launch latency this puts in front of the side streams is three kernels')
+  const bool rows_first = pk->row[0] || pk->row[1];
+  if (rows_first) OG_TRY(sub_rows(c, s));
   OG_HIP(hipEventRecord(ctx->ev0, s0));  // the witness is complete
   DigitSort dsb, dsa, dsl, dh;
   OG_TRY(side(1, s_b2, ctx->ev0));
@@ -977,7 +1163,7 @@ static int issue_fan_out(const ProveCall& c, SubBatch& s) {
   OG_HIP(hipEventRecord(fan[FAN_L_DONE], s_l));
   ctx->lane = s.slot;
   ctx->stream = s0;
-  OG_TRY(sub_rows(c, s));
+  if (!rows_first) OG_TRY(sub_rows(c, s));
   OG_TRY(sub_quotient(c, s));
   OG_TRY(sub_sort_h(c, s, &dh));
   OG_TRY(msm_run_phase(ctx, pk->h, dh, s.res(c, 4), MSM_FULL));

@@ -188,5 +188,48 @@ inline void key_blobs(const KeyParts& k, const QapRows& rows, std::vector<uint8_
   vk.insert(vk.end(), k.ic, k.ic + (k.l + 1) * 64);
 }
 
+// ---- the row-basis extension (OWPR0001) -------------------------------------------------------------------------------------------
+// Key material BESIDE an OWPK0001 blob, never inside it: the Lagrange basis of the key's domain at tau in both groups, over the
+// QAP rows.  sum_i z_i [a_i(tau)] = sum_j (A z)_j [L_j(tau)], so a prover that holds these points may take the A and B queries
+// over the rows instead of the wires (groth16.hip pk_load).  All little-endian:
+//   u64 x 4 : magic, n_rows, log_d, 0
+//   32 B    : Keccak-256 of the OWPK0001 blob the extension belongs to
+//   [L_j(tau)]_1 for j < n_rows (64 B each) | [L_j(tau)]_2 for j < n_rows (128 B each), canonical affine
+constexpr uint64_t PR_MAGIC = 0x313030305250574full;  // "OWPR0001"
+constexpr size_t PR_HEADER = 32, PR_DIGEST = 32, PR_FIXED = 64;
+
+struct RowsView {
+  uint64_t n_rows, log_d;
+  const uint8_t *digest, *g1, *g2;  // 32 B | n_rows x 64 B | n_rows x 128 B
+};
+
+// structure and ownership: the header agrees with the key's, the length is the one the header implies, the digest is the key's
+inline int rows_view(const uint8_t* ext, size_t len, const PkView& pk, const std::string& who, RowsView* v) {
+  OG_REQUIRE(len >= PR_FIXED && rd64(ext) == PR_MAGIC, who + ": not an OWPR0001 row-basis extension");
+  v->n_rows = rd64(ext + 8);
+  v->log_d = rd64(ext + 16);
+  OG_REQUIRE(rd64(ext + 24) == 0, who + ": row-basis extension: unknown header word");
+  OG_REQUIRE(v->n_rows == pk.n_rows && v->log_d == pk.log_d, who + ": row-basis extension: n_rows / log_d are not the key's");
+  OG_REQUIRE(len == PR_FIXED + (size_t)v->n_rows * 192, who + ": row-basis extension: length does not match its header");
+  v->digest = ext + PR_HEADER;
+  v->g1 = ext + PR_FIXED;
+  v->g2 = v->g1 + (size_t)v->n_rows * 64;
+  uint8_t want[32];
+  keccak256(pk.blob, pk.len, want);
+  OG_REQUIRE(memcmp(v->digest, want, 32) == 0, who + ": row-basis extension: the digest is not this key's (another key's extension)");
+  return OG_OK;
+}
+
+inline void rows_blob(const std::vector<uint8_t>& pk, size_t n_rows, int log_d, const uint8_t* g1, const uint8_t* g2, std::vector<uint8_t>& out) {
+  out.clear();
+  const uint64_t head[4] = {PR_MAGIC, n_rows, (uint64_t)log_d, 0};
+  out.insert(out.end(), (const uint8_t*)head, (const uint8_t*)head + PR_HEADER);
+  uint8_t dg[32];
+  keccak256(pk.data(), pk.size(), dg);
+  out.insert(out.end(), dg, dg + 32);
+  out.insert(out.end(), g1, g1 + n_rows * 64);
+  out.insert(out.end(), g2, g2 + n_rows * 128);
+}
+
 }  // namespace
 }  // namespace og

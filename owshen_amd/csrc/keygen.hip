@@ -416,7 +416,10 @@ void csr_transpose(const std::vector<uint32_t>& ptr, const std::vector<uint32_t>
     }
 }
 
-static int keygen_setup(og_ctx* ctx, const og_r1cs* r, const uint8_t toxic[160], std::vector<uint8_t>& pk, std::vector<uint8_t>& vk) {
+// rows_ext (optional): the OWPR0001 row-basis extension of the key (key_blob.h), left EMPTY when neither the A nor the B query
+// of this circuit would run over the rows (row_form_pays, the rule pk_load applies): then the points are never read
+static int keygen_setup(og_ctx* ctx, const og_r1cs* r, const uint8_t toxic[160], std::vector<uint8_t>& pk, std::vector<uint8_t>& vk,
+                        std::vector<uint8_t>* rows_ext = nullptr) {
   const size_t m = r->n_wires, l = r->n_pub, nc = r->n_constraints, n_rows = nc + l + 1;
   QapRows rows;
   OG_TRY(r1cs_qap_rows(r, "og_setup", &rows));
@@ -471,7 +474,7 @@ static int keygen_setup(og_ctx* ctx, const og_r1cs* r, const uint8_t toxic[160],
   Job jobs[8] = {{0, at_d[0], m, {}}, {0, at_d[1], m, {}}, {1, at_d[1], m, {}}, {0, l_s, nl, {}}, {0, h_s, nh, {}},
                  {0, ic_s, l + 1, {}}, {0, toxic_d + 32, 4, {}}, {1, toxic_d + 32, 4, {}}};
   uint8_t* pts_d;
-  OG_TRY(dev.get(std::max<size_t>(std::max<size_t>(m * 128, nh * 64), 512), &pts_d));
+  OG_TRY(dev.get(std::max<size_t>(std::max<size_t>(std::max<size_t>(m * 128, nh * 64), n_rows * 128), 512), &pts_d));
   for (Job& j : jobs) {
     const size_t pb = j.is_g2 ? 128 : 64;
     j.out.resize(j.n * pb);
@@ -488,6 +491,25 @@ static int keygen_setup(og_ctx* ctx, const og_r1cs* r, const uint8_t toxic[160],
   for (int q = 0; q < 5; q++) parts.query[q] = jobs[q].out.data();
   parts.ic = jobs[5].out.data();
   key_blobs(parts, rows, pk, vk);
+  if (rows_ext) {
+    rows_ext->clear();
+    bool pays = OG_HOOK_INT("OG_ROW_FORM", -1) == 1;  // (hooks builds: the form pk_load can then be forced into)
+    for (int k = 0; k < 2; k++) {  // A | B: rows with an entry against wires with one
+      std::vector<uint8_t> seen(m, 0);
+      size_t rows_q = 0, wires_q = 0;
+      for (size_t row = 0; row < n_rows; row++) rows_q += rows.ptr[k][row + 1] > rows.ptr[k][row];
+      for (uint32_t c : rows.col[k]) wires_q += !seen[c]++;
+      pays = pays || row_form_pays(rows_q, wires_q);
+    }
+    if (pays) {  // [L_j(tau)] in both groups: the Lagrange evaluations are still in lag_d
+      std::vector<uint8_t> g1(n_rows * 64), g2(n_rows * 128);
+      OG_TRY(scalar_mul_fixed(ctx, 0, G1_GEN_BYTES, lag_d, n_rows, pts_d));  // synchronises
+      OG_HIP(hipMemcpy(g1.data(), pts_d, g1.size(), hipMemcpyDeviceToHost));
+      OG_TRY(scalar_mul_fixed(ctx, 1, G2_GEN_BYTES, lag_d, n_rows, pts_d));
+      OG_HIP(hipMemcpy(g2.data(), pts_d, g2.size(), hipMemcpyDeviceToHost));
+      rows_blob(pk, n_rows, log_d, g1.data(), g2.data(), *rows_ext);
+    }
+  }
   return OG_OK;
 }
 
@@ -595,29 +617,48 @@ int og_r1cs_export(const og_r1cs* r, int matrix, uint32_t* ptr_out, uint32_t* co
   });
 }
 
-int og_setup(og_ctx* ctx, const og_r1cs* r1cs, const uint8_t toxic[160], uint8_t** pk_out, size_t* pk_len, uint8_t** vk_out, size_t* vk_len) {
+static int setup_entry(const char* who, og_ctx* ctx, const og_r1cs* r1cs, const uint8_t toxic[160], uint8_t** pk_out, size_t* pk_len, uint8_t** vk_out,
+                       size_t* vk_len, uint8_t** rows_out, size_t* rows_len) {
   return guarded([&]() -> int {
-    OG_REQUIRE(ctx && r1cs && toxic && pk_out && pk_len && vk_out && vk_len, "og_setup: null argument");
+    OG_REQUIRE(ctx && r1cs && toxic && pk_out && pk_len && vk_out && vk_len, std::string(who) + ": null argument");
     *pk_out = *vk_out = nullptr;
     *pk_len = *vk_len = 0;
+    if (rows_out) { *rows_out = nullptr; *rows_len = 0; }
     std::lock_guard<std::mutex> lk(ctx->mu);
     OG_HIP(hipSetDevice(ctx->device));
-    std::vector<uint8_t> pk, vk;
-    OG_TRY(keygen_setup(ctx, r1cs, toxic, pk, vk));
+    std::vector<uint8_t> pk, vk, ext;
+    OG_TRY(keygen_setup(ctx, r1cs, toxic, pk, vk, rows_out ? &ext : nullptr));
     uint8_t* a = static_cast<uint8_t*>(malloc(pk.size() ? pk.size() : 1));
     uint8_t* b = static_cast<uint8_t*>(malloc(vk.size() ? vk.size() : 1));
-    if (!a || !b) {
+    uint8_t* e = ext.empty() ? nullptr : static_cast<uint8_t*>(malloc(ext.size()));
+    if (!a || !b || (!ext.empty() && !e)) {
       free(a);
       free(b);
-      set_error("og_setup: out of host memory");
+      free(e);
+      set_error(std::string(who) + ": out of host memory");
       return OG_ERR_INVALID;
     }
     memcpy(a, pk.data(), pk.size());
     memcpy(b, vk.data(), vk.size());
+    if (e) memcpy(e, ext.data(), ext.size());
     *pk_out = a; *pk_len = pk.size();
     *vk_out = b; *vk_len = vk.size();
+    if (rows_out) { *rows_out = e; *rows_len = ext.size(); }
     return OG_OK;
   });
+}
+
+int og_setup(og_ctx* ctx, const og_r1cs* r1cs, const uint8_t toxic[160], uint8_t** pk_out, size_t* pk_len, uint8_t** vk_out, size_t* vk_len) {
+  return setup_entry("og_setup", ctx, r1cs, toxic, pk_out, pk_len, vk_out, vk_len, nullptr, nullptr);
+}
+
+int og_setup_rows(og_ctx* ctx, const og_r1cs* r1cs, const uint8_t toxic[160], uint8_t** pk_out, size_t* pk_len, uint8_t** vk_out, size_t* vk_len,
+                  uint8_t** rows_out, size_t* rows_len) {
+  if (!rows_out || !rows_len) {
+    set_error("og_setup_rows: null argument");
+    return OG_ERR_INVALID;
+  }
+  return setup_entry("og_setup_rows", ctx, r1cs, toxic, pk_out, pk_len, vk_out, vk_len, rows_out, rows_len);
 }
 
 void og_blob_free(uint8_t* blob) { free(blob); }

@@ -235,7 +235,7 @@ static int multi_pk_load(og_multi* m, const uint8_t* blob, size_t len, og_pk** p
   for (int r = 0; r < m->n; r++) pks_out[r] = nullptr;
   int rc = for_each_device(m, [&](int r) -> int {
     std::lock_guard<std::mutex> lk(m->ctx[r]->mu);
-    return pk_load(m->ctx[r], blob, len, &pks_out[r]);
+    return pk_load(m->ctx[r], blob, len, nullptr, 0, &pks_out[r]);
   }, "pk_load");
   if (rc != OG_OK)
     for (int r = 0; r < m->n; r++) {

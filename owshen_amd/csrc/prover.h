@@ -22,9 +22,19 @@ int spmv_canonical(og_ctx* ctx, const uint32_t* ptr_d, const uint32_t* col_d, co
 int lagrange_evals(og_ctx* ctx, int log_d, const uint8_t tau[32], uint8_t* out_d);
 int scalar_mul_fixed(og_ctx* ctx, int is_g2, const uint8_t* base_host, const uint8_t* scalars_d, size_t n, uint8_t* out_d);
 
+// ---- ptau.hip -------------------------------------------------------------------------------------------------------------------------
+// n canonical affine points on the host, checked on the device: *flags |= 1 a coordinate >= q, |= 2 a point off its curve
+int points_on_curve(og_ctx* ctx, int is_g2, const uint8_t* points, size_t n, uint32_t* flags);
+
 // ---- groth16.hip: the proving key (the serialized key: key_blob.h) ----------------------------------------------------------------------
-int pk_load(og_ctx* ctx, const uint8_t* blob, size_t len, og_pk** out);
+// rows (optional, rows_len bytes): the key's OWPR0001 row-basis extension; a wrong one is refused, OG_ERR_INVALID
+int pk_load(og_ctx* ctx, const uint8_t* blob, size_t len, const uint8_t* rows, size_t rows_len, og_pk** out);
 void pk_destroy(og_pk* pk);
+// the rule of pk_load: does a query with rows_q non-empty rows and wires_q bases run over the rows?  (key generation asks too:
+// it makes no extension that no load would use)
+bool row_form_pays(size_t rows_q, size_t wires_q);
+// what each of the five queries A | B1 | B2 | L | H runs: form (0 wires, 1 rows), points, window bits, table number -- 4 words each
+void pk_query_form(const og_pk* pk, uint64_t out[20]);
 // out[0..3] = n_wires, n_pub, log_d, n_rows: the key's header
 void pk_info(const og_pk* pk, uint64_t out[4]);
 // out[0..3] = window bits of the A, B (G1 and G2 copies), L and H queries' precomputed tables (msm_pick_query_c)

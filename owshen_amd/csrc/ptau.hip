@@ -32,6 +32,7 @@
 #include "key_blob.h"
 #include "mimc7.hip.h"
 #include "msm.hip.h"
+#include "prover.h"
 #include "verify_tower.h"
 #include <string.h>
 #include <stdlib.h>
@@ -603,6 +604,12 @@ static int canon_to_mont(og_ctx* ctx, ZDev& dev, const uint8_t* in, size_t n, ui
   return lem_run(ctx, dev, Affine<T>::BYTES == 128, false, in, n, nullptr, *mont_d, flags, [&](uint8_t* in_d, uint8_t* c_d, uint8_t* out_d, uint32_t* f_d) {
     hipLaunchKernelGGL(k_canon_to_mont<T>, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, in_d, n, c_d + 32, out_d, f_d);
   });
+}
+
+int points_on_curve(og_ctx* ctx, int is_g2, const uint8_t* points, size_t n, uint32_t* flags) {
+  ZDev dev;
+  uint8_t* mont_d = nullptr;
+  return is_g2 ? canon_to_mont<Fq2>(ctx, dev, points, n, &mont_d, flags) : canon_to_mont<Fq>(ctx, dev, points, n, &mont_d, flags);
 }
 
 static int pk_verify(og_ctx* ctx, const og_r1cs* r, const uint8_t* data, size_t len, const uint8_t* pkb, size_t pk_len, const uint8_t* vkb, size_t vk_len,

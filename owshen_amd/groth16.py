@@ -153,10 +153,18 @@ def vk_from_bytes(blob):
     return out
 
 
+class ProvingKeyBlob(bytes):
+    """An "OWPK0001" blob -- the bytes are the blob, nothing else: len, slicing, hashing and from_buffer_copy see a plain bytes --
+    that carries the key's "OWPR0001" row-basis extension beside it (include/owshen_gpu.h, og_pk_load_rows) as `.rows`: bytes,
+    or None for a key whose A and B queries stay on the wires.  A slice or a copy through bytes() is a plain blob again."""
+    rows = None
+
+
 def setup(ctx, r1cs, tau, alpha, beta, gamma, delta):
     """Key generation from explicit toxic waste (tests / benchmarks; a production key comes from a ceremony), run by the
-    library (og_setup: Lagrange evaluations, transposed sparse products, query scalars and the fixed-base multiplications on
-    the GPU).  Returns (proving key blob: bytes, verifying key: dict of bytes / np arrays)."""
+    library (og_setup_rows: Lagrange evaluations, transposed sparse products, query scalars and the fixed-base multiplications on
+    the GPU).  Returns (proving key blob: ProvingKeyBlob -- bytes, with the row-basis extension as `.rows` where the library made
+    one --, verifying key: dict of bytes / np arrays)."""
     for v in (tau, alpha, beta, gamma, delta):
         assert 0 < v < R
     lib = ctx._lib
@@ -165,14 +173,18 @@ def setup(ctx, r1cs, tau, alpha, beta, gamma, delta):
     try:
         toxic = (C.c_uint8 * 160).from_buffer_copy(b"".join(_le(v) for v in (tau, alpha, beta, gamma, delta)))
         pk_p, vk_p, pk_n, vk_n = C.c_void_p(), C.c_void_p(), C.c_size_t(), C.c_size_t()
+        ext_p, ext_n = C.c_void_p(), C.c_size_t()
         ctx._pre()
-        ctx._check(lib.og_setup(ctx._h, h, toxic, C.byref(pk_p), C.byref(pk_n), C.byref(vk_p), C.byref(vk_n)))
+        ctx._check(lib.og_setup_rows(ctx._h, h, toxic, C.byref(pk_p), C.byref(pk_n), C.byref(vk_p), C.byref(vk_n), C.byref(ext_p), C.byref(ext_n)))
         try:
-            pk = C.string_at(pk_p, pk_n.value)
+            pk = ProvingKeyBlob(C.string_at(pk_p, pk_n.value))
             vk = C.string_at(vk_p, vk_n.value)
+            if ext_p.value and ext_n.value:
+                pk.rows = C.string_at(ext_p, ext_n.value)
         finally:
             lib.og_blob_free(pk_p)
             lib.og_blob_free(vk_p)
+            lib.og_blob_free(ext_p)
     finally:
         lib.og_r1cs_free(h)
     return pk, vk_from_bytes(vk)
@@ -185,7 +197,13 @@ class ProvingKey:
         self.ctx = ctx
         h = C.c_void_p()
         buf = (C.c_uint8 * len(blob)).from_buffer_copy(blob)
-        ctx._check(ctx._lib.og_pk_load(ctx._h, buf, len(blob), C.byref(h)))
+        rows = getattr(blob, "rows", None)
+        if rows:     # a key of `setup` with its row-basis extension: the A / B queries over the QAP rows where that pays
+            ext = (C.c_uint8 * len(rows)).from_buffer_copy(rows)
+            ctx._pre()
+            ctx._check(ctx._lib.og_pk_load_rows(ctx._h, buf, len(blob), ext, len(rows), C.byref(h)))
+        else:
+            ctx._check(ctx._lib.og_pk_load(ctx._h, buf, len(blob), C.byref(h)))
         self._h = h
         info = (C.c_uint64 * 4)()
         ctx._check(ctx._lib.og_pk_info(h, info))
@@ -215,6 +233,15 @@ class ProvingKey:
         d = (C.c_uint64 * 4)()
         self.ctx._check(self.ctx._lib.og_pk_windows(self._h, d))
         return dict(zip(("a", "b", "l", "h"), (int(x) for x in d)))
+
+    def query_forms(self):
+        """what each of the five queries actually runs (og_pk_query_form): {"a" | "b1" | "b2" | "l" | "h": {"form": "wire" | "row",
+        "points", "bits", "table"}}; queries with the same "table" share one set of window tables"""
+        d = (C.c_uint64 * 20)()
+        self.ctx._check(self.ctx._lib.og_pk_query_form(self._h, d))
+        names = ("a", "b1", "b2", "l", "h")
+        return {q: {"form": "row" if d[4 * k] else "wire", "points": int(d[4 * k + 1]), "bits": int(d[4 * k + 2]), "table": names[int(d[4 * k + 3])]}
+                for k, q in enumerate(names)}
 
     @staticmethod
     def _rs_bytes(rs):
