@@ -289,10 +289,21 @@ int og_pk_windows(const og_pk* pk, uint64_t out[4]);
  * from the digest).  Uses the context's scratch: OG_ERR_INVALID while a submitted call is in flight.
  *   og_setup_rows     og_setup, and the key's extension in *rows_out (malloc'd; og_blob_free) -- or NULL / 0 when the rule
  *                     would keep both queries of this circuit on the wires.  og_setup_ptau and og_zkey_import make none.
- *   og_pk_query_form  what the five queries A | B (G1) | B (G2) | L | H run, four words each: form (0 over the wires, 1 over the
- *                     QAP rows), points (entries of its digit sort = points of its table), window bits, table (queries with
- *                     the same number share one set of window tables: A and B (G1) in row form).  og_pk_density and
- *                     og_pk_windows keep describing the blob's wire queries. */
+ *   og_pk_query_form  what the five queries A | B (G1) | B (G2) | L | H run, four words each: form (OG_QUERY_FORM_*), points
+ *                     (entries of its digit sort = points of its table), window bits, table (queries with the same number
+ *                     share one set of window tables: A and B (G1) in row form).  og_pk_density and og_pk_windows keep
+ *                     describing the blob's wire queries.
+ * The evaluation form of the quotient is decided at load too, by og_pk_load and og_pk_load_rows alike and from the blob alone: a
+ * key that has a C matrix and a domain of 2^14 or more keeps h on the coset -- its H tables hold the DFT of the H query (d
+ * points), its L tables L_i + [the fold of C's column i] over the L wires and every other wire of C -- so that a proof takes
+ * four transforms instead of seven.  The same group elements, the same proof bytes; a derived table that does not reproduce the
+ * blob's own L and H queries fails the load, OG_ERR_INVALID.  Such a key reports OG_QUERY_FORM_EVAL for L and H.  That
+ * load-time check uses the context's scratch, as og_pk_load_rows' does: for a key that takes this form og_pk_load and
+ * og_pk_load_rows answer OG_ERR_INVALID while a submitted call is in flight (og_job_wait it first); a key that stays in
+ * the coefficient form loads through og_pk_load beside a pending job as before. */
+#define OG_QUERY_FORM_WIRE 0 /* over the wires (H: over the quotient's coefficients) */
+#define OG_QUERY_FORM_ROW 1  /* A, B: over the QAP rows */
+#define OG_QUERY_FORM_EVAL 2 /* L, H: H over the coset values of (A z)(B z), C z folded into L */
 int og_pk_load_rows(og_ctx* ctx, const uint8_t* blob, size_t len, const uint8_t* rows, size_t rows_len, og_pk** out);
 int og_pk_query_form(const og_pk* pk, uint64_t out[20]);
 /* Witnesses in HOST memory (n x n_wires x 32 B; pageable is fine): each sub-batch is copied to the device inside the
@@ -571,8 +582,8 @@ int og_transfer_prove_batch_d(og_ctx* ctx, const og_pk* pk, int depth, const uin
  * Submit itself never proves: also a call that fits one sub-batch enqueues its witnesses with the rest and returns (until the
  * end of round 6 a small statement's witnesses were generated before the enqueue, with the host waiting for them).
  * While a thread is inside og_job_wait for a job, og_job_abandon and a second og_job_wait on that job are refused, and
- * og_shutdown waits for the waiter; og_msm_d / og_msm_windows_d / og_msm_combine_d are refused while a submitted call is
- * pending (they use the same scratch). */
+ * og_shutdown waits for the waiter; og_msm_d / og_msm_windows_d / og_msm_combine_d, og_pk_load_rows and og_pk_load of a key that
+ * takes the evaluation form are refused while a submitted call is pending (they use the same scratch). */
 typedef struct og_job og_job;
 int og_withdraw_prove_batch_submit_d(og_ctx* ctx, const og_pk* pk, int depth, uint64_t n_pad3, uint64_t n_pad2,
                                      const uint8_t* inputs_d, size_t n, const uint8_t* rs, uint8_t* proofs_out,

@@ -12,6 +12,8 @@
 //   k_withdraw_*     (og_withdraw_prove_batch_d only) the sub-batch's witnesses
 //   k_spmv x3        a = A z, b = B z, c = C z over the QAP rows              (CSR, one lane per row)
 //   h_poly_device    3 iNTT + 3 coset NTT + pointwise + coset iNTT            (ntt.hip)
+//                    A key in the evaluation form (og_pk::h_form, "the second rule") stops at the coset: iNTT + coset NTT of A z and
+//                    of B z and their product -- its H tables hold the DFT of the H query, its L tables carry C z
 //   msm_digit_sort   signed 16-bit digits of z, counting-sorted once per DENSITY MAP: the A query, the B query
 //                    (its G1 and G2 copies share the sort) and the L query each keep only the wires whose
 //                    base is not the point at infinity (bellman's "query density")
@@ -30,6 +32,8 @@
 #include "glv.h"
 #include "ec.hip.h"
 #include "key_blob.h"
+#include "keygen.h"          // csr_transpose
+#include "point_spmv.hip.h"  // the DFT over points and the sparse product over points: the H query's evaluation form (h_form_derive)
 #include <string.h>
 #include <algorithm>
 #include <iterator>
@@ -64,6 +68,10 @@ struct og_pk {
   size_t rows_q[2] = {0, 0};     // rows with an entry in A | B
   int c_wire[3] = {0, 0, 0};     // window bits of the wire-form tables of A, B, L (og_pk_windows), built or not
   bool merge_lh = false;          // the L and H queries share one bucket set per proof (same window bits): C = sum z L + sum h H is ONE MSM
+  // Evaluation form of the quotient (pk_load_impl, h_form_pays): the H tables hold E'_p = zinv / d sum_k w^(-p k) g^(-k) H_k, d
+  // points in coset order, and the H query's scalars are the coset values (A z)(B z) -- no transform of C z, no inverse transform;
+  // the L tables hold L_i + G'_i, G'_i = -zinv sum_j C_ji F_j the fold of C z, over the L wires and every other wire of C
+  bool h_form = false;
   bool c_is_ab = false;           // header flag 1 (an imported snarkjs key, zkey.hip): no C matrix, C z := (A z) o (B z) on the domain
   uint8_t* consts1 = nullptr;  // alpha1 | beta1 | delta1, affine Montgomery (3 x 64 B)
   uint8_t* consts2 = nullptr;  // beta2 | delta2, affine Montgomery (2 x 128 B)
@@ -350,6 +358,177 @@ static int rows_check(og_ctx* ctx, const og_pk* pk, const PkView& v, const RowsV
   return OG_OK;
 }
 
+// The second rule: the quotient in the evaluation form -- two transforms each of A z and B z, none of C z, no inverse transform
+// (6 tile passes of 11, ntt.hip) -- for a key that has a C matrix (a flag-1 key has none to fold) and a domain of 2^14 or more.
+// Below that bound a call is latency-bound and the quotient is not what it waits for; and the recorded issue orders
+// (tests/golden/issue_order, domains up to 2^12) are recordings of that regime: such keys issue what they always issued.
+static bool h_form_pays(bool has_c, int log_d) { return has_c && log_d >= 14; }
+
+// What a key in the evaluation form derives from its blob, once per load.  With H_k the H query,
+// H_(d-1) := infinity, g the coset generator, zinv = 1 / (g^d - 1):
+//   e[p]   = E'_p = zinv / d sum_k w^(-p k) g^(-k) H_k: sum_k h_k H_k = sum_p ((a b - c)(g w^p)) E'_p for every h of degree <= d - 2
+//   F'_j   = -zinv / d sum_k w^(-j k) H_k,   G'_i = sum_j C_ji F'_j: sum_p c(g w^p) E'_p = -sum_i z_i G'_i (deg c < d: exact)
+//   lg[i]  = L_i + G'_i for EVERY wire i (L_i = infinity for wire 0 and the public wires; all zeros: the wire has neither)
+// The two sums each carry the x^(d-1) coefficient that has no H point; together it is h_(d-1) = 0 for a satisfied witness.
+struct HFormTables {
+  std::vector<uint8_t> e;   // d x 64 B, canonical affine, in coset order (what the last DIT pass writes)
+  std::vector<uint8_t> lg;  // m x 64 B, canonical affine
+};
+static int h_form_derive(og_ctx* ctx, const og_pk* pk, const PkView& v, const std::string& who, HFormTables* out) {
+  const size_t m = pk->m, d = pk->d, nl = v.nl, nh = v.nh, npub1 = pk->n_pub + 1, n_rows = pk->n_rows, nnz = pk->nnz[2];
+  const int log_d = (int)pk->log_d;
+  const FfRoots& f = ff_roots();
+  OG_REQUIRE(f.ok, who + ": internal: the roots of unity are not what the field layer expects");
+  OG_REQUIRE((uint64_t)d + nl < (1ull << 32) && (uint64_t)nnz + nl < (1ull << 32), who + ": key too large for the evaluation form");
+  const Fr seven = fe_to_mont(fe_from_u32<FrParams>(7));
+  Fr nn = Fr::one();  // d as a field element
+  for (int i = 0; i < log_d; i++) nn = fe_dbl(nn);
+  const Fr scale = fe_mul(fe_inv(fe_sub(zfr_pow2k(seven, log_d), Fr::one())), fe_inv(nn));  // zinv / d
+  std::vector<uint8_t> tw, pre, post_e(32), post_f(32);
+  pow_table(fe_inv(zfr_pow2k(f.w28_own, 28 - log_d)), Fr::one(), d / 2, tw);
+  pow_table(fe_inv(seven), Fr::one(), d, pre);
+  zfr_store(post_e.data(), fe_from_mont(scale));
+  zfr_store(post_f.data(), fe_from_mont(fe_neg(scale)));
+  ZDev dev;
+  uint8_t *raw_d, *hm_d, *base_d, *e_d, *lg_d;
+  OG_TRY(dev.get(std::max(d, nl) * 64, &raw_d));
+  OG_TRY(dev.get(d * 64, &hm_d));
+  OG_TRY(dev.get((d + nl) * 64, &base_d));  // F' | the L query, affine Montgomery: what the sparse product reads
+  OG_TRY(dev.get(d * 64, &e_d));
+  OG_TRY(dev.get(m * 64, &lg_d));
+  OG_HIP(hipMemsetAsync(raw_d, 0, d * 64, ctx->stream));  // H_(d-1) := infinity
+  OG_HIP(hipMemcpyAsync(raw_d, v.query[4], nh * 64, hipMemcpyHostToDevice, ctx->stream));
+  OG_TRY(import_points_g1(ctx, raw_d, hm_d, d));
+  OG_TRY(ecntt_run<Fq>(ctx, dev, hm_d, log_d, tw, &pre, &post_e, true, d, e_d, false));
+  OG_TRY(ecntt_run<Fq>(ctx, dev, hm_d, log_d, tw, nullptr, &post_f, true, d, base_d, true));
+  OG_HIP(hipStreamSynchronize(ctx->stream));  // (raw_d is read; the scalar vectors' copies are done)
+  if (nl) {
+    OG_HIP(hipMemcpyAsync(raw_d, v.query[3], nl * 64, hipMemcpyHostToDevice, ctx->stream));
+    OG_TRY(import_points_g1(ctx, raw_d, base_d + d * 64, nl));
+  }
+  // C transposed: wire i's entries over F', and the wire's own L point with coefficient 1
+  std::vector<uint32_t> cptr(n_rows + 1), ccol(nnz), tptr, trow, kptr(m + 1, 0), kidx;
+  std::vector<uint8_t> cval(v.val[2], v.val[2] + nnz * 32), tval, kval;
+  for (size_t r = 0; r <= n_rows; r++) cptr[r] = rd32(v.ptr[2] + r * 4);
+  for (size_t e = 0; e < nnz; e++) ccol[e] = rd32(v.col[2] + e * 4);
+  csr_transpose(cptr, ccol, cval, n_rows, m, tptr, trow, tval);
+  kidx.reserve(nnz + nl);
+  kval.reserve((nnz + nl) * 32);
+  uint8_t one[32] = {1};
+  for (size_t i = 0; i < m; i++) {
+    kidx.insert(kidx.end(), trow.begin() + tptr[i], trow.begin() + tptr[i + 1]);
+    kval.insert(kval.end(), tval.begin() + (size_t)tptr[i] * 32, tval.begin() + (size_t)tptr[i + 1] * 32);
+    if (i >= npub1 && !all_zero(v.query[3] + (i - npub1) * 64, 64)) {
+      kidx.push_back((uint32_t)(d + (i - npub1)));
+      kval.insert(kval.end(), one, one + 32);
+    }
+    kptr[i + 1] = (uint32_t)kidx.size();
+  }
+  OG_TRY(point_spmv<Fq>(ctx, base_d, kptr, kidx, kval, m, lg_d));  // synchronises
+  out->e.resize(d * 64);
+  out->lg.resize(m * 64);
+  OG_HIP(hipMemcpyAsync(out->e.data(), e_d, d * 64, hipMemcpyDeviceToHost, ctx->stream));
+  OG_HIP(hipMemcpyAsync(out->lg.data(), lg_d, m * 64, hipMemcpyDeviceToHost, ctx->stream));
+  OG_HIP(hipStreamSynchronize(ctx->stream));
+  // hooks builds: OG_H_FORM_CORRUPT=1 | 2 puts a wrong point into E' | into L + G' -- what h_form_check exists to refuse
+  const long long corrupt = OG_HOOK_INT("OG_H_FORM_CORRUPT", 0);
+  if (corrupt == 1 && d >= 2) memcpy(&out->e[64], &out->e[0], 64);
+  for (size_t i = 0; i < m && corrupt == 2; i++) {  // (E'_0 in the place of the first folded point: on the curve, and wrong)
+    if (all_zero(&out->lg[i * 64], 64)) continue;
+    memcpy(&out->lg[i * 64], &out->e[0], 64);
+    break;
+  }
+  return OG_OK;
+}
+
+// The derived tables against the blob's own queries, once per load, through the kernels the prover runs: a wrong DFT must fail
+// the load, not every later proof.  u: a pseudo-random coefficient vector with u_(d-1) = 0; rho: a pseudo-random wire vector.
+// The evaluation-form quotient (h_poly_device) runs on two hand-made proofs -- (a, b) = (the values of u on the domain, the
+// constant g^d - 1) and (C rho, the constant 1): their coset products are u's coset values / zinv, and C rho's -- and
+//   1  sum_p q1[p] E'_p = sum_k u_k H_k                                                          (the new H tables | the blob's H query)
+//   2  sum_i rho_i (L_i + G'_i) + sum_p (q1 + q2)[p] E'_p = sum_i rho_i L_i + sum_k u_k H_k     (the C fold, on (rho, u))
+static int h_form_check(og_ctx* ctx, const og_pk* pk, const PkView& v, uint8_t* stage, const std::string& who) {
+  const size_t m = pk->m, d = pk->d, nl = v.nl, nh = v.nh, npub1 = pk->n_pub + 1;
+  const int log_d = (int)pk->log_d;
+  std::vector<uint8_t> sc((m + d) * 32);  // rho | u
+  uint64_t x = rd64(v.query[4]) ^ rd64(v.query[4] + 32) ^ ((uint64_t)m << 32) ^ d;
+  for (size_t i = 0; i < (m + d) * 4; i++) {  // splitmix64; the top word keeps 60 bits: < 2^252 < r, canonical
+    x += 0x9e3779b97f4a7c15ull;
+    uint64_t z = x;
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+    z ^= z >> 31;
+    if ((i & 3) == 3) z &= (1ull << 60) - 1;
+    memcpy(&sc[i * 8], &z, 8);
+  }
+  memset(&sc[(m + d - 1) * 32], 0, 32);  // u_(d-1) = 0
+  std::vector<uint8_t> bh(2 * d * 32);    // b of the two proofs: the constants g^d - 1 and 1, Montgomery form
+  const Fr zc = fe_sub(zfr_pow2k(fe_to_mont(fe_from_u32<FrParams>(7)), log_d), Fr::one());
+  for (size_t i = 0; i < d; i++) {
+    fe_store(&bh[i * 32], zc);
+    fe_store(&bh[(d + i) * 32], Fr::one());
+  }
+  ZDev dev;
+  uint8_t *sc_d, *ue_d, *a_d, *b_d, *h_d, *res_d;
+  OG_TRY(dev.get((m + d) * 32, &sc_d));
+  OG_TRY(dev.get(d * 32, &ue_d));
+  OG_TRY(dev.get(2 * d * 32, &a_d));
+  OG_TRY(dev.get(2 * d * 32, &b_d));
+  OG_TRY(dev.get(2 * d * 32, &h_d));
+  OG_TRY(dev.get(5 * 128, &res_d));  // new H (two proofs) | new L | the blob's H | the blob's L: XYZZ, all zeros = infinity
+  const uint8_t *rho_d = sc_d, *u_d = sc_d + m * 32;
+  OG_HIP(hipMemcpyAsync(sc_d, sc.data(), sc.size(), hipMemcpyHostToDevice, ctx->stream));
+  OG_HIP(hipMemcpyAsync(b_d, bh.data(), bh.size(), hipMemcpyHostToDevice, ctx->stream));
+  OG_HIP(hipMemsetAsync(res_d, 0, 5 * 128, ctx->stream));
+  OG_TRY(ntt_canonical(ctx, u_d, ue_d, log_d, 1, 0, 0));
+  hipLaunchKernelGGL(k_fr_to_mont, dim3(grid_for(d, 256)), dim3(256), 0, ctx->stream, ue_d, a_d, d);
+  OG_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_spmv, dim3(grid_for(d, 256), 1), dim3(256), 0, ctx->stream, pk->ptr[2], pk->col[2], pk->val[2], (size_t)pk->n_rows, d, rho_d,
+                     (size_t)0, a_d + d * 32, (size_t)0, 1, 1, SPMV_LONG, (uint8_t*)nullptr, (size_t)0);
+  OG_HIP(hipGetLastError());
+  if (pk->n_long[2]) {
+    hipLaunchKernelGGL(k_spmv_long, dim3(pk->n_long[2], 1), dim3(256), 0, ctx->stream, pk->long_rows[2], pk->ptr[2], pk->col[2], pk->val[2], rho_d,
+                       (size_t)0, a_d + d * 32, (size_t)0, 1, 1, (uint8_t*)nullptr, (size_t)0);
+    OG_HIP(hipGetLastError());
+  }
+  OG_TRY(h_poly_device(ctx, a_d, b_d, nullptr, nullptr, h_d, log_d, 2, 1));
+  DigitSort ds;
+  OG_TRY(msm_digit_sort(ctx, 0, h_d, d * 32, d, nullptr, 2, pk->h->c, 1, &ds));
+  OG_TRY(msm_run(ctx, pk->h, ds, res_d));
+  if (pk->n_dense[2]) {
+    OG_TRY(msm_digit_sort(ctx, 0, rho_d, m * 32, pk->n_dense[2], pk->map[2], 1, pk->l->c, 1, &ds));
+    OG_TRY(msm_run(ctx, pk->l, ds, res_d + 256));
+  }
+  // the blob's H and L queries as plain bases, in the blob's order
+  const int cw = (int)msm_pick_c(std::max(nh, nl));
+  og_bases *hb = nullptr, *lb = nullptr;
+  struct Drop { og_bases*& b; ~Drop() { bases_destroy(b); } } drop_h{hb}, drop_l{lb};
+  OG_HIP(hipMemcpyAsync(stage, v.query[4], nh * 64, hipMemcpyHostToDevice, ctx->stream));
+  OG_TRY(bases_create(ctx, 0, stage, nh, cw, 0, &hb));
+  OG_TRY(msm_digit_sort(ctx, 0, u_d, d * 32, nh, nullptr, 1, cw, 0, &ds));
+  OG_TRY(msm_run(ctx, hb, ds, res_d + 384));
+  if (nl) {
+    OG_HIP(hipStreamSynchronize(ctx->stream));  // (stage is reused)
+    OG_HIP(hipMemcpyAsync(stage, v.query[3], nl * 64, hipMemcpyHostToDevice, ctx->stream));
+    OG_TRY(bases_create(ctx, 0, stage, nl, cw, 0, &lb));
+    OG_TRY(msm_digit_sort(ctx, 0, rho_d + npub1 * 32, m * 32, nl, nullptr, 1, cw, 0, &ds));
+    OG_TRY(msm_run(ctx, lb, ds, res_d + 512));
+  }
+  uint8_t res[5 * 128];
+  OG_HIP(hipMemcpyAsync(res, res_d, sizeof res, hipMemcpyDeviceToHost, ctx->stream));
+  OG_HIP(hipStreamSynchronize(ctx->stream));  // (also: hb, lb are idle before they are dropped)
+  const G1XYZZ h1 = G1XYZZ::load(res), h2 = G1XYZZ::load(res + 128), ln = G1XYZZ::load(res + 256), ho = G1XYZZ::load(res + 384),
+               lo = G1XYZZ::load(res + 512);
+  auto same = [](const G1XYZZ& p, const G1XYZZ& q) {
+    const G1Affine a = xyzz_to_affine(p), b = xyzz_to_affine(q);
+    return fe_canon(a.x) == fe_canon(b.x) && fe_canon(a.y) == fe_canon(b.y);
+  };
+  OG_REQUIRE(same(h1, ho), who + ": evaluation form: the derived H tables do not reproduce the key's H query");
+  OG_REQUIRE(same(xyzz_add(xyzz_add(ln, h1), h2), xyzz_add(lo, ho)),
+             who + ": evaluation form: the C fold in the derived L tables does not reproduce the key's L and H queries");
+  return OG_OK;
+}
+
 static int pk_load_impl(og_ctx* ctx, const uint8_t* blob, size_t len, const uint8_t* rows, size_t rows_len, og_pk* pk) {
   const std::string who = rows ? "og_pk_load_rows" : "og_pk_load";
   PkView v;
@@ -389,7 +568,7 @@ static int pk_load_impl(og_ctx* ctx, const uint8_t* blob, size_t len, const uint
   }
   // constants -> affine Montgomery
   uint8_t* stage = nullptr;
-  const size_t stage_bytes = std::max<size_t>(std::max<size_t>(std::max<size_t>(512, m * 128), nh * 64), rows ? pk->n_rows * 128 : 0);
+  const size_t stage_bytes = std::max<size_t>(std::max<size_t>(std::max<size_t>(512, m * 128), pk->d * 64), rows ? pk->n_rows * 128 : 0);
   OG_HIP(hipMalloc((void**)&stage, stage_bytes));
   struct Guard { uint8_t* p; ~Guard() { if (p) (void)hipFree(p); } } guard{stage};
   OG_HIP(hipMalloc((void**)&pk->consts1, 256));
@@ -410,6 +589,24 @@ static int pk_load_impl(og_ctx* ctx, const uint8_t* blob, size_t len, const uint
   // polynomial is zero at tau: the wire never occurs in that matrix) contributes nothing; drop it from the
   // table and from the digit sort.  B1 / B2 are the same polynomial in two groups, so they share one map.
   int ch = (int)msm_pick_query_c(nh);
+  // Coefficients or coset values (h_form_pays), per key: decided here, once.  Hooks builds: OG_H_FORM=0|1 forces either form on
+  // every key that has a C matrix.  Then the H tables and the L query come from h_form_derive, not from the blob as it stands.
+  HFormTables hf;
+  {
+    const long long force = OG_HOOK_INT("OG_H_FORM", -1);
+    pk->h_form = !pk->c_is_ab && pk->log_d >= 1 && force != 0 && (force == 1 || h_form_pays(true, (int)pk->log_d));
+  }
+  if (pk->h_form) {
+    // The self-check below sorts and accumulates in the context's scratch (msm_digit_sort / msm_run / the NTT plan: the arena of
+    // ctx->lane, on ctx->stream), as og_pk_load_rows' check does: refused while a submitted call may still be using it, and run
+    // on lane 0 whatever lane and stream the last call left behind.  (The stream was drained above; keys outside the rule touch
+    // no scratch and load as they always did.)
+    OG_REQUIRE(ctx->jobs[0] == nullptr && ctx->jobs[1] == nullptr,
+               who + ": a submitted prove call has not been waited for (og_job_wait) -- this key takes the evaluation form, and its load-time check uses the call's scratch");
+    ctx->lane = 0;
+    ctx->stream = ctx->lanes[0];
+    OG_TRY(h_form_derive(ctx, pk, v, who, &hf));
+  }
   std::vector<uint32_t> wire[3];
   for (size_t i = 0; i < m; i++) {
     if (!all_zero(v.query[0] + i * 64, 64)) wire[0].push_back((uint32_t)i);
@@ -423,6 +620,11 @@ static int pk_load_impl(og_ctx* ctx, const uint8_t* blob, size_t len, const uint
   // the 7 public ones -> one sort instead of three (the three read and decompose the same witness).  The padding as built
   // (131 k | 117 k | 262 k wires) shares nothing; the natural statement shares A with L.
   for (int k = 0; k < 3; k++) pk->n_real[k] = wire[k].size();
+  if (pk->h_form) {  // the L query carries C z: its own wires and every other wire of C -- wire 0 and the public wires among them
+    wire[2].clear();
+    for (size_t i = 0; i < m; i++)
+      if (!all_zero(&hf.lg[i * 64], 64)) wire[2].push_back((uint32_t)i);
+  }
   // Wires or rows (row_form_pays), per query: A decides alone, B once for its two groups.  Hooks builds: OG_ROW_FORM=0|1 forces
   // either form on every query the extension could serve (A/B runs).  L and H never change.
   std::vector<uint32_t> rlist;
@@ -467,7 +669,7 @@ static int pk_load_impl(og_ctx* ctx, const uint8_t* blob, size_t len, const uint
     OG_HIP(hipMemcpyAsync(pk->map[k], wire[k].data(), wire[k].size() * 4, hipMemcpyHostToDevice, ctx->stream));
   }
   OG_HIP(hipStreamSynchronize(ctx->stream));
-  std::vector<uint8_t> host(std::max<size_t>(std::max<size_t>(std::max<size_t>(1, m * 128), nh * 64), rlist.size() * 128));
+  std::vector<uint8_t> host(std::max<size_t>(std::max<size_t>(std::max<size_t>(1, m * 128), pk->d * 64), rlist.size() * 128));
   if (!rlist.empty()) {
     // ONE table per group over the Lagrange points of the rows in rlist: A and B1 share the G1 one.  The points are checked
     // first -- every coordinate below q, every point on its curve -- and against the key's own queries below (rows_check).
@@ -491,34 +693,41 @@ static int pk_load_impl(og_ctx* ctx, const uint8_t* blob, size_t len, const uint
     if (pk->row[q.mapk]) continue;  // runs over the rows: no wire-form table
     const size_t pb = q.is_g2 ? 128 : 64;
     const std::vector<uint32_t>& w = wire[q.mapk];
-    const size_t shift = q.src == 3 ? pk->n_pub + 1 : 0;  // l_query is indexed from wire n_pub + 1
-    const size_t q_len = q.src == 3 ? nl : m;
+    const bool folded = q.src == 3 && pk->h_form;  // L_i + G'_i, indexed by wire
+    const uint8_t* src = folded ? hf.lg.data() : v.query[q.src];
+    const size_t shift = q.src == 3 && !folded ? pk->n_pub + 1 : 0;  // l_query is indexed from wire n_pub + 1
+    const size_t q_len = q.src == 3 && !folded ? nl : m;
     for (size_t k = 0; k < w.size(); k++) {
-      if (w[k] >= shift && w[k] - shift < q_len) memcpy(host.data() + k * pb, v.query[q.src] + (w[k] - shift) * pb, pb);
+      if (w[k] >= shift && w[k] - shift < q_len) memcpy(host.data() + k * pb, src + (w[k] - shift) * pb, pb);
       else memset(host.data() + k * pb, 0, pb);  // a wire of the shared list this query has no base for: infinity
     }
     OG_HIP(hipMemcpyAsync(stage, host.data(), w.size() * pb, hipMemcpyHostToDevice, ctx->stream));
     OG_TRY(bases_create(ctx, q.is_g2, stage, w.size(), (int)msm_pick_query_c(w.size()), 1, q.dst));  // synchronises the stream
   }
   // the quotient leaves h_poly_device in bit-reversed order (ntt.hip): store the H query in that order.  Position
-  // d - 1 is its own reversal, so the d - 1 bases stay the first d - 1 positions.
-  for (size_t k = 0; k < nh; k++) {
+  // d - 1 is its own reversal, so the d - 1 bases stay the first d - 1 positions.  The evaluation form: E', d points, as derived
+  // -- the coset values leave the last DIT pass in natural order.  The window bits are the coefficient form's either way.
+  const size_t h_pts = pk->h_form ? pk->d : nh;
+  if (pk->h_form) memcpy(host.data(), hf.e.data(), h_pts * 64);
+  for (size_t k = 0; k < nh && !pk->h_form; k++) {
     size_t r = 0;
     for (uint64_t bit = 0; bit < pk->log_d; bit++) r |= ((k >> bit) & 1) << (pk->log_d - 1 - bit);
     memcpy(host.data() + k * 64, v.query[4] + r * 64, 64);
   }
-  OG_HIP(hipMemcpyAsync(stage, host.data(), nh * 64, hipMemcpyHostToDevice, ctx->stream));
+  OG_HIP(hipMemcpyAsync(stage, host.data(), h_pts * 64, hipMemcpyHostToDevice, ctx->stream));
   // C = sum z_i L_i + sum h_j H_j is ONE multi-scalar multiplication: when the H query can take the L query's window size, the
   // two share a bucket set per proof (msm_run_phase) -- one bucket reduction, one heavy-bucket tail and one window combine per
   // proof instead of two, and at 17 bits the H query's 131 071 points cost 15 additions each instead of 16.  (17 bits needs
-  // n x 15 < 2^23 entries for the two-level radix sort, msm.hip.)  Hooks builds: OG_MERGE_LH=0 keeps the queries apart (A/B).
+  // n x 15 < 2^23 entries for the two-level radix sort, msm.hip: n = the h_pts scalars that are sorted; the size rule nh >= 512
+  // stays the key's own query, so that a key's window bits do not depend on the form.)  Hooks builds: OG_MERGE_LH=0 keeps the queries apart (A/B).
   const int cl = pk->l->c;
-  const bool h_takes_cl = cl == ch || (cl == 17 && (double)nh * 15 < (double)(1u << 23) && nh >= 512) || (cl == 16 && nh >= 512);
+  const bool h_takes_cl = cl == ch || (cl == 17 && (double)h_pts * 15 < (double)(1u << 23) && nh >= 512) || (cl == 16 && nh >= 512);
   if (OG_HOOK_INT("OG_MERGE_LH", 1) && h_takes_cl && (cl == 16 || cl == 17 || cl == ch)) {
     ch = cl;
     pk->merge_lh = true;
   }
-  OG_TRY(bases_create(ctx, 0, stage, nh, ch, 1, &pk->h));
+  OG_TRY(bases_create(ctx, 0, stage, h_pts, ch, 1, &pk->h));
+  if (pk->h_form) OG_TRY(h_form_check(ctx, pk, v, stage, who));
   return OG_OK;
 }
 
@@ -534,13 +743,14 @@ void pk_windows(const og_pk* pk, uint64_t out[4]) {
 }
 
 // What each of the five queries A | B1 | B2 | L | H actually runs, four words each: form (0 over the wires, 1 over the QAP rows;
-// H: 0, over the quotient), points (the entries its digit sort visits and its table holds), window bits, table (queries with the
+// H: 0, over the quotient's coefficients; L and H: 2, the evaluation form -- H over the coset values of (A z)(B z), L with C z
+// folded in), points (the entries its digit sort visits and its table holds), window bits, table (queries with the
 // same number share ONE set of window tables: A and B1 in row form)
 void pk_query_form(const og_pk* pk, uint64_t out[20]) {
   const og_bases* q[5] = {pk->a, pk->b1, pk->b2, pk->l, pk->h};
   const int mapk[5] = {0, 1, 1, 2, -1};
   for (int k = 0; k < 5; k++) {
-    out[4 * k + 0] = mapk[k] >= 0 && pk->row[mapk[k]] ? 1 : 0;
+    out[4 * k + 0] = mapk[k] >= 0 && pk->row[mapk[k]] ? 1 : k >= 3 && pk->h_form ? 2 : 0;
     out[4 * k + 1] = q[k]->n;
     out[4 * k + 2] = (uint64_t)q[k]->c;
     int first = k;
@@ -935,7 +1145,7 @@ struct SubBatch {
 };
 
 // the digit sort of witness query q (0 A | 1 B | 2 L) over its compacted wire list into sort slot `slot`, and of h into sort
-// slot 2; a sharded front sorts only this rank's windows k = rank (mod world)
+// slot 2 (d - 1 coefficients, or -- evaluation form -- d coset values); a sharded front sorts only this rank's windows k = rank (mod world)
 static int sub_sort(const ProveCall& c, const SubBatch& s, int slot, int q, DigitSort* out) {
   const og_pk* pk = c.pk;
   // the scalars: the witness through the query's wire map, or -- row form -- (A z) / (B z) through the row map.  The canonical
@@ -947,7 +1157,7 @@ static int sub_sort(const ProveCall& c, const SubBatch& s, int slot, int q, Digi
                                 1, c.sh ? c.sh->rank : 0, c.sh ? c.sh->world : 1, out);
 }
 static int sub_sort_h(const ProveCall& c, const SubBatch& s, DigitSort* out) {
-  return msm_digit_sort_windows(c.ctx, 2, s.h, c.pk->d * 32, c.pk->d - 1, nullptr, s.sb, c.pk->h->c, 1, c.sh ? c.sh->rank : 0,
+  return msm_digit_sort_windows(c.ctx, 2, s.h, c.pk->d * 32, c.pk->h_form ? c.pk->d : c.pk->d - 1, nullptr, s.sb, c.pk->h->c, 1, c.sh ? c.sh->rank : 0,
                                 c.sh ? c.sh->world : 1, out);
 }
 
@@ -1070,7 +1280,7 @@ static int sub_rows(const ProveCall& c, const SubBatch& s) {
 
 static int sub_quotient(const ProveCall& c, const SubBatch& s) {
   ProfScope ps(c.ctx, PROF_HPOLY, (double)c.pk->d * s.sb);
-  OG_TRY(h_poly_device(c.ctx, s.ev[0], s.ev[1], s.ev[2], s.tmp, s.h, (int)c.pk->log_d, s.sb));
+  OG_TRY(h_poly_device(c.ctx, s.ev[0], s.ev[1], s.ev[2], s.tmp, s.h, (int)c.pk->log_d, s.sb, c.pk->h_form ? 1 : 0));
   OG_STEP(c.ctx, "g16.hpoly");
   return OG_OK;
 }

@@ -11,6 +11,8 @@
 // in ONE kernel on the contiguous low-stage tile (DIF stages 9..0, x g^i / n, DIT stages 0..9).  The pointwise
 // (a b - c) / Z rides in the store of c's last pass, the final x g^-i / n and the Montgomery exit in the store of the
 // last inverse pass, and h leaves in bit-reversed order (the H-query bases are stored in that order, groth16.hip).
+// For a key whose H tables hold the evaluation basis (groth16.hip, h_form_pays) the pipeline stops at the coset: a and b only,
+// their product in the store of b's last pass, 6 tile passes.
 // Per proof at d = 2^17: 11 tile passes (read + write 4 MB each) instead of 23, and inside a pass the tile lives in
 // LDS as 9 x 29-bit limbs, so the 32-byte <-> limb conversions happen once per pass, not once per butterfly.
 #include "ctx.h"
@@ -157,7 +159,8 @@ __global__ void __launch_bounds__(256) k_ntt_stages(uint8_t* __restrict__ data, 
 // ---- fused stage blocks for the quotient pipeline --------------------------------------------------------------------
 // One workgroup owns the tile of stage block [s0, s0 + ns) (same index split as k_ntt_stages) and runs, on data kept in
 // LDS as 9 x 29-bit limbs:   [to_mont] -> [DIF stages s0+ns-1 .. s0 with tw_dif] -> [x mid[p]] -> [DIT stages s0 .. s0+ns-1
-// with tw_dit] -> [pointwise: (pw_a[p] pw_b[p] - x) zinv] -> [from_mont] -> out.  p = global position of the element.
+// with tw_dit] -> [pointwise: (pw_a[p] pw_b[p] - x) zinv, or -- pw_mul -- pw_a[p] x] -> [from_mont] -> out.  p = global position
+// of the element.
 struct NttBlock {
   const uint8_t* in;
   uint8_t* out;
@@ -170,6 +173,7 @@ struct NttBlock {
   const uint8_t* pw_b;
   const uint8_t* consts;
   int to_mont, from_mont;
+  int pw_mul;  // the pointwise step is the plain product pw_a[p] x (pw_b unused): no subtraction, no zinv -- h over coset values
 };
 
 constexpr int NTT_LIMBS = 9;
@@ -252,12 +256,14 @@ __global__ void __launch_bounds__(256) k_ntt_block(NttBlock a) {
   }
   const uint8_t* pa = a.pw_a ? a.pw_a + (size_t)g * a.stride : nullptr;
   const uint8_t* pb = a.pw_b ? a.pw_b + (size_t)g * a.stride : nullptr;
+  const bool pw_mul = a.pw_mul != 0;
   for (int e = threadIdx.x; e < tile; e += 256) {
     const int m = e >> lo_t_log, t = e & (lo_t - 1);
     const size_t p = gbase + ((size_t)m << s0) + t;
     Fr v = lds_get(&lds[e * NTT_LIMBS]);
     if (a.mid && !a.tw_dit) v = fe_mul(v, fe_load<FrParams>(a.mid + p * 32));  // no second sweep: scale on the way out
-    if (pa) v = fe_mul(fe_sub(fe_mul(fe_load<FrParams>(pa + p * 32), fe_load<FrParams>(pb + p * 32)), v), fe_load<FrParams>(a.consts + 5 * 32));
+    if (pa && pw_mul) v = fe_mul(fe_load<FrParams>(pa + p * 32), v);
+    else if (pa) v = fe_mul(fe_sub(fe_mul(fe_load<FrParams>(pa + p * 32), fe_load<FrParams>(pb + p * 32)), v), fe_load<FrParams>(a.consts + 5 * 32));
     if (a.from_mont) v = fe_from_mont(v);
     fe_store(dst + p * 32, v);
   }
@@ -477,12 +483,15 @@ __global__ void __launch_bounds__(256) k_ntt_block4(NttBlock a) {
   const uint8_t* pa = a.pw_a ? a.pw_a + (size_t)g * a.stride : nullptr;
   const uint8_t* pb = a.pw_b ? a.pw_b + (size_t)g * a.stride : nullptr;
   const bool lazy = a.tw_dit != nullptr;  // the tile holds DIT outputs: normalized limbs, values < 4N + 3N ns (+ 2N) <= 36N
+  const bool pw_mul = a.pw_mul != 0;
   for (int e = threadIdx.x; e < tile; e += 256) {
     const int m = e >> lo_t_log, t = e & (lo_t - 1);
     const size_t p = gbase + ((size_t)m << s0) + t;
     Fr v = lds_get(&lds[e * NTT_LIMBS]);
     if (a.mid && !a.tw_dit) v = fe_mul(v, fe_load<FrParams>(a.mid + p * 32));  // no second sweep: scale on the way out
-    if (pa) {  // (pa pb - v) / Z: the difference through 40N - v (v < 36N), one product reduces it
+    if (pa && pw_mul) {  // pa v: both operands under 4N first (36N x 4N would leave the product's < 2N), one product
+      v = fe_mul(fe_load<FrParams>(pa + p * 32), lazy ? nt_reduce_64n(v) : v);
+    } else if (pa) {  // (pa pb - v) / Z: the difference through 40N - v (v < 36N), one product reduces it
       const Fr ab = fe_mul(fe_load<FrParams>(pa + p * 32), fe_load<FrParams>(pb + p * 32));
       v = fe_mul(lazy ? nt_sub<40>(ab, v) : nt_sub<4>(ab, v), fe_load<FrParams>(a.consts + 5 * 32));
     } else if (lazy) {
@@ -597,7 +606,10 @@ int ntt_canonical(og_ctx* ctx, const uint8_t* in_d, uint8_t* out_d, int log_n, i
 // h_out = canonical coefficients of (A*B - C)/Z in BIT-REVERSED order (position p holds coefficient rev(p)),
 // batch x d x 32 B.  3 iNTT + 3 coset NTT + pointwise + 1 coset iNTT (arkworks convention), as fused
 // DIF / DIT stage blocks (see the head of this file).  tmp is unused (kept for the callers' scratch layout).
-int h_poly_device(og_ctx* ctx, uint8_t* a, uint8_t* b, uint8_t* c, uint8_t* tmp, uint8_t* h_out, int log_d, int batch) {
+// coset_form (a key whose H tables hold the evaluation basis, groth16.hip h_form_pays): h_out = the canonical coset values
+// (a b)(g w^p) at position p, natural order -- iNTT + coset NTT of a and of b, the product in the store of b's last pass.  c is
+// not read: C z went into the key's L tables.
+int h_poly_device(og_ctx* ctx, uint8_t* a, uint8_t* b, uint8_t* c, uint8_t* tmp, uint8_t* h_out, int log_d, int batch, int coset_form) {
   (void)tmp;
   NttPlan p;
   OG_TRY(ntt_plan(ctx, log_d, &p));
@@ -625,10 +637,27 @@ int h_poly_device(og_ctx* ctx, uint8_t* a, uint8_t* b, uint8_t* c, uint8_t* tmp,
     NttBlock x;
     x.in = data; x.out = data; x.stride = stride; x.log_n = log_d; x.s0 = bs[k]; x.ns = bn[k];
     x.tw_dif = nullptr; x.mid = nullptr; x.tw_dit = nullptr; x.pw_a = nullptr; x.pw_b = nullptr; x.consts = p.consts;
-    x.to_mont = 0; x.from_mont = 0;
+    x.to_mont = 0; x.from_mont = 0; x.pw_mul = 0;
     return x;
   };
   uint8_t* arr[3] = {a, b, c};
+  if (coset_form) {
+    for (int k = 0; k < 2; k++) {
+      for (int j = nb - 1; j >= 1; j--) {
+        NttBlock x = block(arr[k], j);
+        x.tw_dif = p.tw_inv;
+        OG_TRY(launch(x));
+      }
+      for (int j = 0; j < nb; j++) {
+        NttBlock x = block(arr[k], j);
+        if (j == 0) { x.tw_dif = p.tw_inv; x.mid = p.cs_fwd_ninv_br; }
+        x.tw_dit = p.tw_fwd;
+        if (k == 1 && j == nb - 1) { x.pw_a = a; x.pw_mul = 1; x.from_mont = 1; x.out = h_out; }  // h <- a b on the way out, canonical
+        OG_TRY(launch(x));
+      }
+    }
+    return OG_OK;
+  }
   for (int k = 0; k < 3; k++) {
     // evaluations -> coefficients (DIF, high blocks first) -> x g^i / n -> coset evaluations (DIT, low block first)
     for (int j = nb - 1; j >= 1; j--) {
@@ -677,7 +706,14 @@ int h_poly_canonical(og_ctx* ctx, const uint8_t* a, const uint8_t* b, const uint
     hipLaunchKernelGGL(k_to_mont_copy, dim3(grid_for(tot, 256)), dim3(256), 0, ctx->stream, src[k], buf[k], tot);
     OG_HIP(hipGetLastError());
   }
-  OG_TRY(h_poly_device(ctx, buf[0], buf[1], buf[2], buf[3], buf[3], log_d, batch));  // bit-reversed coefficients
+  // hooks builds: OG_H_POLY_COSET=1 answers with the evaluation form's half of the pipeline instead -- the canonical coset values
+  // (a b)(g w^p), natural order, c not read -- so that its stage-block shapes can be checked without a key in that form
+  if (OG_HOOK_INT("OG_H_POLY_COSET", 0)) {
+    OG_TRY(h_poly_device(ctx, buf[0], buf[1], buf[2], buf[3], buf[3], log_d, batch, 1));
+    OG_HIP(hipMemcpyAsync(h_out, buf[3], tot * 32, hipMemcpyDeviceToDevice, ctx->stream));
+    return OG_OK;
+  }
+  OG_TRY(h_poly_device(ctx, buf[0], buf[1], buf[2], buf[3], buf[3], log_d, batch, 0));  // bit-reversed coefficients
   hipLaunchKernelGGL(k_bitrev_copy, dim3(grid_for(d, 256), batch), dim3(256), 0, ctx->stream, buf[3], h_out, d * 32, log_d);
   OG_HIP(hipGetLastError());
   return OG_OK;

@@ -12,7 +12,7 @@ int ntt_domain_consts(og_ctx* ctx, int log_n, uint8_t** consts_d);
 int ntt_canonical(og_ctx* ctx, const uint8_t* in_d, uint8_t* out_d, int log_n, int batch, int inverse, int coset);
 // H-polynomial on device buffers: a, b, c Montgomery evaluations (destroyed), tmp scratch,
 // h_out canonical coefficients; all batch x d x 32 B
-int h_poly_device(og_ctx* ctx, uint8_t* a, uint8_t* b, uint8_t* c, uint8_t* tmp, uint8_t* h_out, int log_d, int batch);
+int h_poly_device(og_ctx* ctx, uint8_t* a, uint8_t* b, uint8_t* c, uint8_t* tmp, uint8_t* h_out, int log_d, int batch, int coset_form);
 // C ABI og_h_poly_d: canonical evaluations in (not modified), canonical coefficients out
 int h_poly_canonical(og_ctx* ctx, const uint8_t* a, const uint8_t* b, const uint8_t* c, int log_d, int batch, uint8_t* h_out);
 

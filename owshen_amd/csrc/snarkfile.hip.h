@@ -1,8 +1,9 @@
 // What the snarkjs-file layers share (zkey.hip: .zkey / .wtns / .r1cs, ptau.hip: .ptau): the iden3 binfile container, the
 // decode / encode kernel for points stored as little-endian Montgomery numbers with R = 2^256, the DFT over group elements
 // (both groups: the kernels are written once over the group law of ec.hip.h and stay free of out-of-line device calls,
-// DESIGN.md 4.2), the host's Fr helpers and this library's / ffjavascript's roots of unity.  Included by exactly those two
-// translation units; everything here is a template or static.
+// DESIGN.md 4.2), the host's Fr helpers and this library's / ffjavascript's roots of unity.  Included by those two
+// translation units and, through point_spmv.hip.h, by groth16.hip (the evaluation form of the H query is a DFT over the key's
+// points); everything here is a template or static.
 #pragma once
 #include "ctx.h"
 #include "field.hip.h"

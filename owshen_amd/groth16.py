@@ -16,7 +16,7 @@ import struct
 
 import numpy as np
 
-from . import api
+from . import _abi, api
 from .api import FR, FR_MODULUS as R
 
 G1_GEN = (1, 2)
@@ -235,12 +235,14 @@ class ProvingKey:
         return dict(zip(("a", "b", "l", "h"), (int(x) for x in d)))
 
     def query_forms(self):
-        """what each of the five queries actually runs (og_pk_query_form): {"a" | "b1" | "b2" | "l" | "h": {"form": "wire" | "row",
-        "points", "bits", "table"}}; queries with the same "table" share one set of window tables"""
+        """what each of the five queries actually runs (og_pk_query_form): {"a" | "b1" | "b2" | "l" | "h": {"form": "wire" | "row", "eval": bool,
+        "points", "bits", "table"}}; "eval": L and H in the evaluation form of the quotient -- the C ABI's form word 2,
+        OG_QUERY_FORM_EVAL.  A compatibility shim: "form" keeps the two values callers already compare against (such a query's
+        scalars are still indexed by wires / positions, so it stays "wire") and the third value of the word is this side key; queries with the same "table" share one set of window tables"""
         d = (C.c_uint64 * 20)()
         self.ctx._check(self.ctx._lib.og_pk_query_form(self._h, d))
         names = ("a", "b1", "b2", "l", "h")
-        return {q: {"form": "row" if d[4 * k] else "wire", "points": int(d[4 * k + 1]), "bits": int(d[4 * k + 2]), "table": names[int(d[4 * k + 3])]}
+        return {q: {"form": "row" if d[4 * k] == 1 else "wire", "eval": _abi.QUERY_FORMS[int(d[4 * k])] == "eval", "points": int(d[4 * k + 1]), "bits": int(d[4 * k + 2]), "table": names[int(d[4 * k + 3])]}
                 for k, q in enumerate(names)}
 
     @staticmethod
