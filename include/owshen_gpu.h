@@ -763,7 +763,9 @@ int og_pk_verify(og_ctx* ctx, const og_r1cs* r1cs, const uint8_t* ptau, size_t l
  * out[i] = k_i * base.  base: host, canonical affine; scalars_d / out_d: device, canonical. */
 int og_scalar_mul_d(og_ctx* ctx, int group, const uint8_t* base, const uint8_t* scalars_d, size_t n,
                     uint8_t* out_d);
-/* Lagrange basis of the size-2^log_d NTT domain evaluated at tau: out[k] = L_k(tau), d x 32 B */
+/* Lagrange basis of the size-2^log_d NTT domain evaluated at tau: out[k] = L_k(tau), d x 32 B canonical, in the natural order of
+ * the domain (L_k belongs to w^k).  A tau inside the domain, tau = w^j, gives the unit vector: out[j] = 1, every other element 0.
+ * tau: host, canonical; a tau >= r is refused with OG_ERR_INVALID, it is never reduced mod r. */
 int og_lagrange_evals_d(og_ctx* ctx, int log_d, const uint8_t tau[32], uint8_t* out_d);
 /* out[row] = sum_k val[k] * x[col[k]] over Fr, CSR with canonical values */
 int og_spmv_fr_d(og_ctx* ctx, const uint32_t* row_ptr_d, const uint32_t* col_d, const uint8_t* val_d,

@@ -70,6 +70,17 @@ static int record_prove_batch_d(const Statement& st, og_ctx* ctx, const og_pk* p
   });
 }
 
+// the little-endian integer of a host-side Fr argument is below r
+static bool fr_bytes_canonical(const uint8_t v[32]) {
+  static const uint64_t r[4] = {0x43e1f593f0000001ULL, 0x2833e84879b97091ULL, 0xb85045b68181585dULL, 0x30644e72e131a029ULL};
+  for (int w = 3; w >= 0; w--) {
+    uint64_t x = 0;
+    for (int i = 7; i >= 0; i--) x = x << 8 | v[8 * w + i];
+    if (x != r[w]) return x < r[w];
+  }
+  return false;
+}
+
 extern "C" {
 
 const char* og_last_error(void) { return g_err.c_str(); }
@@ -575,6 +586,8 @@ int og_lagrange_evals_d(og_ctx* ctx, int log_d, const uint8_t tau[32], uint8_t* 
     CTX_OK(ctx);
     OG_REQUIRE(log_d >= 0 && log_d <= 28, "og_lagrange_evals_d: log_d must be 0..28");
     OG_REQUIRE(tau != nullptr, "og_lagrange_evals_d: null tau");
+    // (the Montgomery entry would reduce a value >= r silently: the basis of a DIFFERENT byte string than the caller holds)
+    OG_REQUIRE(fr_bytes_canonical(tau), "og_lagrange_evals_d: tau must be canonical (< r)");
     LOCKED(ctx);
     return lagrange_evals(ctx, log_d, tau, out_d);
   });

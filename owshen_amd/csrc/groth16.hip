@@ -198,7 +198,8 @@ __global__ void __launch_bounds__(256) k_check_canonical(const uint8_t* __restri
   if (!fe_lt_modulus(fe_load<FrParams>(x + (size_t)g * stride + i * 32))) atomicMin(&bad[g], (uint32_t)i);
 }
 
-// Lagrange basis of the size-2^log_d domain at tau: out[k] = Z(tau)/d * w^k / (tau - w^k), canonical
+// Lagrange basis of the size-2^log_d domain at tau: out[k] = Z(tau)/d * w^k / (tau - w^k), canonical.  At tau = w^j the formula
+// is 0/0 for k = j (and fe_inv(0) = 0): that element is 1, the others are 0 through Z(tau) = 0 -- the unit vector e_j
 __global__ void __launch_bounds__(256) k_lagrange(const uint8_t* __restrict__ consts, const uint8_t* __restrict__ tau_c, int log_d,
                                                  uint8_t* __restrict__ out) {
   size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -215,7 +216,7 @@ __global__ void __launch_bounds__(256) k_lagrange(const uint8_t* __restrict__ co
   }
   Fr num = fe_mul(fe_mul(zt, fe_load<FrParams>(consts + 4 * 32)), wk);
   Fr den = fe_sub(tau, wk);
-  fe_store(out + k * 32, fe_from_mont(fe_mul(num, fe_inv(den))));
+  fe_store(out + k * 32, fe_from_mont(den.is_zero() ? Fr::one() : fe_mul(num, fe_inv(den))));
 }
 
 int spmv_canonical(og_ctx* ctx, const uint32_t* ptr_d, const uint32_t* col_d, const uint8_t* val_d, size_t n_rows,
