@@ -184,6 +184,31 @@ int og_eddsa_verify_compressed_batch_d(og_ctx* ctx, const uint8_t* records_d, si
 int og_note_seal_batch_d(og_ctx* ctx, const uint8_t* requests_d, size_t n, uint8_t* memos_out_d, uint8_t* notes_out_d, uint32_t* ok_out);
 int og_note_scan_batch_d(og_ctx* ctx, const uint8_t sk[32], const uint8_t* memos_d, const uint8_t* leaves_d, size_t n, uint8_t* opened_out_d, uint32_t* hit_out);
 
+/* ---- owned notes: a note sealed to a ONE-TIME key, which only the payee can spend ----------------------------------------------------
+ * The notes above have a hole.  Their spending secrets nullifier' = H(k, 2) and secret' = H(k, 3) derive from S = e * pk = sk * E, and
+ * the SENDER chose e: the sender knows S, k and both secrets, every statement spends a note on knowledge of (nullifier, secret) alone,
+ * so whoever pays such a note can spend it again before the payee does, and can watch for its nullifier hash.  The owned form is the
+ * usual fix for stealth addresses: the note is bound to a one-time public key P = pk + t * BASE.  The sender can compute P; only
+ * the payee knows its discrete logarithm x = sk + t mod l, and the claim statement (og_claim_prove_batch_d, below) spends the note
+ * on knowledge of x.  Notation as above, l = ORDER / 8 the prime order of BASE:
+ *   KDF     from S, on indices disjoint from 1..5: k = H(S.x, S.y); tag = H(k, 6); t = H(k, 7); pad_a = H(k, 8); pad_t = H(k, 9).
+ *           Because the indices are disjoint, og_note_scan_batch_d answers 0 for an owned memo and og_note_scan_owned_batch_d
+ *           answers 0 for an ordinary one.
+ *   seal    request as above.  E = e * BASE, S = e * pk, P = pk + t * BASE, c = H(P.x, P.y), leaf = H(c, H(amount, token)) -- the
+ *           pool's leaf shape with c in the commitment's place.  memo: E.x | E.y | tag | amount + pad_a | token + pad_t; note: c | leaf.
+ *           Refused: what og_note_seal_batch_d refuses, and small(P).
+ *   scan    S = sk * E, then the KDF.  hit 0 and hit 2 as above; hit 1 opens the memo as x | amount | token | c (4 x 32 B) with
+ *           x = (sk + t) mod l, written canonically, and c = H(P.x, P.y) for P = x * BASE -- with the leaf's index and siblings, the
+ *           private half of a claim record.  When leaves are given, each is compared with H(c, H(amount, token)); a difference is
+ *           hit 2.  Only a lane whose tag matches computes t, x, P, c and the leaf.  The host passes sk mod l beside the recoded
+ *           digits, as a kernel argument: neither sk nor anything derived from it stays in the context.
+ * Two facts: a sender who reuses e for the same pk makes two notes with one x, of which only one can be claimed (one nullifier
+ * hash) -- the loss is the sender's; a pk with a torsion component can never be claimed (P = pk + t * BASE is then outside the
+ * subgroup x * BASE generates) -- the fault lies with the key's owner.  The specification is tests/owned_note_spec.py.
+ * Arguments, sizes and refusals of the calls: those of og_note_seal_batch_d and og_note_scan_batch_d. */
+int og_note_seal_owned_batch_d(og_ctx* ctx, const uint8_t* requests_d, size_t n, uint8_t* memos_out_d, uint8_t* notes_out_d, uint32_t* ok_out);
+int og_note_scan_owned_batch_d(og_ctx* ctx, const uint8_t sk[32], const uint8_t* memos_d, const uint8_t* leaves_d, size_t n, uint8_t* opened_out_d, uint32_t* hit_out);
+
 /* ---- N4: radix-2 Fr NTT (domain generator 7^((r-1)/n), coset generator 7) ------
  * batch transforms of size n = 2^log_n, natural order in and out, canonical bytes.
  *   inverse = 0, coset = 0 : out[i] = sum_j in[j] w^(ij)
@@ -567,6 +592,48 @@ int og_transfer_witness_d(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_
 int og_transfer_prove_batch_d(og_ctx* ctx, const og_pk* pk, int depth, const uint8_t* inputs_d, size_t n, const uint8_t* rs,
                               uint8_t* proofs_out, uint8_t* public_out);
 
+/* ---- claim statement: turn an owned note into an ordinary note of the same value that only the claimant can open ---------------------
+ * "I know the discrete logarithm x of the one-time key P of an owned note under `root`.  It is spent.  Its whole value goes into the
+ * new leaf `out_leaf`."  Nothing leaves the pool; after it withdraw, split, join and transfer work unchanged on the out note.  The
+ * sender of the owned note knows pk, e, S, t and P but not x = sk + t: with any x' of their own, x' * BASE is another point, c another
+ * value and the root the statement publishes is not the tree's.  (No reference counterpart: the snapshot has no circuit.)
+ * public (n_pub = 4, verifier order): root, nullifier_hash, chain_id, out_leaf
+ * private: x, amount, token, out_commitment, a depth-`depth` MiMC7 Merkle path.  With H = MultiMiMC7 2-to-1, l the order of BASE:
+ *   x = sum 2^i b_i over 251 boolean wires (one recomposition row);
+ *   x < l, against the constant m = l - 1, most significant bit first: t starts as 1; at a 1-bit of m a new wire t <- t b_i (one row);
+ *     at a 0-bit of m the row b_i t = 0 (114 wires, 251 rows).  NOT optional: l has 251 bits and 2^251 - l ~ 0.32 l, so without it
+ *     about a third of all keys have a second representation x + l with another nullifier_hash -- a double spend;
+ *   P = x * BASE bit by bit: T_i = 2^i * BASE = (u_i, v_i) are constants, (x1, y1) is the running sum from (0, 1); per bit the rows
+ *     b (b - 1) = 0, w1 = b x1, w2 = b y1, w3 = w1 y1, x3 (1 + d u_i v_i w3) = x1 + (v_i - 1) w1 + u_i w2,
+ *     y3 (1 - d u_i v_i w3) = y1 + (v_i - 1) w2 - a u_i w1 -- the complete twisted Edwards law with the addend (b u_i, 1 + b (v_i - 1)),
+ *     linear in the bit; no denominator can vanish (1 255 wires, 1 506 rows);
+ *   c = H(P.x, P.y);  asset = H(amount, token);  leaf = H(c, asset) is under root at `index`;
+ *   nullifier_hash = H(x, 1): an ordinary spend publishes H(nullifier, 0), so both kinds share the ledger's spent set and never collide;
+ *   out_leaf = H(out_commitment, asset): the SAME asset wire, so value and token carry over without a range check;  chain_id is
+ *   bound by its square.
+ * out_commitment is an unconstrained private input, a c' = H(nullifier', secret') the claimant forms off-circuit.  The ledger's part:
+ * og_verify the proof, check that root is known and nullifier_hash unspent (and mark it), append out_leaf (og_mimc7_append_d).
+ * Wire and row order: tests/claim_spec.py (the spec), og_claim_r1cs / owshen_amd/circuit.py claim_r1cs (the R1CS):
+ *   n_wires = 1627 + 3 depth + (5 + depth) 730, n_constraints = 3 + 1506 + 251 + 730 (5 + depth) + 2 depth (28 733 / 28 834 at depth 32:
+ *   domain 2^15; the 3: chain_id^2, the recomposition of x, and one * one = one on the constant wire).  depth 1..64; n <= 65 535 per
+ *   og_claim_witness_d call.  shape[0..2] = n_wires, n_constraints, n_pub.
+ * inputs_d: n records of (6 + depth) x 32 B canonical little-endian:
+ *   x | amount | token | chain_id | out_commitment | index (u64, low bytes) | siblings[depth]
+ * witness_out_d: n x n_wires x 32 B.  og_claim_prove_batch_d: records -> proofs (rs: n x 64 B host, proofs_out: n x 256 B host,
+ * public_out (host, may be NULL): n x 4 x 32 B in verifier order).  Same bytes as og_claim_witness_d + og_prove_batch_d.  The key must
+ * have this shape's wire count and n_pub.
+ * OG_ERR_INVALID, before anything is proved: a malformed record; og_last_error names the record and its lowest offending field
+ * ("input record 3: field 0 (x)"; 0 x, 1 amount, 2 token, 3 chain_id, 4 out_commitment, 5 index, 6 + l sibling l): any field >= r;
+ * field 0 if x >= l; field 1 if amount >= 2^128; an index that does not fit the tree.
+ * The witness generator has ONE walk, one lane per request whatever n: the 251 affine partial sums are walked projectively, parked
+ * in their own wire slots and brought to affine by one inversion per request (Montgomery's trick).  Out of scope: a wave-wide walk,
+ * host chains, a submit / job form, a multi-GPU and a window-sharded form, and Rust and Solidity bindings (ffi/ and contracts/ are
+ * frozen). */
+int og_claim_shape(int depth, uint64_t shape[3]);
+int og_claim_witness_d(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, uint8_t* witness_out_d);
+int og_claim_prove_batch_d(og_ctx* ctx, const og_pk* pk, int depth, const uint8_t* inputs_d, size_t n, const uint8_t* rs,
+                           uint8_t* proofs_out, uint8_t* public_out);
+
 /* The same call in two halves, for a host that keeps requests flowing (a sequencer proving batch after batch): submit
  * enqueues ALL the work of the batch on the ctx's streams and returns; og_job_wait blocks until it is done, fills
  * proofs_out / public_out (which, like rs, must stay valid until then) and frees the job.  At most two calls may be in
@@ -643,6 +710,8 @@ int og_split_r1cs(og_ctx* ctx, int depth, og_r1cs** out);
 int og_join_r1cs(og_ctx* ctx, int depth, og_r1cs** out);
 /* the statement of og_transfer_witness_d at this depth (wire and row order: tests/transfer_spec.py) */
 int og_transfer_r1cs(og_ctx* ctx, int depth, og_r1cs** out);
+/* the statement of og_claim_witness_d at this depth (wire and row order: tests/claim_spec.py) */
+int og_claim_r1cs(og_ctx* ctx, int depth, og_r1cs** out);
 int og_r1cs_from_csr(uint64_t n_wires, uint64_t n_pub, uint64_t n_constraints, const uint32_t* const ptr[3],
                      const uint32_t* const col[3], const uint8_t* const val[3], og_r1cs** out);
 void og_r1cs_free(og_r1cs* r1cs);

@@ -274,6 +274,34 @@ class Context:
             C.memset(skb, 0, 32)
         return out, hit
 
+    def note_seal_owned(self, requests):
+        """the owned form (a note bound to the one-time key P = pk + t BASE, spent by the claim statement): requests device uint8
+        [n, 5, 32] (e | pk.x | pk.y | amount | token) -> (memos device [n, 5, 32]: E.x | E.y | tag | amount + pad_a | token + pad_t, notes
+        device [n, 2, 32]: c | leaf with c = H(P.x, P.y), np.uint32 [n] (0 = refused, memo and note zeroed))"""
+        self._pre()
+        n = requests.shape[0]
+        memos, notes = self.empty(n, 5, 32), self.empty(n, 2, 32)
+        ok = np.zeros(n, dtype=np.uint32)
+        self._check(self._lib.og_note_seal_owned_batch_d(self._h, self.ptr(requests), n, self.ptr(memos), self.ptr(notes),
+                                                         ok.ctypes.data_as(C.c_void_p)))
+        return memos, notes, ok
+
+    def note_scan_owned(self, sk, memos, leaves=None, opened=True):
+        """the owned form's scan, arguments as note_scan -> (opened device [n, 4, 32]: x | amount | token | c with x = (sk + t) mod l the
+        discrete logarithm of the note's one-time key -- the `x` of a claim record --, zero rows unless the hit is 1, np.uint32 [n]: 0 not
+        this key's | 1 opened | 2 this key's tag on a memo that does not open)"""
+        self._pre()
+        n = memos.shape[0]
+        skb = (C.c_uint8 * 32).from_buffer_copy(sk.to_bytes(32, "little") if isinstance(sk, int) else bytes(sk))
+        out = self.empty(n, 4, 32) if opened else None
+        hit = np.zeros(n, dtype=np.uint32)
+        try:
+            self._check(self._lib.og_note_scan_owned_batch_d(self._h, skb, self.ptr(memos), self.ptr(leaves), n, self.ptr(out),
+                                                             hit.ctypes.data_as(C.c_void_p)))
+        finally:
+            C.memset(skb, 0, 32)
+        return out, hit
+
     # -- N4 NTT --
     def ntt(self, data, inverse=False, coset=False):
         """data: device uint8 [n,32] or [batch,n,32] canonical -> same shape."""

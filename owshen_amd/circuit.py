@@ -20,8 +20,8 @@ points, Fr NTT 2^17"): n_wires = 2^18, domain 2^17.
 Only index arrays and constants are produced here (numpy); there is no host-side witness
 generator -- the witness comes from og_withdraw_witness_d.
 
-The deposit, the split, the join and the transfer statement (oracle/py/deposit.py, tests/split_spec.py, tests/join_spec.py,
-tests/transfer_spec.py are their specs) follow further down, built with the same gadget builder.
+The deposit, the split, the join, the transfer and the claim statement (oracle/py/deposit.py, tests/split_spec.py, tests/join_spec.py,
+tests/transfer_spec.py, tests/claim_spec.py are their specs) follow further down, built with the same gadget builder.
 """
 import ctypes as C
 
@@ -36,6 +36,18 @@ PAD_SEGMENT = 64
 N_DENSE_ROWS = 2
 W_ROOT, W_NH, W_RECIPIENT, W_AMOUNT, W_TOKEN, W_CHAIN, W_NULLIFIER, W_SECRET = 1, 2, 3, 4, 5, 6, 7, 8
 N_REC = 8  # fields of an input record before the siblings
+# BabyJubJub: a x^2 + y^2 = 1 + d x^2 y^2 over Fr, its base point and l, the prime order of BASE (8 l points on the curve)
+ED_A, ED_D = 168700, 168696
+ED_BASE = (5299619240641551281634865583518297030282874472190772894086521144482721001553,
+           16950150798460657717958625567821834550301663161624707787222815936182638968203)
+ED_L = 2736030358979909402780800718157159386076813972158567259200215660948447373041
+
+
+def _ed_double(p):
+    """2 p on BabyJubJub, affine (the complete law with both operands p)"""
+    x, y = p
+    t = ED_D * x * x % R * y * y % R
+    return 2 * x * y * pow(1 + t, -1, R) % R, (y * y - ED_A * x * x) * pow(1 - t, -1, R) % R
 
 
 def shape(depth, n_pad3=0, n_pad2=0):
@@ -129,6 +141,42 @@ class _Builder:
         for i in range(n_bits):
             self.enforce([(bits + i, 1)], [(bits + i, 1), (0, R - 1)], [])
         self.enforce([(bits + i, 1 << i) for i in range(n_bits)], [(0, 1)], [(value, 1)])
+
+    def less_equal_const(self, bits, n_bits, m):
+        """sum 2^i b_i <= m for the constant m < 2^n_bits, over the boolean wires bits .. bits + n_bits - 1 (LSB first), most
+        significant bit first: t starts as the constant 1; a 1-bit of m allocates t' = t b_i (one row), a 0-bit adds the row
+        b_i t = 0.  popcount(m) wires, n_bits rows; the caller makes the wires boolean"""
+        assert 0 <= m < (1 << n_bits)
+        t = [(0, 1)]
+        for i in reversed(range(n_bits)):
+            if (m >> i) & 1:
+                nt = self.alloc()
+                self.enforce(t, [(bits + i, 1)], [(nt, 1)])
+                t = [(nt, 1)]
+            else:
+                self.enforce([(bits + i, 1)], t, [])
+
+    def fixed_base_mul(self, bits, n_bits):
+        """P = (sum 2^i b_i) BASE on BabyJubJub over the wires bits .. bits + n_bits - 1 (LSB first), which it makes boolean.  Per bit
+        the wires w1 = b x1, w2 = b y1, w3 = w1 y1, x3, y3 and six rows: the complete twisted Edwards law with the addend
+        (b u_i, 1 + b (v_i - 1)), (u_i, v_i) = 2^i BASE, on the running sum (x1, y1) that starts at the constants (0, 1).  Returns the
+        linear combinations of P.x and P.y"""
+        x1, y1 = [], [(0, 1)]
+        u, v = ED_BASE
+        for i in range(n_bits):
+            b = bits + i
+            duv = ED_D * u % R * v % R
+            w1 = self.alloc(5)
+            w2, w3, x3, y3 = w1 + 1, w1 + 2, w1 + 3, w1 + 4
+            self.enforce([(b, 1)], [(b, 1), (0, R - 1)], [])
+            self.enforce([(b, 1)], x1, [(w1, 1)])
+            self.enforce([(b, 1)], y1, [(w2, 1)])
+            self.enforce([(w1, 1)], y1, [(w3, 1)])
+            self.enforce([(x3, 1)], [(0, 1), (w3, duv)], _lc_merge(x1, [(w1, v - 1)], [(w2, u)]))
+            self.enforce([(y3, 1)], [(0, 1), (w3, R - duv)], _lc_merge(y1, [(w2, v - 1)], [(w1, R - ED_A * u % R)]))
+            x1, y1 = [(x3, 1)], [(y3, 1)]
+            u, v = _ed_double((u, v))
+        return x1, y1
 
     def merkle_walk(self, cur, w_sib, w_bit, depth, root):
         """the path from `cur` up to the wire `root`, the output wire of the last level's hash: per level a boolean index bit, the
@@ -651,6 +699,76 @@ def transfer_leaves(pay_commitment, pay_amount, change_commitment, change, token
     tok = _dev(ctx, token, token)
     leaves = ctx.mimc7_hash2(_dev(ctx, pay_commitment, change_commitment), ctx.mimc7_hash2(_dev(ctx, pay_amount, change), tok))
     return tuple(int.from_bytes(row.tobytes(), "little") for row in ctx.to_host(leaves))
+
+
+# ---- the claim statement (tests/claim_spec.py is the spec; witness.hip k_claim_core fills the wires) -----------------------------------
+# public: root, nullifier_hash, chain_id, out_leaf; private: x, amount, token, out_commitment, the path.  An owned note
+# (og_note_seal_owned_batch_d) is bound to a one-time key P = pk + t BASE; only the payee knows x = sk + t mod l with P = x BASE.
+# x = sum 2^i b_i over 251 boolean wires with x < l; c = H(P.x, P.y); leaf = H(c, asset = H(amount, token)) under root;
+# nullifier_hash = H(x, 1); out_leaf = H(out_commitment, asset) -- an ordinary note of the same value that only the claimant opens.
+C_N_PUB, C_N_REC, C_N_BITS = 4, 6, 251
+C_N_CMP = bin(ED_L - 1).count("1")     # 114: the comparison's wires
+(CW_ROOT, CW_NH, CW_CHAIN, CW_OUT_LEAF, CW_X, CW_AMOUNT, CW_TOKEN, CW_OUT_COMMITMENT) = range(1, 9)
+
+
+def claim_shape(depth):
+    """(n_wires, n_constraints): (28733, 28834) at depth 32"""
+    return 1627 + 3 * depth + (5 + depth) * 730, 3 + 6 * C_N_BITS + C_N_BITS + 730 * (5 + depth) + 2 * depth
+
+
+def claim_r1cs(mimc7_constants, depth=32):
+    """the claim statement as an R1CS (the same gadget builder as the withdraw circuit); no padding gates"""
+    assert depth >= 1 and len(mimc7_constants) == N_ROUNDS
+    n_wires, n_constraints = claim_shape(depth)
+    bld = _Builder([int(c) for c in mimc7_constants])
+    bld.alloc(1 + C_N_PUB + 4)
+    w_sib = bld.alloc(depth)
+    w_bit = bld.alloc(depth)
+    w_csq = bld.alloc()
+    w_xbit = bld.alloc(C_N_BITS)
+    bld.enforce([(CW_CHAIN, 1)], [(CW_CHAIN, 1)], [(w_csq, 1)])
+    bld.enforce([(w_xbit + i, 1 << i) for i in range(C_N_BITS)], [(0, 1)], [(CW_X, 1)])
+    bld.enforce([(0, 1)], [(0, 1)], [(0, 1)])
+    bld.less_equal_const(w_xbit, C_N_BITS, ED_L - 1)
+    px, py = bld.fixed_base_mul(w_xbit, C_N_BITS)
+    c = bld.hash2(px, py)
+    asset = bld.hash2([(CW_AMOUNT, 1)], [(CW_TOKEN, 1)])
+    leaf = bld.hash2([(c, 1)], [(asset, 1)])
+    bld.hash2([(CW_X, 1)], [(0, 1)], out_wire=CW_NH)
+    bld.merkle_walk(leaf, w_sib, w_bit, depth, CW_ROOT)
+    bld.hash2([(CW_OUT_COMMITMENT, 1)], [(asset, 1)], out_wire=CW_OUT_LEAF)
+    return _finish(bld, n_wires, C_N_PUB, n_constraints)
+
+
+def claim_r1cs_native(ctx, depth=32):
+    """the same statement built by the library (og_claim_r1cs: what a Rust host calls)"""
+    h = C.c_void_p()
+    ctx._check(ctx._lib.og_claim_r1cs(ctx._h, depth, C.byref(h)))
+    return _r1cs_from_handle(ctx, h)
+
+
+def pack_claim_inputs(x, amount, index, siblings, token=0, chain_id=0, out_commitment=0):
+    """one claim record: (6 + depth) x 32 B (include/owshen_gpu.h):
+    x | amount | token | chain_id | out_commitment | index | siblings[depth]"""
+    return _pack([x, amount, token, chain_id, out_commitment, index] + list(siblings))
+
+
+def claim_witness(ctx, depth, inputs_d):
+    """inputs_d: device uint8 [n, 6 + depth, 32] -> device uint8 [n, n_wires, 32] (og_claim_witness_d)"""
+    return _records_witness(ctx, "claim", C_N_REC + depth, depth, inputs_d, claim_shape(depth), C_N_PUB)
+
+
+def claim_prove(ctx, pk, depth, inputs_d, rs, return_public=False):
+    """inputs_d: device uint8 [n, 6 + depth, 32]; rs: (r, s) pairs or uint8 [n, 64] -> np.uint8 [n, 256] (og_claim_prove_batch_d);
+    return_public: also (root, nullifier_hash, chain_id, out_leaf) of every proof, np.uint8 [n, 4, 32]"""
+    return _records_prove(ctx, pk, "claim", C_N_REC + depth, C_N_PUB, depth, inputs_d, rs, return_public)
+
+
+def claim_out_leaf(out_commitment, amount, token, ctx):
+    """the ledger's and the claimant's side of a claim: out_leaf = H(out_commitment, H(amount, token)) through og_mimc7_hash2_d (the
+    value of public input 4; what og_mimc7_append_d appends).  Returns an int."""
+    leaf = ctx.mimc7_hash2(_dev(ctx, out_commitment), ctx.mimc7_hash2(_dev(ctx, amount), _dev(ctx, token)))
+    return int.from_bytes(ctx.to_host(leaf).tobytes(), "little")
 
 
 class ProveJob:

@@ -799,6 +799,15 @@ int og_transfer_shape(int depth, uint64_t shape[3]) { return record_shape(ST_TRA
 int og_transfer_witness_d(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, uint8_t* witness_out_d) {
   return record_witness_d(ST_TRANSFER, ctx, {depth}, inputs_d, n, witness_out_d);
 }
+int og_claim_shape(int depth, uint64_t shape[3]) { return record_shape(ST_CLAIM, {depth}, shape); }
+int og_claim_witness_d(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, uint8_t* witness_out_d) {
+  return record_witness_d(ST_CLAIM, ctx, {depth}, inputs_d, n, witness_out_d);
+}
+int og_claim_prove_batch_d(og_ctx* ctx, const og_pk* pk, int depth, const uint8_t* inputs_d, size_t n, const uint8_t* rs, uint8_t* proofs_out,
+                           uint8_t* public_out) {
+  return record_prove_batch_d(ST_CLAIM, ctx, pk, {depth}, inputs_d, n, rs, proofs_out, public_out);
+}
+
 int og_transfer_prove_batch_d(og_ctx* ctx, const og_pk* pk, int depth, const uint8_t* inputs_d, size_t n, const uint8_t* rs,
                               uint8_t* proofs_out, uint8_t* public_out) {
   return record_prove_batch_d(ST_TRANSFER, ctx, pk, {depth}, inputs_d, n, rs, proofs_out, public_out);
@@ -1003,6 +1012,34 @@ int og_note_scan_batch_d(og_ctx* ctx, const uint8_t sk[32], const uint8_t* memos
     uint32_t* hit_d = nullptr;
     OG_TRY(arena_get(ctx, "eddsa.ok", n * 4, (void**)&hit_d));
     OG_TRY(note_scan(ctx, sk, memos_d, leaves_d, n, opened_out_d, hit_d));
+    return eddsa_ok_out(ctx, hit_d, n, hit_out);
+  });
+}
+
+int og_note_seal_owned_batch_d(og_ctx* ctx, const uint8_t* requests_d, size_t n, uint8_t* memos_out_d, uint8_t* notes_out_d, uint32_t* ok_out) {
+  return guarded([&]() -> int {
+    CTX_OK(ctx);
+    OG_REQUIRE(n == 0 || (requests_d && memos_out_d && notes_out_d && ok_out), "og_note_seal_owned_batch_d: null argument");
+    if (n == 0) return OG_OK;
+    LOCKED(ctx);
+    uint32_t* ok_d = nullptr;
+    OG_TRY(arena_get(ctx, "eddsa.ok", n * 4, (void**)&ok_d));
+    OG_TRY(note_seal_owned(ctx, requests_d, n, memos_out_d, notes_out_d, ok_d));
+    return eddsa_ok_out(ctx, ok_d, n, ok_out);
+  });
+}
+
+int og_note_scan_owned_batch_d(og_ctx* ctx, const uint8_t sk[32], const uint8_t* memos_d, const uint8_t* leaves_d, size_t n, uint8_t* opened_out_d,
+                               uint32_t* hit_out) {
+  return guarded([&]() -> int {
+    CTX_OK(ctx);
+    OG_REQUIRE(n == 0 || (sk && memos_d && hit_out), "og_note_scan_owned_batch_d: null argument");
+    if (n == 0) return OG_OK;
+    OG_REQUIRE(note_sk_canonical(sk), "og_note_scan_owned_batch_d: sk is not a canonical field element (sk >= r)");
+    LOCKED(ctx);
+    uint32_t* hit_d = nullptr;
+    OG_TRY(arena_get(ctx, "eddsa.ok", n * 4, (void**)&hit_d));
+    OG_TRY(note_scan_owned(ctx, sk, memos_d, leaves_d, n, opened_out_d, hit_d));
     return eddsa_ok_out(ctx, hit_d, n, hit_out);
   });
 }

@@ -10,6 +10,44 @@ struct EdPoint {
   Fr x, y, z;
 };
 
+// l, the prime order of BASE (251 bits; the curve has 8 l points), as eight words.  Device code reads it at unrolled, constant
+// indices only (the form of FrSqrt in eddsa_keys.hip)
+struct EdOrder {
+  static constexpr int BITS = 251;
+  static constexpr uint32_t L[8] = {0x392126f1u, 0x677297dcu, 0x3920ee0au, 0xab3eedb8u, 0xd0302b0bu, 0x370a08b6u, 0x5c263405u, 0x060c89ceu};
+};
+// word w of l, without dynamic indexing of a constant array
+OG_HD uint32_t ed_order_word(int w) {
+  uint32_t word = 0;
+#pragma unroll
+  for (int k = 0; k < 8; k++) word = k == w ? EdOrder::L[k] : word;
+  return word;
+}
+// bit i of l - 1 (l is odd: only word 0 differs)
+OG_HD bool ed_order_minus_1_bit(int i) { return (((ed_order_word(i >> 5) - (i < 32 ? 1u : 0u)) >> (i & 31)) & 1u) != 0; }
+// a < l for the eight words of a 256-bit integer, most significant word first
+OG_HD bool ed_below_order(const uint32_t a[8]) {
+  bool lt = false, decided = false;
+#pragma unroll
+  for (int i = 7; i >= 0; i--) {
+    if (!decided && a[i] != EdOrder::L[i]) {
+      lt = a[i] < EdOrder::L[i];
+      decided = true;
+    }
+  }
+  return lt;
+}
+// a <- a - l on the eight words (a >= l)
+OG_HD void ed_sub_order(uint32_t a[8]) {
+  uint32_t borrow = 0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    const uint64_t d = (uint64_t)a[i] - EdOrder::L[i] - borrow;
+    a[i] = (uint32_t)d;
+    borrow = (uint32_t)(d >> 63);
+  }
+}
+
 __device__ __forceinline__ Fr ed_const(uint32_t v) { return fe_to_mont(fe_from_u32<FrParams>(v)); }
 
 // unified projective addition on a x^2 + y^2 = 1 + d x^2 y^2 (add-2008-bbjlp: the reference's projective add :118-143 without

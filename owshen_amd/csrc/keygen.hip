@@ -8,8 +8,9 @@
 //
 //   og_withdraw_r1cs   constraint rows of the depth-D MiMC7 Merkle withdraw circuit (+ synthetic padding gates, + the two
 //                      optional density rows), CSR, canonical 32-byte coefficients
-//   og_deposit_r1cs / og_split_r1cs / og_join_r1cs / og_transfer_r1cs   the deposit, the split, the join and the transfer statement,
-//                      with the same builder (oracle/py/deposit.py, tests/split_spec.py, tests/join_spec.py, tests/transfer_spec.py)
+//   og_deposit_r1cs / og_split_r1cs / og_join_r1cs / og_transfer_r1cs / og_claim_r1cs   the deposit, the split, the join, the transfer
+//                      and the claim statement, with the same builder (oracle/py/deposit.py, tests/split_spec.py, tests/join_spec.py,
+//                      tests/transfer_spec.py, tests/claim_spec.py)
 //   og_r1cs_from_csr   any R1CS the caller built
 //   og_setup           Groth16 key generation from (tau, alpha, beta, gamma, delta): Lagrange evaluations, the three
 //                      transposed sparse products, the query scalars and ~3 m + d fixed-base multiplications, all on the
@@ -20,6 +21,8 @@
 #include "field.hip.h"
 #include "keygen.h"
 #include "statements.h"
+#include "host_fr4.h"
+#include "eddsa.hip.h"
 #include <string.h>
 #include <stdlib.h>
 #include <algorithm>
@@ -63,6 +66,41 @@ static HFr hfr_neg_one() { return {{FR_MOD[0] - 1, FR_MOD[1], FR_MOD[2], FR_MOD[
 static HFr hfr_from_bytes(const uint8_t* p) {
   HFr r;
   memcpy(r.v, p, 32);
+  return r;
+}
+
+
+// ---- BabyJubJub on the host, for the constants of the fixed-base gadget: a x^2 + y^2 = 1 + d x^2 y^2, affine points in the host's
+// Montgomery form (host_fr4.h).  Only a doubling is needed: the gadget's constants are 2^i BASE.
+struct HEd {
+  H4 x, y;
+};
+static H4 h4_neg(const H4Field& f, const H4& a) { return (a.v[0] | a.v[1] | a.v[2] | a.v[3]) ? h4_sub_raw(f.n, a) : a; }
+static H4 h4_sub(const H4Field& f, const H4& a, const H4& b) { return h4_add(f, a, h4_neg(f, b)); }
+static H4 h4_small(const H4Field& f, uint64_t v) { return h4_to_mont(f, H4{{v, 0, 0, 0}}); }
+static H4 h4_inv(const H4Field& f, const H4& a) {  // a^(r-2), a != 0
+  H4 e = f.n, acc = f.one;
+  e.v[0] -= 2;  // (r ends in ...0001: no borrow)
+  for (int i = 255; i >= 0; i--) {
+    acc = h4_mul(f, acc, acc);
+    if ((e.v[i >> 6] >> (i & 63)) & 1) acc = h4_mul(f, acc, a);
+  }
+  return acc;
+}
+static HFr hfr_of(const H4Field& f, const H4& mont) {
+  const H4 c = h4_from_mont(f, mont);
+  return {{c.v[0], c.v[1], c.v[2], c.v[3]}};
+}
+constexpr uint64_t ED_A = 168700, ED_D = 168696;
+// BASE (the reference's babyjubjub/mod.rs:177-188; eddsa_keys.hip k_ed_table holds the same words)
+static const H4 ED_BASE_X = {{0x2893f3f6bb957051ULL, 0x2ab8d8010534e0b6ULL, 0x4eacb2e09d6277c1ULL, 0x0bb77a6ad63e739bULL}};
+static const H4 ED_BASE_Y = {{0x4b3c257a872d7d8bULL, 0xfce0051fb9e13377ULL, 0x25572e1cd16bf9edULL, 0x25797203f7a0b249ULL}};
+static HEd hed_double(const H4Field& f, const HEd& p) {  // the complete law with both operands p
+  const H4 xx = h4_mul(f, p.x, p.x), yy = h4_mul(f, p.y, p.y), xy = h4_mul(f, p.x, p.y);
+  const H4 t = h4_mul(f, h4_small(f, ED_D), h4_mul(f, xx, yy));
+  HEd r;
+  r.x = h4_mul(f, h4_add(f, xy, xy), h4_inv(f, h4_add(f, f.one, t)));
+  r.y = h4_mul(f, h4_sub(f, yy, h4_mul(f, h4_small(f, ED_A), xx)), h4_inv(f, h4_sub(f, f.one, t)));
   return r;
 }
 
@@ -140,6 +178,49 @@ struct R1csBuilder {
       sum.push_back({bits + i, p2});
     }
     enforce(sum, one(0), one(value));
+  }
+  // sum 2^i b_i <= m for the constant m < 2^n_bits over the boolean wires bits .. bits + n_bits - 1 (LSB first), most significant bit
+  // first: t starts as the constant 1; a 1-bit of m allocates t' = t b_i (one row), a 0-bit adds the row b_i t = 0.  popcount(m)
+  // wires, n_bits rows; the caller makes the wires boolean
+  void less_equal_const(uint32_t bits, uint32_t n_bits, const uint64_t m[4]) {
+    LC t = one(0);
+    for (int i = (int)n_bits - 1; i >= 0; i--) {
+      if ((m[i >> 6] >> (i & 63)) & 1) {
+        const uint32_t nt = alloc();
+        enforce(t, one(bits + i), one(nt));
+        t = one(nt);
+      } else {
+        enforce(one(bits + i), t, LC{});
+      }
+    }
+  }
+  // P = (sum 2^i b_i) BASE on BabyJubJub over the wires bits .. bits + n_bits - 1 (LSB first), which it makes boolean.  Per bit the
+  // wires w1 = b x1, w2 = b y1, w3 = w1 y1, x3, y3 and six rows: the complete twisted Edwards law with the addend
+  // (b u_i, 1 + b (v_i - 1)), (u_i, v_i) = 2^i BASE, on the running sum (x1, y1) that starts at the constants (0, 1).  px, py: the
+  // linear combinations of P
+  void fixed_base_mul(uint32_t bits, uint32_t n_bits, LC& px, LC& py) {
+    const H4Field& f = h4_field();
+    const HFr m1 = hfr_neg_one();
+    HEd t{h4_to_mont(f, ED_BASE_X), h4_to_mont(f, ED_BASE_Y)};
+    LC x1, y1 = one(0);
+    for (uint32_t i = 0; i < n_bits; i++) {
+      const uint32_t b = bits + i, w1 = alloc(5), w2 = w1 + 1, w3 = w1 + 2, x3 = w1 + 3, y3 = w1 + 4;
+      const H4 duv = h4_mul(f, h4_small(f, ED_D), h4_mul(f, t.x, t.y));
+      const HFr c_duv = hfr_of(f, duv), c_nduv = hfr_of(f, h4_neg(f, duv)), c_u = hfr_of(f, t.x), c_vm1 = hfr_of(f, h4_sub(f, t.y, f.one));
+      const HFr c_nau = hfr_of(f, h4_neg(f, h4_mul(f, h4_small(f, ED_A), t.x)));
+      enforce(one(b), LC{{b, hfr_u64(1)}, {0u, m1}}, LC{});
+      enforce(one(b), x1, one(w1));
+      enforce(one(b), y1, one(w2));
+      enforce(one(w1), y1, one(w3));
+      const LC tx{{w1, c_vm1}, {w2, c_u}}, ty{{w2, c_vm1}, {w1, c_nau}};
+      enforce(one(x3), LC{{0u, hfr_u64(1)}, {w3, c_duv}}, lc_merge({&x1, &tx}));
+      enforce(one(y3), LC{{0u, hfr_u64(1)}, {w3, c_nduv}}, lc_merge({&y1, &ty}));
+      x1 = one(x3);
+      y1 = one(y3);
+      t = hed_double(f, t);
+    }
+    px = x1;
+    py = y1;
   }
   // the path from `cur` up to the wire `root`, which is the output wire of the last level's hash: per level a boolean index bit, the
   // `left` selector wire (allocated here) and one hash
@@ -288,6 +369,37 @@ void transfer_r1cs_rows(R1csBuilder& b, int depth) {
   b.hash2(R1csBuilder::one(TW_PAY_COMMITMENT), R1csBuilder::one(pay_asset), (int)TW_PAY_LEAF);
   const uint32_t change_asset = b.hash2(R1csBuilder::one(TW_CHANGE), R1csBuilder::one(TW_TOKEN));
   b.hash2(R1csBuilder::one(TW_CHANGE_COMMITMENT), R1csBuilder::one(change_asset), (int)TW_CHANGE_LEAF);
+}
+
+// the claim statement (tests/claim_spec.py; witness.hip k_claim_core): an owned note, bound to the one-time key P = x BASE, into an
+// ordinary note of the same value
+void claim_r1cs_rows(R1csBuilder& b, int depth) {
+  constexpr uint32_t CW_ROOT = 1, CW_NH = 2, CW_CHAIN = 3, CW_OUT_LEAF = 4, CW_X = 5, CW_AMOUNT = 6, CW_TOKEN = 7, CW_OUT_COMMITMENT = 8;
+  constexpr uint32_t C_BITS = EdOrder::BITS;
+  b.alloc(1 + 4 + 4);
+  const uint32_t w_sib = b.alloc(depth), w_bit = b.alloc(depth), w_csq = b.alloc();
+  const uint32_t w_xbit = b.alloc(C_BITS);
+  b.enforce(R1csBuilder::one(CW_CHAIN), R1csBuilder::one(CW_CHAIN), R1csBuilder::one(w_csq));
+  LC sum;
+  for (uint32_t i = 0; i < C_BITS; i++) {
+    HFr p2 = {{0, 0, 0, 0}};
+    p2.v[i >> 6] = 1ull << (i & 63);
+    sum.push_back({w_xbit + i, p2});
+  }
+  b.enforce(sum, R1csBuilder::one(0), R1csBuilder::one(CW_X));  // x = sum 2^i b_i
+  b.enforce(R1csBuilder::one(0), R1csBuilder::one(0), R1csBuilder::one(0));
+  uint64_t l_minus_1[4];  // (l is odd)
+  for (int k = 0; k < 4; k++) l_minus_1[k] = (uint64_t)EdOrder::L[2 * k] | (uint64_t)EdOrder::L[2 * k + 1] << 32;
+  l_minus_1[0] -= 1;
+  b.less_equal_const(w_xbit, C_BITS, l_minus_1);  // x < l: without it x + l is a second key for the same note
+  LC px, py;
+  b.fixed_base_mul(w_xbit, C_BITS, px, py);
+  const uint32_t c = b.hash2(px, py);
+  const uint32_t asset = b.hash2(R1csBuilder::one(CW_AMOUNT), R1csBuilder::one(CW_TOKEN));
+  const uint32_t leaf = b.hash2(R1csBuilder::one(c), R1csBuilder::one(asset));
+  b.hash2(R1csBuilder::one(CW_X), R1csBuilder::one(0), (int)CW_NH);  // H(x, 1): an ordinary spend publishes H(nullifier, 0)
+  b.merkle_walk(leaf, w_sib, w_bit, depth, CW_ROOT);
+  b.hash2(R1csBuilder::one(CW_OUT_COMMITMENT), R1csBuilder::one(asset), (int)CW_OUT_LEAF);  // the SAME asset wire
 }
 
 static int records_r1cs_build(const Statement& st, const uint8_t* mimc_consts, int depth, og_r1cs* r) {
@@ -568,6 +680,7 @@ int og_deposit_r1cs(og_ctx* ctx, og_r1cs** out) {
 int og_split_r1cs(og_ctx* ctx, int depth, og_r1cs** out) { return record_r1cs(ST_SPLIT, ctx, depth, out); }
 int og_join_r1cs(og_ctx* ctx, int depth, og_r1cs** out) { return record_r1cs(ST_JOIN, ctx, depth, out); }
 int og_transfer_r1cs(og_ctx* ctx, int depth, og_r1cs** out) { return record_r1cs(ST_TRANSFER, ctx, depth, out); }
+int og_claim_r1cs(og_ctx* ctx, int depth, og_r1cs** out) { return record_r1cs(ST_CLAIM, ctx, depth, out); }
 
 int og_r1cs_from_csr(uint64_t n_wires, uint64_t n_pub, uint64_t n_constraints, const uint32_t* const ptr[3], const uint32_t* const col[3],
                      const uint8_t* const val[3], og_r1cs** out) {

@@ -12,6 +12,10 @@
 //          DESIGN.md, row "f-5 notes", for the resource table that decided it).
 //   KDF    k = H(S.x, S.y); the five outputs H(k, j) share the absorption of k (kdf_absorb_k), so each costs one permutation: four
 //          permutations to the tag, and only a lane whose tag matches computes the rest.
+//   owned  the form a wallet can use (tests/owned_note_spec.py): the ordinary note's secrets derive from S, which the SENDER knows too,
+//          so the payer could spend what they paid.  The owned note is bound to P = pk + t BASE with t = H(k, 7); only the payee knows
+//          x = sk + t mod l, and the claim statement (witness.hip) spends on knowledge of x.  Both kernels share the fronts of the
+//          ordinary pair (note_seal_front, note_scan_front) and draw from the same sponge on indices 6 .. 9.
 //   seal   E = e * BASE from the 64 x 16 window table of eddsa_keys.hip, S = e * pk by a plain ladder over the unified law (one
 //          addition site, no divergence), sixteen permutations.
 #include "ctx.h"
@@ -170,6 +174,8 @@ __device__ __forceinline__ Fr kdf_absorb_k(const uint32_t* __restrict__ consts, 
   return note_absorb(consts, Fr::zero(), note_hash2(consts, sx, sy));
 }
 enum { KDF_TAG = 1, KDF_NULLIFIER = 2, KDF_SECRET = 3, KDF_PAD_AMOUNT = 4, KDF_PAD_TOKEN = 5 };
+// the owned form (tests/owned_note_spec.py) draws from the same sponge on indices of its own: neither scan sees the other form's tag
+enum { KDF_OWNED_TAG = 6, KDF_OWNED_T = 7, KDF_OWNED_PAD_AMOUNT = 8, KDF_OWNED_PAD_TOKEN = 9 };
 
 __device__ __forceinline__ bool fe_same_limbs(const Fr& a, const Fr& b) {
   uint32_t x = 0;
@@ -185,6 +191,25 @@ __device__ __forceinline__ bool below_2_128(const Fr& canonical) {
 }
 
 // ---- scan ------------------------------------------------------------------------------------------------------------------------
+// What both scans do with a memo before they know whose it is: the five fields canonical, E on the curve and not small, S = sk E,
+// k = H(S.x, S.y) absorbed into `a`, and the tag H(k, tag_index) compared with the memo's.  true: the tag is this wallet's.
+template <int FORM>
+__device__ __forceinline__ bool note_scan_front(const uint32_t* __restrict__ consts, const NoteDigits& dg, const uint8_t* m, uint32_t tag_index, Fr& a) {
+  bool good = true;
+#pragma unroll 1
+  for (int k = 0; k < 5; k++) good = good && canonical_fr(m + 32 * k);
+  const Fr ca = ed_const(168700), cd = ed_const(168696);
+  {
+    const Fr ex = fe_to_mont(fe_load<FrParams>(m)), ey = fe_to_mont(fe_load<FrParams>(m + 32));
+    good = good && ed_on_curve(ex, ey, ca, cd) && !ed_small(ex, ey, ca);
+    const EdPoint s = ed_mul_uniform<FORM>(dg, ex, ey, ca, cd);
+    const Fr zi = fe_inv(s.z);  // never zero for a point of the curve; an off-curve E is refused whatever comes out
+    a = kdf_absorb_k(consts, fe_mul(s.x, zi), fe_mul(s.y, zi));
+  }
+  const Fr tag = fe_from_mont(note_absorb(consts, a, ed_const(tag_index)));
+  return good && fe_same_limbs(tag, fe_load<FrParams>(m + 64));
+}
+
 // memo: E.x | E.y | tag | amount + pad_a | token + pad_t.  hit 0: not this wallet's (or malformed); 1: opened -> nullifier' | secret' |
 // amount | token; 2: the tag is this wallet's and the memo does not open (amount >= 2^128, or the leaf beside it is another).
 template <int FORM>
@@ -193,20 +218,8 @@ __global__ void __launch_bounds__(64) k_note_scan(const uint32_t* __restrict__ c
   const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= n) return;
   const uint8_t* m = memos + g * 160;
-  bool good = true;
-#pragma unroll 1
-  for (int k = 0; k < 5; k++) good = good && canonical_fr(m + 32 * k);
-  const Fr ca = ed_const(168700), cd = ed_const(168696);
   Fr a;  // the sponge with k absorbed
-  {
-    const Fr ex = fe_to_mont(fe_load<FrParams>(m)), ey = fe_to_mont(fe_load<FrParams>(m + 32));
-    good = good && ed_on_curve(ex, ey, ca, cd) && !ed_small(ex, ey, ca);
-    const EdPoint s = ed_mul_uniform<FORM>(dg, ex, ey, ca, cd);
-    const Fr zi = fe_inv(s.z);  // never zero for a point of the curve; an off-curve E is refused whatever comes out
-    a = kdf_absorb_k(consts, fe_mul(s.x, zi), fe_mul(s.y, zi));
-  }
-  const Fr tag = fe_from_mont(note_absorb(consts, a, ed_const(KDF_TAG)));
-  uint32_t code = good && fe_same_limbs(tag, fe_load<FrParams>(m + 64)) ? 1u : 0u;
+  uint32_t code = note_scan_front<FORM>(consts, dg, m, KDF_TAG, a) ? 1u : 0u;
   uint8_t* o = opened ? opened + g * 128 : nullptr;
   if (code) {  // diverges; a wallet owns a vanishing share of the pool
     const Fr amount = fe_canon(fe_sub(fe_load<FrParams>(m + 96), fe_from_mont(note_absorb(consts, a, ed_const(KDF_PAD_AMOUNT)))));
@@ -230,20 +243,83 @@ __global__ void __launch_bounds__(64) k_note_scan(const uint32_t* __restrict__ c
   hit[g] = code;
 }
 
-// ---- seal ------------------------------------------------------------------------------------------------------------------------
-// request e | pk.x | pk.y | amount | token -> memo E.x | E.y | tag | amount + pad_a | token + pad_t and note c' | leaf
-__global__ void __launch_bounds__(64) k_note_seal(const uint32_t* __restrict__ consts, const uint8_t* __restrict__ tab, const uint8_t* __restrict__ reqs,
-                                                 size_t n, uint8_t* __restrict__ memos, uint8_t* __restrict__ notes, uint32_t* __restrict__ ok) {
+// ---- the owned form: a note bound to a one-time key P = pk + t BASE ----------------------------------------------------------------------
+// sk mod l beside the recoded digits: a kernel argument like them, so it lives in scalar registers and nowhere else
+struct NoteScalar {
+  uint32_t w[8];
+};
+
+// k BASE, affine, for the integer in w (any value below 2^256): the 64 table additions of ed_mul_base and one inversion
+__device__ __forceinline__ void note_mul_base_affine(const uint8_t* __restrict__ tab, const uint32_t w[8], const Fr& ca, const Fr& cd, Fr& x, Fr& y) {
+  EdPoint p, unused;
+  ed_mul_base<false>(tab, w, w, p, unused, ca, cd);
+  const Fr zi = fe_inv(p.z);
+  x = fe_mul(p.x, zi);
+  y = fe_mul(p.y, zi);
+}
+
+// memo: E.x | E.y | tag | amount + pad_a | token + pad_t, the KDF on the owned indices.  hit 0 and 2 as k_note_scan; 1: opened ->
+// x | amount | token | c with x = (sk + t) mod l and c = H(P.x, P.y), P = x BASE.  Only a lane whose tag matches computes t, x, P, c
+// and the leaf.
+template <int FORM>
+__global__ void __launch_bounds__(64) k_note_scan_owned(const uint32_t* __restrict__ consts, const uint8_t* __restrict__ tab, const NoteDigits dg,
+                                                       const NoteScalar sk_mod_l, const uint8_t* __restrict__ memos, const uint8_t* __restrict__ leaves,
+                                                       size_t n, uint8_t* __restrict__ opened, uint32_t* __restrict__ hit) {
   const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= n) return;
-  const uint8_t* req = reqs + g * 160;
-  uint8_t* memo = memos + g * 160;
-  uint8_t* note = notes + g * 64;
+  const uint8_t* m = memos + g * 160;
+  Fr a;  // the sponge with k absorbed
+  uint32_t code = note_scan_front<FORM>(consts, dg, m, KDF_OWNED_TAG, a) ? 1u : 0u;
+  uint8_t* o = opened ? opened + g * 128 : nullptr;
+  if (code) {  // diverges; a wallet owns a vanishing share of the pool
+    const Fr amount = fe_canon(fe_sub(fe_load<FrParams>(m + 96), fe_from_mont(note_absorb(consts, a, ed_const(KDF_OWNED_PAD_AMOUNT)))));
+    const Fr token = fe_canon(fe_sub(fe_load<FrParams>(m + 128), fe_from_mont(note_absorb(consts, a, ed_const(KDF_OWNED_PAD_TOKEN)))));
+    if (!below_2_128(amount)) code = 2u;
+    if (code == 1u && (leaves || o)) {
+      // x = (sk + t) mod l on the integer words: t < r < 8 l, sk mod l < l
+      uint32_t xw[8];
+      fe_to_words(xw, fe_from_mont(note_absorb(consts, a, ed_const(KDF_OWNED_T))));
+#pragma unroll 1
+      for (int k = 0; k < 8; k++)
+        if (!ed_below_order(xw)) ed_sub_order(xw);
+      uint32_t carry = 0;
+#pragma unroll
+      for (int k = 0; k < 8; k++) {  // (below 2 l < 2^252: no carry out)
+        const uint64_t v = (uint64_t)xw[k] + sk_mod_l.w[k] + carry;
+        xw[k] = (uint32_t)v;
+        carry = (uint32_t)(v >> 32);
+      }
+      if (!ed_below_order(xw)) ed_sub_order(xw);
+      const Fr ca = ed_const(168700), cd = ed_const(168696);
+      Fr px, py;
+      note_mul_base_affine(tab, xw, ca, cd, px, py);
+      const Fr c = note_hash2(consts, px, py);
+      if (leaves) {
+        const Fr leaf = note_hash2(consts, c, note_hash2(consts, fe_to_mont(amount), fe_to_mont(token)));
+        if (!fe_same_limbs(fe_from_mont(leaf), fe_load<FrParams>(leaves + g * 32))) code = 2u;
+      }
+      if (o && code == 1u) {
+        fe_store(o, fe_from_words<FrParams>(xw));
+        fe_store(o + 32, amount);
+        fe_store(o + 64, token);
+        fe_store(o + 96, fe_from_mont(c));
+      }
+    }
+  }
+  if (o && code != 1u) store_zeros(o, 8);
+  hit[g] = code;
+}
+
+// ---- seal ------------------------------------------------------------------------------------------------------------------------
+// What both seals do with a request e | pk.x | pk.y | amount | token before the KDF: the five fields canonical, amount < 2^128, pk on
+// the curve and not small, E = e BASE from the window table (not the identity) and S = e pk by the ladder, both brought to affine
+// by one inversion.  false: the request is refused (the points are then meaningless).
+__device__ __forceinline__ bool note_seal_front(const uint8_t* __restrict__ tab, const uint8_t* req, const Fr& ca, const Fr& cd, Fr& ex, Fr& ey, Fr& sx,
+                                                Fr& sy) {
   bool good = true;
 #pragma unroll 1
   for (int k = 0; k < 5; k++) good = good && canonical_fr(req + 32 * k);
   good = good && below_2_128(fe_load<FrParams>(req + 96));
-  const Fr ca = ed_const(168700), cd = ed_const(168696);
   uint32_t we[8];
   fe_to_words(we, fe_load<FrParams>(req));
   EdPoint ep, sp;
@@ -280,13 +356,31 @@ __global__ void __launch_bounds__(64) k_note_seal(const uint32_t* __restrict__ c
   // both points to affine by one inversion
   const Fr zi = fe_inv(fe_mul(ep.z, sp.z));
   const Fr ezi = fe_mul(zi, sp.z), szi = fe_mul(zi, ep.z);
-  const Fr a = kdf_absorb_k(consts, fe_mul(sp.x, szi), fe_mul(sp.y, szi));
+  ex = fe_mul(ep.x, ezi);
+  ey = fe_mul(ep.y, ezi);
+  sx = fe_mul(sp.x, szi);
+  sy = fe_mul(sp.y, szi);
+  return good;
+}
+
+// request e | pk.x | pk.y | amount | token -> memo E.x | E.y | tag | amount + pad_a | token + pad_t and note c' | leaf
+__global__ void __launch_bounds__(64) k_note_seal(const uint32_t* __restrict__ consts, const uint8_t* __restrict__ tab, const uint8_t* __restrict__ reqs,
+                                                 size_t n, uint8_t* __restrict__ memos, uint8_t* __restrict__ notes, uint32_t* __restrict__ ok) {
+  const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= n) return;
+  const uint8_t* req = reqs + g * 160;
+  uint8_t* memo = memos + g * 160;
+  uint8_t* note = notes + g * 64;
+  const Fr ca = ed_const(168700), cd = ed_const(168696);
+  Fr ex, ey, sx, sy;
+  const bool good = note_seal_front(tab, req, ca, cd, ex, ey, sx, sy);
+  const Fr a = kdf_absorb_k(consts, sx, sy);
   const Fr nul = note_absorb(consts, a, ed_const(KDF_NULLIFIER)), sec = note_absorb(consts, a, ed_const(KDF_SECRET));
   const Fr leaf = note_hash2(consts, note_hash2(consts, nul, sec),
                              note_hash2(consts, fe_to_mont(fe_load<FrParams>(req + 96)), fe_to_mont(fe_load<FrParams>(req + 128))));
   if (good) {
-    fe_store(memo, fe_from_mont(fe_mul(ep.x, ezi)));
-    fe_store(memo + 32, fe_from_mont(fe_mul(ep.y, ezi)));
+    fe_store(memo, fe_from_mont(ex));
+    fe_store(memo + 32, fe_from_mont(ey));
     fe_store(memo + 64, fe_from_mont(note_absorb(consts, a, ed_const(KDF_TAG))));
     fe_store(memo + 96, fe_canon(fe_add(fe_load<FrParams>(req + 96), fe_from_mont(note_absorb(consts, a, ed_const(KDF_PAD_AMOUNT))))));
     fe_store(memo + 128, fe_canon(fe_add(fe_load<FrParams>(req + 128), fe_from_mont(note_absorb(consts, a, ed_const(KDF_PAD_TOKEN))))));
@@ -299,7 +393,89 @@ __global__ void __launch_bounds__(64) k_note_seal(const uint32_t* __restrict__ c
   ok[g] = good ? 1u : 0u;
 }
 
+// request e | pk.x | pk.y | amount | token -> memo E.x | E.y | tag | amount + pad_a | token + pad_t (the KDF on the owned indices) and
+// note c | leaf with P = pk + t BASE, c = H(P.x, P.y), leaf = H(c, H(amount, token)).  Refused: what k_note_seal refuses, and small(P).
+__global__ void __launch_bounds__(64) k_note_seal_owned(const uint32_t* __restrict__ consts, const uint8_t* __restrict__ tab,
+                                                       const uint8_t* __restrict__ reqs, size_t n, uint8_t* __restrict__ memos, uint8_t* __restrict__ notes,
+                                                       uint32_t* __restrict__ ok) {
+  const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= n) return;
+  const uint8_t* req = reqs + g * 160;
+  uint8_t* memo = memos + g * 160;
+  uint8_t* note = notes + g * 64;
+  const Fr ca = ed_const(168700), cd = ed_const(168696);
+  Fr ex, ey, sx, sy;
+  bool good = note_seal_front(tab, req, ca, cd, ex, ey, sx, sy);
+  const Fr a = kdf_absorb_k(consts, sx, sy);
+  Fr px, py;  // P = pk + t BASE, affine
+  {
+    uint32_t tw[8];
+    fe_to_words(tw, fe_from_mont(note_absorb(consts, a, ed_const(KDF_OWNED_T))));
+    EdPoint tb, pk;
+    {
+      EdPoint unused;
+      ed_mul_base<false>(tab, tw, tw, tb, unused, ca, cd);
+    }
+    pk.x = fe_to_mont(fe_load<FrParams>(req + 32));
+    pk.y = fe_to_mont(fe_load<FrParams>(req + 64));
+    pk.z = Fr::one();
+    const EdPoint p = ed_add(tb, pk, ca, cd);
+    const Fr zi = fe_inv(p.z);  // never zero for a pk of the curve; a pk off it is refused whatever comes out
+    px = fe_mul(p.x, zi);
+    py = fe_mul(p.y, zi);
+    good = good && !ed_small(px, py, ca);
+  }
+  const Fr c = note_hash2(consts, px, py);
+  const Fr leaf = note_hash2(consts, c, note_hash2(consts, fe_to_mont(fe_load<FrParams>(req + 96)), fe_to_mont(fe_load<FrParams>(req + 128))));
+  if (good) {
+    fe_store(memo, fe_from_mont(ex));
+    fe_store(memo + 32, fe_from_mont(ey));
+    fe_store(memo + 64, fe_from_mont(note_absorb(consts, a, ed_const(KDF_OWNED_TAG))));
+    fe_store(memo + 96, fe_canon(fe_add(fe_load<FrParams>(req + 96), fe_from_mont(note_absorb(consts, a, ed_const(KDF_OWNED_PAD_AMOUNT))))));
+    fe_store(memo + 128, fe_canon(fe_add(fe_load<FrParams>(req + 128), fe_from_mont(note_absorb(consts, a, ed_const(KDF_OWNED_PAD_TOKEN))))));
+    fe_store(note, fe_from_mont(c));
+    fe_store(note + 32, fe_from_mont(leaf));
+  } else {
+    store_zeros(memo, 10);
+    store_zeros(note, 4);
+  }
+  ok[g] = good ? 1u : 0u;
+}
+
 // ---- launches --------------------------------------------------------------------------------------------------------------------
+int note_seal_owned(og_ctx* ctx, const uint8_t* requests_d, size_t n, uint8_t* memos_d, uint8_t* notes_d, uint32_t* ok_d) {
+  if (n == 0) return OG_OK;
+  const uint8_t* tab = nullptr;
+  OG_TRY(eddsa_base_table(ctx, &tab));
+  hipLaunchKernelGGL(k_note_seal_owned, dim3(grid_for(n, 64)), dim3(64), 0, ctx->stream, (const uint32_t*)ctx->mimc_consts_d, tab, requests_d, n, memos_d,
+                     notes_d, ok_d);
+  OG_HIP(hipGetLastError());
+  return OG_OK;
+}
+
+// sk is reduced mod l here, once, and handed over beside its digits; both copies are wiped before returning, and the launch copies
+// its arguments: neither sk nor anything derived from it stays in the context
+int note_scan_owned(og_ctx* ctx, const uint8_t sk[32], const uint8_t* memos_d, const uint8_t* leaves_d, size_t n, uint8_t* opened_d, uint32_t* hit_d) {
+  if (n == 0) return OG_OK;
+  const uint8_t* tab = nullptr;
+  OG_TRY(eddsa_base_table(ctx, &tab));
+  NoteDigits dg;
+  NoteScalar sl;
+  for (int i = 0; i < 8; i++) sl.w[i] = (uint32_t)sk[4 * i] | (uint32_t)sk[4 * i + 1] << 8 | (uint32_t)sk[4 * i + 2] << 16 | (uint32_t)sk[4 * i + 3] << 24;
+  for (int k = 0; k < 8; k++)  // sk < r < 8 l
+    if (!ed_below_order(sl.w)) ed_sub_order(sl.w);
+  note_recode(sk, NOTE_NAF_W, dg);
+  hipLaunchKernelGGL(k_note_scan_owned<NOTE_NAF_W>, dim3(grid_for(n, 64)), dim3(64), 0, ctx->stream, (const uint32_t*)ctx->mimc_consts_d, tab, dg, sl,
+                     memos_d, leaves_d, n, opened_d, hit_d);
+  note_wipe(dg);
+  {
+    volatile uint32_t* p = sl.w;
+    for (int i = 0; i < 8; i++) p[i] = 0;
+  }
+  OG_HIP(hipGetLastError());
+  return OG_OK;
+}
+
 int note_seal(og_ctx* ctx, const uint8_t* requests_d, size_t n, uint8_t* memos_d, uint8_t* notes_d, uint32_t* ok_d) {
   if (n == 0) return OG_OK;
   const uint8_t* tab = nullptr;

@@ -46,5 +46,8 @@ int note_seal(og_ctx* ctx, const uint8_t* requests_d, size_t n, uint8_t* memos_d
 bool note_sk_canonical(const uint8_t sk[32]);
 // sk: HOST, canonical (the caller has checked it); leaves_d (n x 32) and opened_d (n x 128) may each be null
 int note_scan(og_ctx* ctx, const uint8_t sk[32], const uint8_t* memos_d, const uint8_t* leaves_d, size_t n, uint8_t* opened_d, uint32_t* hit_d);
+// the owned form (a note bound to a one-time key, spent by the claim statement): the same argument lists
+int note_seal_owned(og_ctx* ctx, const uint8_t* requests_d, size_t n, uint8_t* memos_d, uint8_t* notes_d, uint32_t* ok_d);
+int note_scan_owned(og_ctx* ctx, const uint8_t sk[32], const uint8_t* memos_d, const uint8_t* leaves_d, size_t n, uint8_t* opened_d, uint32_t* hit_d);
 
 }  // namespace og

@@ -11,6 +11,8 @@
 //   k_join_core      the join statement: two lanes per request, one per note
 //   k_transfer_core / k_tw9_*   the transfer statement (near the end): one lane per request for batches, a permutation per wave in three
 //                    launches for calls of at most 512 requests
+//   k_claim_core     the claim statement (behind the wave-wide walks): one lane per request, whatever the size of the call -- x BASE walked
+//                    projectively with its coordinates parked in the witness row, one inversion per request
 //   k_sw9_* / k_jw9_*   the wave-wide walk of split and of join (at the end, behind transfer's, whose bodies they share): three launches
 //                    each, for calls of at most 512 requests; k_split_core / k_join_core stay the form for batches
 //
@@ -23,6 +25,8 @@
 #include "mimc7.hip.h"
 #include "host_fr4.h"
 #include "field_w9.hip.h"
+#include "eddsa.hip.h"
+#include "primitives.h"
 #include <string.h>
 #include <algorithm>
 #include <thread>
@@ -1960,6 +1964,221 @@ static void join_launch_w9(og_ctx* ctx, int depth, const RecordShape& s, const u
   OG_W9_LAUNCH(k_jw9_chain, w9_rows(), dim3((unsigned)(n * 4)), dim3(64), 0, ctx->stream, c9, inputs_d, depth, (size_t)s.n_wires, fgw, ngw, wl, xch);
 }
 
+// ---- the claim statement: an owned note into an ordinary note of the same value ---------------------------------------------------------
+// Spec: tests/claim_spec.py.  public: root, nullifier_hash, chain_id, out_leaf (n_pub = 4); private: x, amount, token, out_commitment,
+// the path.  An owned note (notes.hip, og_note_seal_owned_batch_d) is bound to a one-time key P = pk + t BASE of which only the payee
+// knows the discrete logarithm x = sk + t mod l; the sender, who knows everything else about the note, cannot spend it.  x = sum 2^i b_i
+// over 251 boolean wires with x < l (l the order of BASE: without the bound x + l is a second key with another nullifier hash);
+// P = x BASE; c = H(P.x, P.y); asset = H(amount, token); leaf = H(c, asset) lies under root; nullifier_hash = H(x, 1) (an ordinary
+// spend publishes H(nullifier, 0)); out_leaf = H(out_commitment, asset) -- the SAME asset wire, a leaf of the deposit shape.  No
+// reference counterpart (the snapshot has no circuit).
+// Input record per request, (6 + depth) x 32 B canonical LE:
+//   x | amount | token | chain_id | out_commitment | index (u64 in the low bytes) | siblings[depth]
+// Wires:
+//   0 one | 1 root | 2 nullifier_hash | 3 chain_id | 4 out_leaf | 5 x | 6 amount | 7 token | 8 out_commitment
+//   9.. siblings[D] | index bits[D] | chain_id^2 | x bits[251] (LSB first) | the comparison's 114 wires t (one per 1-bit of l - 1, most
+//   significant first: t = "x equals l - 1 on every bit so far") | the multiplication's wires, per bit w1 = b x1, w2 = b y1, w3 = w1 y1,
+//   x3, y3 with (x1, y1) the partial sum before the bit and (x3, y3) after it | the gadgets: c, asset, leaf, nullifier_hash (out =
+//   wire 2), level 0..D-1 (the last one's out = wire 1), out_leaf (out = wire 4)
+// One walk: k_claim_core, one lane per request.  NOT built for this statement: a wave-wide walk, host chains.
+constexpr int C_PUB = 4;
+constexpr int C_REC = 6;  // fields of a claim record before the siblings
+constexpr int C_BITS = EdOrder::BITS, C_CMP = 114;
+// byte offsets of the record's fields
+constexpr int C_X = 0, C_AMOUNT = 32, C_TOKEN = 64, C_CHAIN = 96, C_OUT_COMMITMENT = 128, C_INDEX = 160;
+
+static RecordShape claim_shape(const StatementArgs& a) {
+  RecordShape s{};
+  const int depth = a.depth;
+  const uint64_t hashes = 5 + (uint64_t)depth;
+  s.first_bit_wire = 1 + C_PUB + 4 + 2 * (uint64_t)depth + 1;
+  s.first_gadget_wire = s.first_bit_wire + C_BITS + C_CMP + 5 * C_BITS;
+  s.n_wires = s.first_gadget_wire + depth + hashes * 730 - 3;  // a `left` per level; nullifier_hash, root and out_leaf are public wires
+  s.n_constraints = 3 + C_BITS + 6 * C_BITS + 2 * (uint64_t)depth + hashes * 730;
+  return s;
+}
+
+// bit i of the record's x (the records are checked first: x < l < 2^251), read from the record: no register array is indexed
+__device__ __forceinline__ bool claim_x_bit(const uint8_t* in, int i) {
+  return ((reinterpret_cast<const uint32_t*>(in + C_X)[i >> 5] >> (i & 31)) & 1u) != 0;
+}
+
+// One lane per request, as k_transfer_core: the (5 + depth) MultiMiMC7 gadgets through the one rolled permutation body (gadget_wires);
+// Montgomery values are stored and k_wires_from_mont converts them afterwards, in parallel.
+// The multiplication's wires are the 251 AFFINE partial sums S_1 .. S_251 of x BASE, bit 0 first.  Two inversions per bit would be ~10^5
+// products a request against ~2.7 10^4 for the 37 hashes; instead the sum is walked projectively through the one addition site of the
+// unified law (the addend taken from the 64 x 16 table of BASE under a select on the bit, as the seal's ladder takes its own: entry
+// d = 2^(i mod 4) of window i / 4 is 2^i BASE) and every step PARKS what the way back needs in its own wire slots of the output row:
+//     slot w1 <- Z_1 Z_2 .. Z_(i+1), the running product;  w2 <- Z_(i+1);  x3 <- X_(i+1);  y3 <- Y_(i+1)      (w3 stays free)
+// One inversion of the last running product (Montgomery's trick), then the slots are passed backwards: step i reads the running
+// product of step i - 1, forms 1 / Z_(i+1) and the affine S_(i+1), stores x3 and y3 of its own step and w1, w2, w3 of step i + 1,
+// whose parked values the previous iteration has consumed.  No scratch buffer beyond the witness, no runtime-indexed register array.
+// Z never vanishes: the law is complete on the curve.
+__global__ void __launch_bounds__(64) k_claim_core(const uint32_t* __restrict__ consts, const uint8_t* __restrict__ tab, const uint8_t* __restrict__ inputs,
+                                                  int depth, size_t n_wires, uint32_t first_bit_wire, size_t n, uint8_t* __restrict__ out) {
+  OG_FILLER_PRIO();
+  const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= n) return;
+  const uint8_t* in = inputs + g * (size_t)(C_REC + depth) * 32;
+  uint8_t* z = out + g * n_wires * 32;
+  WireWriterT<false> ww{z, first_bit_wire};
+  const Fr x = fe_to_mont(fe_load<FrParams>(in + C_X));
+  const Fr amount = fe_to_mont(fe_load<FrParams>(in + C_AMOUNT));
+  const Fr token = fe_to_mont(fe_load<FrParams>(in + C_TOKEN));
+  const Fr chain_id = fe_to_mont(fe_load<FrParams>(in + C_CHAIN));
+  const Fr out_commitment = fe_to_mont(fe_load<FrParams>(in + C_OUT_COMMITMENT));
+  const uint64_t index = *reinterpret_cast<const uint64_t*>(in + C_INDEX);
+  ww.put(0, Fr::one());
+  ww.put(3, chain_id);
+  ww.put(5, x);
+  ww.put(6, amount);
+  ww.put(7, token);
+  ww.put(8, out_commitment);
+  for (int l = 0; l < depth; l++) {
+    ww.put(9 + l, fe_to_mont(fe_load<FrParams>(in + (size_t)(C_REC + l) * 32)));
+    ww.put(9 + depth + l, ((index >> l) & 1) ? Fr::one() : Fr::zero());
+  }
+  ww.put(9 + 2 * depth, fe_sqr(chain_id));
+#pragma unroll 1
+  for (int i = 0; i < C_BITS; i++) ww.push(claim_x_bit(in, i) ? Fr::one() : Fr::zero());
+  {  // the comparison with l - 1, most significant bit first: a wire per 1-bit of l - 1 (wave-uniform: a constant)
+    bool t = true;
+#pragma unroll 1
+    for (int i = C_BITS - 1; i >= 0; i--) {
+      if (ed_order_minus_1_bit(i)) {
+        t = t && claim_x_bit(in, i);
+        ww.push(t ? Fr::one() : Fr::zero());
+      }
+    }
+  }
+  Fr px, py;  // P = x BASE, affine
+  {
+    const Fr ca = ed_const(168700), cd = ed_const(168696);
+    uint8_t* mul = z + (size_t)ww.w * 32;  // step i: w1 | w2 | w3 | x3 | y3 at mul + 160 i
+    EdPoint acc = ed_identity();
+    Fr run = Fr::one();
+#pragma unroll 1
+    for (int i = 0; i < C_BITS; i++) {
+      const bool b = claim_x_bit(in, i);
+      const uint8_t* e = tab + (size_t)((i >> 2) * ED_TAB_DIGITS + (1 << (i & 3))) * 64;
+      const Fr tx = fe_load<FrParams>(e), ty = fe_load<FrParams>(e + 32);
+      EdPoint q = ed_identity();
+#pragma unroll
+      for (int k = 0; k < 9; k++) {
+        q.x.l[k] = b ? tx.l[k] : q.x.l[k];
+        q.y.l[k] = b ? ty.l[k] : q.y.l[k];
+      }
+      acc = ed_add(acc, q, ca, cd);
+      run = fe_mul(run, acc.z);
+      uint8_t* slot = mul + (size_t)i * 160;
+      fe_store(slot, run);
+      fe_store(slot + 32, acc.z);
+      fe_store(slot + 96, acc.x);
+      fe_store(slot + 128, acc.y);
+    }
+    Fr inv = fe_inv(run);
+    px = Fr::zero();
+    py = Fr::one();
+#pragma unroll 1
+    for (int i = C_BITS - 1; i >= 0; i--) {
+      uint8_t* slot = mul + (size_t)i * 160;
+      const Fr before = i ? fe_load<FrParams>(slot - 160) : Fr::one();  // Z_1 .. Z_i
+      const Fr zi = fe_mul(inv, before);                                // 1 / Z_(i+1)
+      inv = fe_mul(inv, fe_load<FrParams>(slot + 32));
+      const Fr sx = fe_mul(fe_load<FrParams>(slot + 96), zi), sy = fe_mul(fe_load<FrParams>(slot + 128), zi);
+      fe_store(slot + 96, sx);
+      fe_store(slot + 128, sy);
+      if (i == C_BITS - 1) {
+        px = sx;
+        py = sy;
+      } else {  // S_(i+1) is what step i + 1 starts from
+        const bool b = claim_x_bit(in, i + 1);
+        const Fr sxy = fe_mul(sx, sy);
+        fe_store(slot + 160, b ? sx : Fr::zero());
+        fe_store(slot + 192, b ? sy : Fr::zero());
+        fe_store(slot + 224, b ? sxy : Fr::zero());
+      }
+    }
+    // step 0 starts from (0, 1)
+    fe_store(mul, Fr::zero());
+    fe_store(mul + 32, claim_x_bit(in, 0) ? Fr::one() : Fr::zero());
+    fe_store(mul + 64, Fr::zero());
+    ww.w += 5 * C_BITS;
+  }
+  // gadget 0: c = H(P.x, P.y); 1: asset = H(amount, token); 2: leaf = H(c, asset); 3: nullifier_hash = H(x, 1) -> wire 2; 4 + l: level
+  // l of the path (wire 1 = root for the last level); 4 + depth: out_leaf = H(out_commitment, asset) -> wire 4
+  Fr cur = Fr::zero(), c = Fr::zero(), asset = Fr::zero();
+#pragma unroll 1
+  for (int h = 0; h < 5 + depth; h++) {
+    Fr l_in, r_in;
+    int out_wire = -1;
+    if (h == 0) {
+      l_in = px; r_in = py;
+    } else if (h == 1) {
+      l_in = amount; r_in = token;
+    } else if (h == 2) {
+      l_in = c; r_in = asset;
+    } else if (h == 3) {
+      l_in = x; r_in = Fr::one(); out_wire = 2;
+    } else if (h < 4 + depth) {
+      const int lvl = h - 4;
+      const Fr sib = fe_to_mont(fe_load<FrParams>(in + (size_t)(C_REC + lvl) * 32));
+      const bool right_child = (index >> lvl) & 1;
+      l_in = right_child ? sib : cur;
+      r_in = right_child ? cur : sib;
+      ww.push(l_in);  // the `left` selector wire
+      if (lvl == depth - 1) out_wire = 1;
+    } else {
+      l_in = out_commitment; r_in = asset; out_wire = 4;
+    }
+    const Fr hout = gadget_wires(consts, ww, l_in, r_in);
+    if (out_wire < 0) ww.push(hout); else ww.put((uint32_t)out_wire, hout);
+    if (h == 0) c = hout;
+    if (h == 1) asset = hout;
+    if (h != 3) cur = hout;
+  }
+}
+
+// Boundary check of the claim records, one lane per field as k_check_transfer_records: every field canonical (< r), x < l (field 0),
+// amount < 2^128 (field 1), the index inside the tree (field 5) -- compared on the integer words, not in the field.  bad[g] = lowest
+// offending field of record g (the caller initialises it to 0xffffffff): 0 x, 1 amount, 2 token, 3 chain_id, 4 out_commitment,
+// 5 index, 6 + l sibling l.
+__global__ void __launch_bounds__(64) k_check_claim_records(const uint8_t* __restrict__ inputs, int depth, size_t n, uint32_t* __restrict__ bad) {
+  OG_FILLER_PRIO();
+  const size_t g = blockIdx.y;
+  const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= n || f >= (uint32_t)(C_REC + depth)) return;
+  const uint8_t* rec = inputs + g * (size_t)(C_REC + depth) * 32;
+  const uint8_t* p = rec + (size_t)f * 32;
+  bool ok = fe_lt_modulus(fe_load<FrParams>(p));
+  const uint32_t* w = reinterpret_cast<const uint32_t*>(p);
+  if (f == 0) {
+    const uint32_t xw[8] = {w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7]};
+    ok = ok && ed_below_order(xw);
+  }
+  if (f == 1) ok = ok && rec_amount_ok(w);
+  if (f == 5) ok = ok && rec_index_ok(w, depth);
+  if (!ok) atomicMin(&bad[g], f);
+}
+
+static void claim_launch_check(og_ctx* ctx, const StatementArgs& a, const uint8_t* inputs_d, size_t n, uint32_t* bad_d) {
+  hipLaunchKernelGGL(k_check_claim_records, dim3(grid_for(C_REC + a.depth, 64), (unsigned)n), dim3(64), 0, ctx->stream, inputs_d, a.depth, n, bad_d);
+}
+
+// (claim_witness has asked for the table of BASE before records_witness gets here)
+static void claim_launch_core(og_ctx* ctx, int depth, const RecordShape& s, const uint8_t* inputs_d, size_t n, uint8_t* out_d) {
+  hipLaunchKernelGGL(k_claim_core, dim3(grid_for(n, 64)), dim3(64), 0, ctx->stream, (const uint32_t*)ctx->mimc_consts_d, (const uint8_t*)ctx->ed_tab_d,
+                     inputs_d, depth, (size_t)s.n_wires, (uint32_t)s.first_bit_wire, n, out_d);
+}
+
+// the 64 x 16 table of BASE is built on the context's stream by the first call that needs it (eddsa_keys.hip); then the walk of the
+// record statements, which is lane-local for this one whatever n
+static int claim_witness(const Statement& st, og_ctx* ctx, const StatementArgs& a, const uint8_t* inputs_d, size_t n, uint8_t* out_d) {
+  const uint8_t* tab = nullptr;
+  OG_TRY(eddsa_base_table(ctx, &tab));
+  return records_witness(st, ctx, a, inputs_d, n, out_d);
+}
+
 // ---- the statements: one descriptor each, and the host code they share (statements.h) --------------------------------------------------
 static const char* const WITHDRAW_FIELDS[W_REC] = {"nullifier", "secret", "amount", "recipient", "pad_seed", "index", "token", "chain_id"};
 static const char* const DEPOSIT_FIELDS[D_REC] = {"nullifier", "secret", "depositor"};
@@ -1968,6 +2187,7 @@ static const char* const JOIN_FIELDS[J_REC] = {"nullifier_a", "secret_a", "amoun
                                                "token", "chain_id", "out_commitment"};
 static const char* const TRANSFER_FIELDS[T_REC] = {"nullifier", "secret", "amount", "index", "token", "chain_id", "pay_commitment", "pay_amount",
                                                    "change_commitment"};
+static const char* const CLAIM_FIELDS[C_REC] = {"x", "amount", "token", "chain_id", "out_commitment", "index"};
 #define OG_RECORD_TAIL(what) "is not a valid value (>= r, an index outside the tree, an amount >= 2^128, " what ")"
 #ifndef __HIP_DEVICE_COMPILE__  // (host data: the device pass would emit the tables too, and has none of the functions they name)
 const Statement ST_WITHDRAW = {"withdraw", W_PUB, W_REC, 1, WITHDRAW_FIELDS, "is not a canonical value (>= r, or an index outside the tree)",
@@ -1982,6 +2202,8 @@ const Statement ST_JOIN = {"join", J_PUB, J_REC, 2, JOIN_FIELDS, OG_RECORD_TAIL(
 const Statement ST_TRANSFER = {"transfer", T_PUB, T_REC, 1, TRANSFER_FIELDS, OG_RECORD_TAIL("or pay_amount > amount"), "this transfer-statement shape",
                                transfer_shape, transfer_launch_check, records_witness, TW9_XCH, transfer_launch_core, transfer_launch_w9,
                                transfer_r1cs_rows};
+const Statement ST_CLAIM = {"claim", C_PUB, C_REC, 1, CLAIM_FIELDS, OG_RECORD_TAIL("or x >= l"), "this claim-statement shape", claim_shape,
+                            claim_launch_check, claim_witness, 0, claim_launch_core, nullptr, claim_r1cs_rows};
 #endif
 
 // the argument checks every call of a statement with a path makes (deposit has neither a depth nor a bound on its flat check grid)
@@ -2035,7 +2257,8 @@ int records_ok(const Statement& st, og_ctx* ctx, const StatementArgs& a, const u
 }
 
 // The wave-wide walk for the calls witness_walks_wave_wide names -- its limb buffer is n x n_wires x 36 B from the arena --, the lane-local
-// kernel for batches: there a wave per permutation would be paid out of the prover's accumulations
+// kernel for batches: there a wave per permutation would be paid out of the prover's accumulations.  A statement without a wave-wide
+// form (claim) walks lane-local whatever n
 int records_witness(const Statement& st, og_ctx* ctx, const StatementArgs& a, const uint8_t* inputs_d, size_t n, uint8_t* out_d) {
   OG_TRY(statement_args_ok(st, a));
   OG_REQUIRE(n <= 65535, std::string(st.name) + ": at most 65535 witnesses per call");
@@ -2043,7 +2266,7 @@ int records_witness(const Statement& st, og_ctx* ctx, const StatementArgs& a, co
   const int depth = a.depth;
   const RecordShape s = st.shape(a);
   ProfScope ps(ctx, PROF_WITNESS, (double)n);
-  if (witness_walks_wave_wide(ctx, n)) {
+  if (st.launch_w9 && witness_walks_wave_wide(ctx, n)) {
     uint32_t *wl = nullptr, *xch = nullptr;
     OG_TRY(arena_get(ctx, "wit.w9.limbs", n * (size_t)s.n_wires * 36, (void**)&wl));
     OG_TRY(arena_get(ctx, "wit.w9.xch", n * (size_t)(st.paths * depth + st.w9_xch) * 36, (void**)&xch));
