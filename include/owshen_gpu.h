@@ -209,7 +209,41 @@ int og_note_scan_batch_d(og_ctx* ctx, const uint8_t sk[32], const uint8_t* memos
 int og_note_seal_owned_batch_d(og_ctx* ctx, const uint8_t* requests_d, size_t n, uint8_t* memos_out_d, uint8_t* notes_out_d, uint32_t* ok_out);
 int og_note_scan_owned_batch_d(og_ctx* ctx, const uint8_t sk[32], const uint8_t* memos_d, const uint8_t* leaves_d, size_t n, uint8_t* opened_out_d, uint32_t* hit_out);
 
-/* ---- N4: radix-2 Fr NTT (domain generator 7^((r-1)/n), coset generator 7) ------
+/* ---- view keys: find and open owned notes without the key that spends them -------------------------------------------------------------
+ * og_note_scan_owned_batch_d takes sk, the wallet's only secret: whoever scans can spend.  A scan is a service by nature (a machine
+ * that is not the wallet walks the whole pool), so the view form separates the two powers, as every deployed stealth-address scheme
+ * does.  Notation as above.
+ *   keys    a view scalar v and a spend scalar sk, both canonical Fr elements; PV = v * BASE, PS = sk * BASE; the address is (PV, PS),
+ *           which og_eddsa_pubkey_batch_d makes from [v, sk].
+ *   KDF     from S, on indices disjoint from 1..5 and 6..9: k = H(S.x, S.y); tag = H(k, 10); t = H(k, 11); pad_a = H(k, 12);
+ *           pad_t = H(k, 13).  Each of the three scans answers 0 on the memos of the other two forms.
+ *   seal    request, 7 x 32 B: e | PV.x | PV.y | PS.x | PS.y | amount | token.  E = e * BASE, S = e * PV, P = PS + t * BASE,
+ *           c = H(P.x, P.y), leaf = H(c, H(amount, token)).  memo, 5 x 32 B: E.x | E.y | tag | amount + pad_a | token + pad_t; note,
+ *           2 x 32 B: c | leaf -- both the owned form's shapes, so a ledger stores them alike.  Refused (ok = 0, outputs zeroed): a
+ *           field >= r, amount >= 2^128, PV or PS off the curve, small(PV), small(PS), small(E), small(P).
+ *   scan    with (v, PS): S = v * E on the integer v < r (not reduced mod l), then the KDF.  hit 0: a field >= r, E off the curve,
+ *           small(E), or another tag; hit 2: the tag matches and the amount is >= 2^128, or small(P), or leaves were given and the
+ *           leaf differs from H(c, H(amount, token)); hit 1: the memo opens as t | amount | token | c (4 x 32 B), t the KDF's output,
+ *           canonical and not reduced, c = H(P.x, P.y) for P = PS + t * BASE.  No x appears anywhere: the scanner never holds sk.
+ *   unlock  with sk, in the wallet: row t | amount | token | c -> x | amount | token | c with x = (sk + t) mod l -- byte for byte the
+ *           opened row of og_note_scan_owned_batch_d, the private half of a claim record.  ok = 1 only if the four fields are
+ *           canonical, amount < 2^128, H(x * BASE) = c and, when leaves are given, leaf = H(c, H(amount, token)); otherwise ok = 0
+ *           and the row is zeroed.  The all-zero row a scan writes for a non-hit gives ok = 0 by itself.
+ * What each party knows: the sender t and P, not x.  The view-key holder t, P, amount, token and c; not x and not the nullifier hash
+ * H(x, 1): it finds and reads notes, it cannot spend them and cannot see them spent.  The tag depends on v alone: two addresses with
+ * one view key and different spend keys open each other's memos with a c that is not the sealed one -- hit 2 with a leaf; without a
+ * leaf the scan cannot tell, and unlock with a leaf can.  A PS with a torsion component seals, and the note never unlocks
+ * (x * BASE != P).  A scanning service may withhold notes, or lie about amount and token: unlock with the leaf catches the lie,
+ * nothing catches withholding.  The specification is tests/view_note_spec.py.
+ * Conventions of the owned pair: v, ps (PS.x | PS.y) and sk are HOST pointers; ok_out / hit_out are HOST arrays; leaves_d and
+ * opened_out_d may be NULL; n = 0 is OG_OK and touches nothing; a null handle or required pointer is OG_ERR_INVALID before the device
+ * is touched.  OG_ERR_INVALID, naming the reason, also for v >= r, sk >= r, and a PS with a coordinate >= r, off the curve or small
+ * (decided once per call, on the host).  Neither v, sk, their digits nor sk mod l stay in the context. */
+int og_note_seal_view_batch_d(og_ctx* ctx, const uint8_t* requests_d, size_t n, uint8_t* memos_out_d, uint8_t* notes_out_d, uint32_t* ok_out);
+int og_note_scan_view_batch_d(og_ctx* ctx, const uint8_t v[32], const uint8_t ps[64], const uint8_t* memos_d, const uint8_t* leaves_d, size_t n, uint8_t* opened_out_d, uint32_t* hit_out);
+int og_note_unlock_batch_d(og_ctx* ctx, const uint8_t sk[32], const uint8_t* rows_d, const uint8_t* leaves_d, size_t n, uint8_t* unlocked_out_d, uint32_t* ok_out);
+
+/* ---- N4: radix-2 Fr NTT(domain generator 7^((r-1)/n), coset generator 7) ------
  * batch transforms of size n = 2^log_n, natural order in and out, canonical bytes.
  *   inverse = 0, coset = 0 : out[i] = sum_j in[j] w^(ij)
  *   inverse = 0, coset = 1 : evaluates at 7 w^i

@@ -302,6 +302,51 @@ class Context:
             C.memset(skb, 0, 32)
         return out, hit
 
+    def note_seal_view(self, requests):
+        """the view form (found and opened with the view scalar, spent with the spend scalar): requests device uint8 [n, 7, 32]
+        (e | PV.x | PV.y | PS.x | PS.y | amount | token) -> (memos device [n, 5, 32], notes device [n, 2, 32]: c | leaf with c = H(P.x, P.y),
+        P = PS + t BASE -- the owned form's shapes --, np.uint32 [n] (0 = refused, memo and note zeroed))"""
+        self._pre()
+        n = requests.shape[0]
+        memos, notes = self.empty(n, 5, 32), self.empty(n, 2, 32)
+        ok = np.zeros(n, dtype=np.uint32)
+        self._check(self._lib.og_note_seal_view_batch_d(self._h, self.ptr(requests), n, self.ptr(memos), self.ptr(notes),
+                                                        ok.ctypes.data_as(C.c_void_p)))
+        return memos, notes, ok
+
+    def note_scan_view(self, v, ps, memos, leaves=None, opened=True):
+        """v: the view scalar, int or 32 little-endian bytes (canonical); ps: the public spend key, (x, y) ints or 64 bytes x | y; memos and
+        leaves as note_scan -> (opened device [n, 4, 32]: t | amount | token | c, zero rows unless the hit is 1 -- None with opened=False --,
+        np.uint32 [n]: 0 | 1 | 2 as note_scan).  No row holds x: note_unlock, with sk, makes it."""
+        self._pre()
+        n = memos.shape[0]
+        vb = (C.c_uint8 * 32).from_buffer_copy(v.to_bytes(32, "little") if isinstance(v, int) else bytes(v))
+        psb = (C.c_uint8 * 64).from_buffer_copy(b"".join(int(c).to_bytes(32, "little") for c in ps) if isinstance(ps, (tuple, list)) else bytes(ps))
+        out = self.empty(n, 4, 32) if opened else None
+        hit = np.zeros(n, dtype=np.uint32)
+        try:
+            self._check(self._lib.og_note_scan_view_batch_d(self._h, vb, psb, self.ptr(memos), self.ptr(leaves), n, self.ptr(out),
+                                                            hit.ctypes.data_as(C.c_void_p)))
+        finally:
+            C.memset(vb, 0, 32)
+        return out, hit
+
+    def note_unlock(self, sk, rows, leaves=None):
+        """sk: the spend scalar, int or 32 little-endian bytes (canonical); rows: device uint8 [n, 4, 32] as note_scan_view opens them;
+        leaves: device uint8 [n, 32] or None -> (unlocked device [n, 4, 32]: x | amount | token | c with x = (sk + t) mod l, the opened
+        row of note_scan_owned; zero rows unless ok, np.uint32 [n]: 1 = H(x BASE) is the row's c, and the leaf's when leaves are given)"""
+        self._pre()
+        n = rows.shape[0]
+        skb = (C.c_uint8 * 32).from_buffer_copy(sk.to_bytes(32, "little") if isinstance(sk, int) else bytes(sk))
+        out = self.empty(n, 4, 32)
+        ok = np.zeros(n, dtype=np.uint32)
+        try:
+            self._check(self._lib.og_note_unlock_batch_d(self._h, skb, self.ptr(rows), self.ptr(leaves), n, self.ptr(out),
+                                                         ok.ctypes.data_as(C.c_void_p)))
+        finally:
+            C.memset(skb, 0, 32)
+        return out, ok
+
     # -- N4 NTT --
     def ntt(self, data, inverse=False, coset=False):
         """data: device uint8 [n,32] or [batch,n,32] canonical -> same shape."""

@@ -1044,6 +1044,53 @@ int og_note_scan_owned_batch_d(og_ctx* ctx, const uint8_t sk[32], const uint8_t*
   });
 }
 
+int og_note_seal_view_batch_d(og_ctx* ctx, const uint8_t* requests_d, size_t n, uint8_t* memos_out_d, uint8_t* notes_out_d, uint32_t* ok_out) {
+  return guarded([&]() -> int {
+    CTX_OK(ctx);
+    OG_REQUIRE(n == 0 || (requests_d && memos_out_d && notes_out_d && ok_out), "og_note_seal_view_batch_d: null argument");
+    if (n == 0) return OG_OK;
+    LOCKED(ctx);
+    uint32_t* ok_d = nullptr;
+    OG_TRY(arena_get(ctx, "eddsa.ok", n * 4, (void**)&ok_d));
+    OG_TRY(note_seal_view(ctx, requests_d, n, memos_out_d, notes_out_d, ok_d));
+    return eddsa_ok_out(ctx, ok_d, n, ok_out);
+  });
+}
+
+int og_note_scan_view_batch_d(og_ctx* ctx, const uint8_t v[32], const uint8_t ps[64], const uint8_t* memos_d, const uint8_t* leaves_d, size_t n,
+                              uint8_t* opened_out_d, uint32_t* hit_out) {
+  return guarded([&]() -> int {
+    CTX_OK(ctx);
+    OG_REQUIRE(n == 0 || (v && ps && memos_d && hit_out), "og_note_scan_view_batch_d: null argument");
+    if (n == 0) return OG_OK;
+    OG_REQUIRE(note_sk_canonical(v), "og_note_scan_view_batch_d: v is not a canonical field element (v >= r)");
+    if (const char* why = note_ps_refusal(ps)) {  // once per call, on the host
+      set_error(std::string("og_note_scan_view_batch_d: ") + why);
+      return OG_ERR_INVALID;
+    }
+    LOCKED(ctx);
+    uint32_t* hit_d = nullptr;
+    OG_TRY(arena_get(ctx, "eddsa.ok", n * 4, (void**)&hit_d));
+    OG_TRY(note_scan_view(ctx, v, ps, memos_d, leaves_d, n, opened_out_d, hit_d));
+    return eddsa_ok_out(ctx, hit_d, n, hit_out);
+  });
+}
+
+int og_note_unlock_batch_d(og_ctx* ctx, const uint8_t sk[32], const uint8_t* rows_d, const uint8_t* leaves_d, size_t n, uint8_t* unlocked_out_d,
+                           uint32_t* ok_out) {
+  return guarded([&]() -> int {
+    CTX_OK(ctx);
+    OG_REQUIRE(n == 0 || (sk && rows_d && unlocked_out_d && ok_out), "og_note_unlock_batch_d: null argument");
+    if (n == 0) return OG_OK;
+    OG_REQUIRE(note_sk_canonical(sk), "og_note_unlock_batch_d: sk is not a canonical field element (sk >= r)");
+    LOCKED(ctx);
+    uint32_t* ok_d = nullptr;
+    OG_TRY(arena_get(ctx, "eddsa.ok", n * 4, (void**)&ok_d));
+    OG_TRY(note_unlock(ctx, sk, rows_d, leaves_d, n, unlocked_out_d, ok_d));
+    return eddsa_ok_out(ctx, ok_d, n, ok_out);
+  });
+}
+
 int og_vk_load(og_ctx* ctx, const uint8_t* vk, size_t vk_len, og_vk** out) {
   return guarded([&]() -> int {
     CTX_OK(ctx);

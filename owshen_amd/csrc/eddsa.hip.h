@@ -48,7 +48,7 @@ OG_HD void ed_sub_order(uint32_t a[8]) {
   }
 }
 
-__device__ __forceinline__ Fr ed_const(uint32_t v) { return fe_to_mont(fe_from_u32<FrParams>(v)); }
+OG_HD Fr ed_const(uint32_t v) { return fe_to_mont(fe_from_u32<FrParams>(v)); }
 
 // unified projective addition on a x^2 + y^2 = 1 + d x^2 y^2 (add-2008-bbjlp: the reference's projective add :118-143 without
 // its affine equality test; a is a square and d is not, so the law is complete: it doubles, and the identity is no exception)
@@ -68,7 +68,7 @@ __device__ __forceinline__ EdPoint ed_add(const EdPoint& p, const EdPoint& q, co
   return r;
 }
 
-__device__ __forceinline__ bool ed_on_curve(const Fr& x, const Fr& y, const Fr& ca, const Fr& cd) {
+OG_HD bool ed_on_curve(const Fr& x, const Fr& y, const Fr& ca, const Fr& cd) {
   const Fr xx = fe_sqr(x), yy = fe_sqr(y);
   return fe_add(fe_mul(ca, xx), yy) == fe_add(Fr::one(), fe_mul(cd, fe_mul(xx, yy)));
 }

@@ -16,6 +16,9 @@
 //          so the payer could spend what they paid.  The owned note is bound to P = pk + t BASE with t = H(k, 7); only the payee knows
 //          x = sk + t mod l, and the claim statement (witness.hip) spends on knowledge of x.  Both kernels share the fronts of the
 //          ordinary pair (note_seal_front, note_scan_front) and draw from the same sponge on indices 6 .. 9.
+//   view   the owned scan needs sk, so whoever scans can spend.  The view form (tests/view_note_spec.py) splits the address into
+//          PV = v BASE and PS = sk BASE: S = e PV = v E, P = PS + t BASE, the sponge on indices 10 .. 13.  k_note_scan_view holds v and
+//          the public PS and opens t | amount | token | c; k_note_unlock, in the wallet, makes x = sk + t mod l and checks H(x BASE) = c.
 //   seal   E = e * BASE from the 64 x 16 window table of eddsa_keys.hip, S = e * pk by a plain ladder over the unified law (one
 //          addition site, no divergence), sixteen permutations.
 #include "ctx.h"
@@ -93,7 +96,7 @@ static bool host_canonical_fr(const uint8_t v[32]) {  // the little-endian integ
 // ---- the curve beside eddsa.hip.h ------------------------------------------------------------------------------------------------
 // dedicated doubling (dbl-2008-bbjlp, the reference's projective double :152-164): 4 squarings, 3 products and the product by a.
 // Like the unified law it has no exception on the curve: F = Z^2 (1 + d x^2 y^2) and J = -Z^2 (1 - d x^2 y^2) never vanish.
-__device__ __forceinline__ EdPoint ed_dbl(const EdPoint& p, const Fr& ca) {
+OG_HD EdPoint ed_dbl(const EdPoint& p, const Fr& ca) {
   const Fr B = fe_sqr(fe_add(p.x, p.y));
   const Fr C = fe_sqr(p.x);
   const Fr D = fe_sqr(p.y);
@@ -108,7 +111,7 @@ __device__ __forceinline__ EdPoint ed_dbl(const EdPoint& p, const Fr& ca) {
 }
 
 // 8 P = (0, 1): P lies in the torsion subgroup of order 8 (P on the curve)
-__device__ __forceinline__ bool ed_small(const Fr& x, const Fr& y, const Fr& ca) {
+OG_HD bool ed_small(const Fr& x, const Fr& y, const Fr& ca) {
   EdPoint p;
   p.x = x;
   p.y = y;
@@ -176,6 +179,8 @@ __device__ __forceinline__ Fr kdf_absorb_k(const uint32_t* __restrict__ consts, 
 enum { KDF_TAG = 1, KDF_NULLIFIER = 2, KDF_SECRET = 3, KDF_PAD_AMOUNT = 4, KDF_PAD_TOKEN = 5 };
 // the owned form (tests/owned_note_spec.py) draws from the same sponge on indices of its own: neither scan sees the other form's tag
 enum { KDF_OWNED_TAG = 6, KDF_OWNED_T = 7, KDF_OWNED_PAD_AMOUNT = 8, KDF_OWNED_PAD_TOKEN = 9 };
+// and the view form (tests/view_note_spec.py) on a third set, in the owned form's order: tag, t, pad_a, pad_t
+enum { KDF_VIEW_TAG = 10, KDF_VIEW_T = 11, KDF_VIEW_PAD_AMOUNT = 12, KDF_VIEW_PAD_TOKEN = 13 };
 
 __device__ __forceinline__ bool fe_same_limbs(const Fr& a, const Fr& b) {
   uint32_t x = 0;
@@ -310,16 +315,137 @@ __global__ void __launch_bounds__(64) k_note_scan_owned(const uint32_t* __restri
   hit[g] = code;
 }
 
-// ---- seal ------------------------------------------------------------------------------------------------------------------------
-// What both seals do with a request e | pk.x | pk.y | amount | token before the KDF: the five fields canonical, amount < 2^128, pk on
-// the curve and not small, E = e BASE from the window table (not the identity) and S = e pk by the ladder, both brought to affine
-// by one inversion.  false: the request is refused (the points are then meaningless).
-__device__ __forceinline__ bool note_seal_front(const uint8_t* __restrict__ tab, const uint8_t* req, const Fr& ca, const Fr& cd, Fr& ex, Fr& ey, Fr& sx,
-                                                Fr& sy) {
+// ---- the view form: find and open with the view scalar v, spend with sk ------------------------------------------------------------------
+// The address is (PV, PS) = (v BASE, sk BASE); a note is sealed to S = e PV and bound to P = PS + t BASE.  The scan holds v and the
+// PUBLIC point PS: it finds the memo, opens amount and token and computes P and c, and it never sees x = sk + t, which k_note_unlock
+// computes in the wallet.
+// PS as canonical words: a kernel argument, public, converted only by a lane that has a hit
+struct NotePoint {
+  uint32_t x[8], y[8];
+};
+
+// memo: E.x | E.y | tag | amount + pad_a | token + pad_t, the KDF on the view indices; the front is the owned scan's with another tag
+// index.  hit 0 as k_note_scan; 2: the tag matches and the amount is >= 2^128, P = PS + t BASE is small, or the leaf beside the memo
+// is another; 1: opened -> t | amount | token | c with t = H(k, 11) canonical and unreduced, c = H(P.x, P.y).
+template <int FORM>
+__global__ void __launch_bounds__(64) k_note_scan_view(const uint32_t* __restrict__ consts, const uint8_t* __restrict__ tab, const NoteDigits dg,
+                                                      const NotePoint ps, const uint8_t* __restrict__ memos, const uint8_t* __restrict__ leaves, size_t n,
+                                                      uint8_t* __restrict__ opened, uint32_t* __restrict__ hit) {
+  const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= n) return;
+  const uint8_t* m = memos + g * 160;
+  Fr a;  // the sponge with k absorbed
+  uint32_t code = note_scan_front<FORM>(consts, dg, m, KDF_VIEW_TAG, a) ? 1u : 0u;
+  uint8_t* o = opened ? opened + g * 128 : nullptr;
+  if (code) {  // diverges; a wallet owns a vanishing share of the pool
+    const Fr amount = fe_canon(fe_sub(fe_load<FrParams>(m + 96), fe_from_mont(note_absorb(consts, a, ed_const(KDF_VIEW_PAD_AMOUNT)))));
+    const Fr token = fe_canon(fe_sub(fe_load<FrParams>(m + 128), fe_from_mont(note_absorb(consts, a, ed_const(KDF_VIEW_PAD_TOKEN)))));
+    if (!below_2_128(amount)) code = 2u;
+    if (code == 1u) {
+      const Fr t = fe_from_mont(note_absorb(consts, a, ed_const(KDF_VIEW_T)));
+      const Fr ca = ed_const(168700), cd = ed_const(168696);
+      Fr px, py;  // P = PS + t BASE, affine
+      {
+        uint32_t tw[8];
+        fe_to_words(tw, t);
+        EdPoint tb, q;
+        {
+          EdPoint unused;
+          ed_mul_base<false>(tab, tw, tw, tb, unused, ca, cd);
+        }
+        q.x = fe_to_mont(fe_from_words<FrParams>(ps.x));
+        q.y = fe_to_mont(fe_from_words<FrParams>(ps.y));
+        q.z = Fr::one();
+        const EdPoint p = ed_add(tb, q, ca, cd);
+        const Fr zi = fe_inv(p.z);  // never zero: the host has checked that PS is on the curve
+        px = fe_mul(p.x, zi);
+        py = fe_mul(p.y, zi);
+      }
+      if (ed_small(px, py, ca)) code = 2u;
+      const Fr c = note_hash2(consts, px, py);
+      if (leaves && code == 1u) {
+        const Fr leaf = note_hash2(consts, c, note_hash2(consts, fe_to_mont(amount), fe_to_mont(token)));
+        if (!fe_same_limbs(fe_from_mont(leaf), fe_load<FrParams>(leaves + g * 32))) code = 2u;
+      }
+      if (o && code == 1u) {
+        fe_store(o, t);
+        fe_store(o + 32, amount);
+        fe_store(o + 64, token);
+        fe_store(o + 96, fe_from_mont(c));
+      }
+    }
+  }
+  if (o && code != 1u) store_zeros(o, 8);
+  hit[g] = code;
+}
+
+// row: t | amount | token | c as k_note_scan_view opens it (or as anybody claims to have) -> x | amount | token | c with
+// x = (sk + t) mod l, the opened row of k_note_scan_owned.  ok = 1: the four fields canonical, amount < 2^128, H(x BASE) = c and, when
+// leaves are given, leaf = H(c, H(amount, token)); otherwise the row is zeroed.  Every lane does the same work up to the store.
+__global__ void __launch_bounds__(64) k_note_unlock(const uint32_t* __restrict__ consts, const uint8_t* __restrict__ tab, const NoteScalar sk_mod_l,
+                                                   const uint8_t* __restrict__ rows, const uint8_t* __restrict__ leaves, size_t n, uint8_t* __restrict__ out,
+                                                   uint32_t* __restrict__ ok) {
+  const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= n) return;
+  const uint8_t* row = rows + g * 128;
+  uint8_t* o = out + g * 128;
   bool good = true;
 #pragma unroll 1
-  for (int k = 0; k < 5; k++) good = good && canonical_fr(req + 32 * k);
-  good = good && below_2_128(fe_load<FrParams>(req + 96));
+  for (int k = 0; k < 4; k++) good = good && canonical_fr(row + 32 * k);
+  const Fr amount = fe_load<FrParams>(row + 32), token = fe_load<FrParams>(row + 64), c = fe_load<FrParams>(row + 96);
+  good = good && below_2_128(amount);
+  // x = (sk + t) mod l on the integer words: t < r < 8 l (a t that is not canonical is refused whatever comes out), sk mod l < l
+  uint32_t xw[8];
+  fe_to_words(xw, fe_load<FrParams>(row));
+#pragma unroll 1
+  for (int k = 0; k < 8; k++)
+    if (!ed_below_order(xw)) ed_sub_order(xw);
+  uint32_t carry = 0;
+#pragma unroll
+  for (int k = 0; k < 8; k++) {  // (below 2 l < 2^252 for a canonical t: no carry out)
+    const uint64_t v = (uint64_t)xw[k] + sk_mod_l.w[k] + carry;
+    xw[k] = (uint32_t)v;
+    carry = (uint32_t)(v >> 32);
+  }
+  if (!ed_below_order(xw)) ed_sub_order(xw);
+  const Fr ca = ed_const(168700), cd = ed_const(168696);
+  Fr px, py;
+  note_mul_base_affine(tab, xw, ca, cd, px, py);
+  const Fr cx = fe_from_mont(note_hash2(consts, px, py));  // (computed by every lane, then compared: no lane skips a hash)
+  good = fe_same_limbs(cx, c) && good;
+  if (leaves) {  // (uniform)
+    const Fr leaf = fe_from_mont(note_hash2(consts, fe_to_mont(c), note_hash2(consts, fe_to_mont(amount), fe_to_mont(token))));
+    good = fe_same_limbs(leaf, fe_load<FrParams>(leaves + g * 32)) && good;
+  }
+  if (good) {
+    fe_store(o, fe_from_words<FrParams>(xw));
+    fe_store(o + 32, amount);
+    fe_store(o + 64, token);
+    fe_store(o + 96, c);
+  } else {
+    store_zeros(o, 8);
+  }
+  ok[g] = good ? 1u : 0u;
+}
+
+// ---- seal ------------------------------------------------------------------------------------------------------------------------
+// What the seals do with a request of FIELDS fields before the KDF.  FIELDS = 5, e | pk.x | pk.y | amount | token: the ladder's point
+// and the one-time key's base point are the same pk.  FIELDS = 7, e | PV.x | PV.y | PS.x | PS.y | amount | token (the view form): the
+// ladder runs over PV, and PS, which the caller adds t BASE to, is checked here like PV.  All fields canonical, amount (field
+// FIELDS - 2) < 2^128, the points on the curve and not small, E = e BASE from the window table (not the identity) and S = e pk (e PV)
+// by the ladder, both brought to affine by one inversion.  false: the request is refused (the points are then meaningless).
+template <int FIELDS>
+__device__ __forceinline__ bool note_seal_front(const uint8_t* __restrict__ tab, const uint8_t* req, const Fr& ca, const Fr& cd, Fr& ex, Fr& ey, Fr& sx,
+                                                Fr& sy) {
+  static_assert(FIELDS == 5 || FIELDS == 7, "a seal request has five fields, or seven with a spend key of its own");
+  bool good = true;
+#pragma unroll 1
+  for (int k = 0; k < FIELDS; k++) good = good && canonical_fr(req + 32 * k);
+  good = good && below_2_128(fe_load<FrParams>(req + 32 * (FIELDS - 2)));
+  if (FIELDS == 7) {
+    const Fr qx = fe_to_mont(fe_load<FrParams>(req + 96)), qy = fe_to_mont(fe_load<FrParams>(req + 128));
+    good = good && ed_on_curve(qx, qy, ca, cd) && !ed_small(qx, qy, ca);
+  }
   uint32_t we[8];
   fe_to_words(we, fe_load<FrParams>(req));
   EdPoint ep, sp;
@@ -373,7 +499,7 @@ __global__ void __launch_bounds__(64) k_note_seal(const uint32_t* __restrict__ c
   uint8_t* note = notes + g * 64;
   const Fr ca = ed_const(168700), cd = ed_const(168696);
   Fr ex, ey, sx, sy;
-  const bool good = note_seal_front(tab, req, ca, cd, ex, ey, sx, sy);
+  const bool good = note_seal_front<5>(tab, req, ca, cd, ex, ey, sx, sy);
   const Fr a = kdf_absorb_k(consts, sx, sy);
   const Fr nul = note_absorb(consts, a, ed_const(KDF_NULLIFIER)), sec = note_absorb(consts, a, ed_const(KDF_SECRET));
   const Fr leaf = note_hash2(consts, note_hash2(consts, nul, sec),
@@ -405,7 +531,7 @@ __global__ void __launch_bounds__(64) k_note_seal_owned(const uint32_t* __restri
   uint8_t* note = notes + g * 64;
   const Fr ca = ed_const(168700), cd = ed_const(168696);
   Fr ex, ey, sx, sy;
-  bool good = note_seal_front(tab, req, ca, cd, ex, ey, sx, sy);
+  bool good = note_seal_front<5>(tab, req, ca, cd, ex, ey, sx, sy);
   const Fr a = kdf_absorb_k(consts, sx, sy);
   Fr px, py;  // P = pk + t BASE, affine
   {
@@ -442,6 +568,56 @@ __global__ void __launch_bounds__(64) k_note_seal_owned(const uint32_t* __restri
   ok[g] = good ? 1u : 0u;
 }
 
+// request e | PV.x | PV.y | PS.x | PS.y | amount | token -> memo E.x | E.y | tag | amount + pad_a | token + pad_t (the KDF on the view
+// indices, S = e PV) and note c | leaf with P = PS + t BASE, c = H(P.x, P.y), leaf = H(c, H(amount, token)): k_note_seal_owned with the
+// ladder's point and the one-time key's base point apart.  Refused: what note_seal_front<7> refuses, and small(P).
+__global__ void __launch_bounds__(64) k_note_seal_view(const uint32_t* __restrict__ consts, const uint8_t* __restrict__ tab,
+                                                      const uint8_t* __restrict__ reqs, size_t n, uint8_t* __restrict__ memos, uint8_t* __restrict__ notes,
+                                                      uint32_t* __restrict__ ok) {
+  const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= n) return;
+  const uint8_t* req = reqs + g * 224;
+  uint8_t* memo = memos + g * 160;
+  uint8_t* note = notes + g * 64;
+  const Fr ca = ed_const(168700), cd = ed_const(168696);
+  Fr ex, ey, sx, sy;
+  bool good = note_seal_front<7>(tab, req, ca, cd, ex, ey, sx, sy);
+  const Fr a = kdf_absorb_k(consts, sx, sy);
+  Fr px, py;  // P = PS + t BASE, affine
+  {
+    uint32_t tw[8];
+    fe_to_words(tw, fe_from_mont(note_absorb(consts, a, ed_const(KDF_VIEW_T))));
+    EdPoint tb, ps;
+    {
+      EdPoint unused;
+      ed_mul_base<false>(tab, tw, tw, tb, unused, ca, cd);
+    }
+    ps.x = fe_to_mont(fe_load<FrParams>(req + 96));
+    ps.y = fe_to_mont(fe_load<FrParams>(req + 128));
+    ps.z = Fr::one();
+    const EdPoint p = ed_add(tb, ps, ca, cd);
+    const Fr zi = fe_inv(p.z);  // never zero for a PS of the curve; a PS off it is refused whatever comes out
+    px = fe_mul(p.x, zi);
+    py = fe_mul(p.y, zi);
+    good = good && !ed_small(px, py, ca);
+  }
+  const Fr c = note_hash2(consts, px, py);
+  const Fr leaf = note_hash2(consts, c, note_hash2(consts, fe_to_mont(fe_load<FrParams>(req + 160)), fe_to_mont(fe_load<FrParams>(req + 192))));
+  if (good) {
+    fe_store(memo, fe_from_mont(ex));
+    fe_store(memo + 32, fe_from_mont(ey));
+    fe_store(memo + 64, fe_from_mont(note_absorb(consts, a, ed_const(KDF_VIEW_TAG))));
+    fe_store(memo + 96, fe_canon(fe_add(fe_load<FrParams>(req + 160), fe_from_mont(note_absorb(consts, a, ed_const(KDF_VIEW_PAD_AMOUNT))))));
+    fe_store(memo + 128, fe_canon(fe_add(fe_load<FrParams>(req + 192), fe_from_mont(note_absorb(consts, a, ed_const(KDF_VIEW_PAD_TOKEN))))));
+    fe_store(note, fe_from_mont(c));
+    fe_store(note + 32, fe_from_mont(leaf));
+  } else {
+    store_zeros(memo, 10);
+    store_zeros(note, 4);
+  }
+  ok[g] = good ? 1u : 0u;
+}
+
 // ---- launches --------------------------------------------------------------------------------------------------------------------
 int note_seal_owned(og_ctx* ctx, const uint8_t* requests_d, size_t n, uint8_t* memos_d, uint8_t* notes_d, uint32_t* ok_d) {
   if (n == 0) return OG_OK;
@@ -468,6 +644,67 @@ int note_scan_owned(og_ctx* ctx, const uint8_t sk[32], const uint8_t* memos_d, c
   hipLaunchKernelGGL(k_note_scan_owned<NOTE_NAF_W>, dim3(grid_for(n, 64)), dim3(64), 0, ctx->stream, (const uint32_t*)ctx->mimc_consts_d, tab, dg, sl,
                      memos_d, leaves_d, n, opened_d, hit_d);
   note_wipe(dg);
+  {
+    volatile uint32_t* p = sl.w;
+    for (int i = 0; i < 8; i++) p[i] = 0;
+  }
+  OG_HIP(hipGetLastError());
+  return OG_OK;
+}
+
+int note_seal_view(og_ctx* ctx, const uint8_t* requests_d, size_t n, uint8_t* memos_d, uint8_t* notes_d, uint32_t* ok_d) {
+  if (n == 0) return OG_OK;
+  const uint8_t* tab = nullptr;
+  OG_TRY(eddsa_base_table(ctx, &tab));
+  hipLaunchKernelGGL(k_note_seal_view, dim3(grid_for(n, 64)), dim3(64), 0, ctx->stream, (const uint32_t*)ctx->mimc_consts_d, tab, requests_d, n, memos_d,
+                     notes_d, ok_d);
+  OG_HIP(hipGetLastError());
+  return OG_OK;
+}
+
+static void note_words(uint32_t w[8], const uint8_t v[32]) {
+  for (int i = 0; i < 8; i++) w[i] = (uint32_t)v[4 * i] | (uint32_t)v[4 * i + 1] << 8 | (uint32_t)v[4 * i + 2] << 16 | (uint32_t)v[4 * i + 3] << 24;
+}
+
+// PS is public and the same for every memo of a call: it is judged here, once, on the host, by the functions the kernels use
+const char* note_ps_refusal(const uint8_t ps[64]) {
+  if (!host_canonical_fr(ps) || !host_canonical_fr(ps + 32)) return "a coordinate of ps is not a canonical field element (>= r)";
+  const Fr ca = ed_const(168700), cd = ed_const(168696);
+  const Fr x = fe_to_mont(fe_load<FrParams>(ps)), y = fe_to_mont(fe_load<FrParams>(ps + 32));
+  if (!ed_on_curve(x, y, ca, cd)) return "ps is not on the curve";
+  if (ed_small(x, y, ca)) return "ps is a small point (8 ps = (0, 1))";
+  return nullptr;
+}
+
+// v is recoded like the sk of the other scans and wiped like it; PS goes over as words
+int note_scan_view(og_ctx* ctx, const uint8_t v[32], const uint8_t ps[64], const uint8_t* memos_d, const uint8_t* leaves_d, size_t n, uint8_t* opened_d,
+                   uint32_t* hit_d) {
+  if (n == 0) return OG_OK;
+  const uint8_t* tab = nullptr;
+  OG_TRY(eddsa_base_table(ctx, &tab));
+  NoteDigits dg;
+  NotePoint pt;
+  note_words(pt.x, ps);
+  note_words(pt.y, ps + 32);
+  note_recode(v, NOTE_NAF_W, dg);
+  hipLaunchKernelGGL(k_note_scan_view<NOTE_NAF_W>, dim3(grid_for(n, 64)), dim3(64), 0, ctx->stream, (const uint32_t*)ctx->mimc_consts_d, tab, dg, pt,
+                     memos_d, leaves_d, n, opened_d, hit_d);
+  note_wipe(dg);
+  OG_HIP(hipGetLastError());
+  return OG_OK;
+}
+
+// sk mod l is the launch's only secret: reduced here, handed over as a kernel argument, wiped before returning
+int note_unlock(og_ctx* ctx, const uint8_t sk[32], const uint8_t* rows_d, const uint8_t* leaves_d, size_t n, uint8_t* unlocked_d, uint32_t* ok_d) {
+  if (n == 0) return OG_OK;
+  const uint8_t* tab = nullptr;
+  OG_TRY(eddsa_base_table(ctx, &tab));
+  NoteScalar sl;
+  note_words(sl.w, sk);
+  for (int k = 0; k < 8; k++)  // sk < r < 8 l
+    if (!ed_below_order(sl.w)) ed_sub_order(sl.w);
+  hipLaunchKernelGGL(k_note_unlock, dim3(grid_for(n, 64)), dim3(64), 0, ctx->stream, (const uint32_t*)ctx->mimc_consts_d, tab, sl, rows_d, leaves_d, n,
+                     unlocked_d, ok_d);
   {
     volatile uint32_t* p = sl.w;
     for (int i = 0; i < 8; i++) p[i] = 0;

@@ -49,5 +49,13 @@ int note_scan(og_ctx* ctx, const uint8_t sk[32], const uint8_t* memos_d, const u
 // the owned form (a note bound to a one-time key, spent by the claim statement): the same argument lists
 int note_seal_owned(og_ctx* ctx, const uint8_t* requests_d, size_t n, uint8_t* memos_d, uint8_t* notes_d, uint32_t* ok_d);
 int note_scan_owned(og_ctx* ctx, const uint8_t sk[32], const uint8_t* memos_d, const uint8_t* leaves_d, size_t n, uint8_t* opened_d, uint32_t* hit_d);
+// the view form (find and open with the view scalar v and the public spend key PS, spend with sk): requests n x 224 B -> memos and
+// notes as above; v, ps and sk: HOST, checked by the caller (note_ps_refusal: null, or why PS cannot be an address's spend key);
+// rows_d and unlocked_d n x 128 B
+int note_seal_view(og_ctx* ctx, const uint8_t* requests_d, size_t n, uint8_t* memos_d, uint8_t* notes_d, uint32_t* ok_d);
+const char* note_ps_refusal(const uint8_t ps[64]);
+int note_scan_view(og_ctx* ctx, const uint8_t v[32], const uint8_t ps[64], const uint8_t* memos_d, const uint8_t* leaves_d, size_t n, uint8_t* opened_d,
+                   uint32_t* hit_d);
+int note_unlock(og_ctx* ctx, const uint8_t sk[32], const uint8_t* rows_d, const uint8_t* leaves_d, size_t n, uint8_t* unlocked_d, uint32_t* ok_d);
 
 }  // namespace og
