@@ -668,6 +668,83 @@ int og_claim_witness_d(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n
 int og_claim_prove_batch_d(og_ctx* ctx, const og_pk* pk, int depth, const uint8_t* inputs_d, size_t n, const uint8_t* rs,
                            uint8_t* proofs_out, uint8_t* public_out);
 
+/* ---- send statement: an owned note pays part of itself to somebody else INSIDE the pool and keeps the rest -------------------------
+ * "I know the discrete logarithm x of the one-time key P of an owned note under `root`, worth `amount` of `token`.  It is spent.
+ * `pay_amount` of it goes into the new leaf `pay_leaf`, the rest into the new leaf `change_leaf`."  Nothing leaves the pool.  It is
+ * transfer for an owned note: one proof where claim followed by transfer took two.  After it claim is needed only in front of join.
+ * (No reference counterpart: the snapshot has no circuit.)
+ * public (n_pub = 5, verifier order): root, nullifier_hash, chain_id, pay_leaf, change_leaf -- transfer's list
+ * private: x, amount, token, pay_commitment, pay_amount, change_commitment, change, a depth-`depth` MiMC7 Merkle path.
+ * The front is the claim statement's, gadget for gadget (above: the decomposition of x, x < l, P = x * BASE), without its
+ * one * one = one row:
+ *   x = sum 2^i b_i over 251 boolean wires;  x < l against l - 1 (114 wires, 251 rows);  P = x * BASE (1 255 wires, 1 506 rows);
+ *   c = H(P.x, P.y);  asset = H(amount, token);  leaf = H(c, asset) is under root at `index`;
+ *   nullifier_hash = H(x, 1).  claim, send and redeem publish the SAME nullifier_hash for the same note, so the ledger's one spent
+ *     set stops a note that was claimed from also being sent or redeemed;
+ * the back is the transfer statement's:
+ *   pay_amount + change = amount with pay_amount < 2^128 and change < 2^128 (a 128-bit decomposition each: the sum cannot wrap);
+ *   pay_leaf = H(pay_commitment, H(pay_amount, token));  change_leaf = H(change_commitment, H(change, token)), over the ONE token
+ *   wire;  chain_id is bound by its square.
+ * pay_commitment and change_commitment are unconstrained: each may be an ordinary c' = H(nullifier', secret') or the c of an owned or
+ * view note (og_note_seal_owned_batch_d / og_note_seal_view_batch_d return it), which is what lets the payer seal the pay note to the
+ * payee's address and the change note to its own.  pay_amount = 0 and pay_amount = amount are both allowed.
+ * The ledger's part: og_verify the proof, check that root is known and nullifier_hash unspent (and mark it), append pay_leaf, then
+ * change_leaf (og_mimc7_append_d).
+ * Wire and row order: tests/send_spec.py (the spec), og_send_r1cs / owshen_amd/circuit.py send_r1cs (the R1CS):
+ *   n_wires = 1886 + 3 depth + (8 + depth) 730, n_constraints = 2018 + 2 depth + (8 + depth) 730 (31 182 / 31 282 at depth 32:
+ *   domain 2^15; the 2018: chain_id^2, the sum, 2 x 129 range rows, the recomposition of x, 251 + 1 506).  depth 1..64; n <= 65 535
+ *   per og_send_witness_d call.  shape[0..2] = n_wires, n_constraints, n_pub.
+ * inputs_d: n records of (8 + depth) x 32 B canonical little-endian:
+ *   x | amount | token | chain_id | pay_commitment | pay_amount | change_commitment | index (u64, low bytes) | siblings[depth]
+ * witness_out_d: n x n_wires x 32 B.  og_send_prove_batch_d: records -> proofs (rs: n x 64 B host, proofs_out: n x 256 B host,
+ * public_out (host, may be NULL): n x 5 x 32 B in verifier order).  Same bytes as og_send_witness_d + og_prove_batch_d.  The key must
+ * have this shape's wire count and n_pub (a transfer key has the n_pub and is refused by its wire count).
+ * OG_ERR_INVALID, before anything is proved: a malformed record; og_last_error names the record and its lowest offending field
+ * ("input record 3: field 5 (pay_amount)"; 0 x, 1 amount, 2 token, 3 chain_id, 4 pay_commitment, 5 pay_amount, 6 change_commitment,
+ * 7 index, 8 + l sibling l): any field >= r; field 0 if x >= l; field 1 if amount >= 2^128; field 5 if pay_amount >= 2^128 or
+ * pay_amount > amount (compared as integers); field 7 if the index does not fit the tree.
+ * The witness generator has ONE walk, one lane per request whatever n: the claim statement's walk of x * BASE, then the hashes.
+ * Out of scope: a wave-wide walk, host chains, a submit / job form, a multi-GPU and a window-sharded form, and Rust and Solidity
+ * bindings (ffi/ and contracts/ are frozen). */
+int og_send_shape(int depth, uint64_t shape[3]);
+int og_send_witness_d(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, uint8_t* witness_out_d);
+int og_send_prove_batch_d(og_ctx* ctx, const og_pk* pk, int depth, const uint8_t* inputs_d, size_t n, const uint8_t* rs,
+                          uint8_t* proofs_out, uint8_t* public_out);
+
+/* ---- redeem statement: an owned note pays part of itself OUT of the pool to a recipient and keeps the rest --------------------------
+ * "I know the discrete logarithm x of the one-time key P of an owned note under `root`.  It is spent.  I take `amount_out` of it out
+ * to `recipient`, and the rest goes into the new leaf `change_leaf`."  It is split for an owned note: one proof where claim followed
+ * by split took two.  (No reference counterpart: the snapshot has no circuit.)
+ * public (n_pub = 7, verifier order): root, nullifier_hash, recipient, amount_out, token, chain_id, change_leaf -- split's list
+ * private: x, amount, change_commitment, change, a depth-`depth` MiMC7 Merkle path.  `amount` stays private.
+ * The front is the claim statement's, as in the send statement (no one * one = one row):
+ *   x = sum 2^i b_i over 251 boolean wires;  x < l;  P = x * BASE;  c = H(P.x, P.y);  asset = H(amount, token);  leaf = H(c, asset) is
+ *   under root at `index`;  nullifier_hash = H(x, 1) -- the SAME nullifier_hash claim and send publish for the note: one spent set;
+ * the back is the split statement's:
+ *   amount_out + change = amount with amount_out < 2^128 and change < 2^128 (a 128-bit decomposition each);
+ *   change_leaf = H(change_commitment, H(change, token));  recipient and chain_id are bound by a square each.
+ * change_commitment is unconstrained: an ordinary c' or the c of an owned or view note.  amount_out = 0 and amount_out = amount are both
+ * allowed.  The ledger's part: og_verify the proof, check that root is known and nullifier_hash unspent (and mark it), pay amount_out of
+ * token to recipient, append change_leaf (og_mimc7_append_d).
+ * Wire and row order: tests/redeem_spec.py (the spec), og_redeem_r1cs / owshen_amd/circuit.py redeem_r1cs (the R1CS):
+ *   n_wires = 1887 + 3 depth + (6 + depth) 730, n_constraints = 2019 + 2 depth + (6 + depth) 730 (29 723 / 29 823 at depth 32:
+ *   domain 2^15).  depth 1..64; n <= 65 535 per og_redeem_witness_d call.  shape[0..2] = n_wires, n_constraints, n_pub.
+ * inputs_d: n records of (8 + depth) x 32 B canonical little-endian:
+ *   x | amount | recipient | amount_out | token | chain_id | change_commitment | index (u64, low bytes) | siblings[depth]
+ * witness_out_d: n x n_wires x 32 B.  og_redeem_prove_batch_d: records -> proofs (rs: n x 64 B host, proofs_out: n x 256 B host,
+ * public_out (host, may be NULL): n x 7 x 32 B in verifier order).  Same bytes as og_redeem_witness_d + og_prove_batch_d.  The key must
+ * have this shape's wire count and n_pub (a split key has the n_pub and is refused by its wire count).
+ * OG_ERR_INVALID, before anything is proved: a malformed record; og_last_error names the record and its lowest offending field
+ * ("input record 3: field 3 (amount_out)"; 0 x, 1 amount, 2 recipient, 3 amount_out, 4 token, 5 chain_id, 6 change_commitment,
+ * 7 index, 8 + l sibling l): any field >= r; field 0 if x >= l; field 1 if amount >= 2^128; field 3 if amount_out >= 2^128 or
+ * amount_out > amount (compared as integers); field 7 if the index does not fit the tree.
+ * One walk, one lane per request whatever n, as the send statement.  Out of scope: a wave-wide walk, host chains, a submit / job
+ * form, a multi-GPU and a window-sharded form, and Rust and Solidity bindings (ffi/ and contracts/ are frozen). */
+int og_redeem_shape(int depth, uint64_t shape[3]);
+int og_redeem_witness_d(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, uint8_t* witness_out_d);
+int og_redeem_prove_batch_d(og_ctx* ctx, const og_pk* pk, int depth, const uint8_t* inputs_d, size_t n, const uint8_t* rs,
+                            uint8_t* proofs_out, uint8_t* public_out);
+
 /* The same call in two halves, for a host that keeps requests flowing (a sequencer proving batch after batch): submit
  * enqueues ALL the work of the batch on the ctx's streams and returns; og_job_wait blocks until it is done, fills
  * proofs_out / public_out (which, like rs, must stay valid until then) and frees the job.  At most two calls may be in
@@ -746,6 +823,10 @@ int og_join_r1cs(og_ctx* ctx, int depth, og_r1cs** out);
 int og_transfer_r1cs(og_ctx* ctx, int depth, og_r1cs** out);
 /* the statement of og_claim_witness_d at this depth (wire and row order: tests/claim_spec.py) */
 int og_claim_r1cs(og_ctx* ctx, int depth, og_r1cs** out);
+/* the statement of og_send_witness_d at this depth (wire and row order: tests/send_spec.py) */
+int og_send_r1cs(og_ctx* ctx, int depth, og_r1cs** out);
+/* the statement of og_redeem_witness_d at this depth (wire and row order: tests/redeem_spec.py) */
+int og_redeem_r1cs(og_ctx* ctx, int depth, og_r1cs** out);
 int og_r1cs_from_csr(uint64_t n_wires, uint64_t n_pub, uint64_t n_constraints, const uint32_t* const ptr[3],
                      const uint32_t* const col[3], const uint8_t* const val[3], og_r1cs** out);
 void og_r1cs_free(og_r1cs* r1cs);

@@ -20,8 +20,9 @@ points, Fr NTT 2^17"): n_wires = 2^18, domain 2^17.
 Only index arrays and constants are produced here (numpy); there is no host-side witness
 generator -- the witness comes from og_withdraw_witness_d.
 
-The deposit, the split, the join, the transfer and the claim statement (oracle/py/deposit.py, tests/split_spec.py, tests/join_spec.py,
-tests/transfer_spec.py, tests/claim_spec.py are their specs) follow further down, built with the same gadget builder.
+The deposit, the split, the join, the transfer, the claim, the send and the redeem statement (oracle/py/deposit.py, tests/split_spec.py,
+tests/join_spec.py, tests/transfer_spec.py, tests/claim_spec.py, tests/send_spec.py, tests/redeem_spec.py are their specs) follow further
+down, built with the same gadget builder.
 """
 import ctypes as C
 
@@ -769,6 +770,154 @@ def claim_out_leaf(out_commitment, amount, token, ctx):
     value of public input 4; what og_mimc7_append_d appends).  Returns an int."""
     leaf = ctx.mimc7_hash2(_dev(ctx, out_commitment), ctx.mimc7_hash2(_dev(ctx, amount), _dev(ctx, token)))
     return int.from_bytes(ctx.to_host(leaf).tobytes(), "little")
+
+
+# ---- the send and the redeem statement (tests/send_spec.py, tests/redeem_spec.py are the specs; witness.hip k_send_core and
+# k_redeem_core fill the wires): claim's front -- the bits of x, x < l, P = x BASE, c = H(P), leaf = H(c, H(amount, token)) under root,
+# nullifier_hash = H(x, 1), the SAME hash for all three owned statements -- in front of transfer's and of split's back.  An owned note
+# is spent directly: no claim first.
+def _owned_front(bld, w_x, w_amount, w_token, w_nh, w_xbit, w_sib, w_bit, depth, w_root):
+    """the rows all owned statements share behind their own first rows: the recomposition of x, the comparison, the multiplication,
+    then the gadgets c, asset, leaf, nullifier_hash and the path (claim keeps its own text: a one * one row follows its recomposition)"""
+    bld.enforce([(w_xbit + i, 1 << i) for i in range(C_N_BITS)], [(0, 1)], [(w_x, 1)])
+    bld.less_equal_const(w_xbit, C_N_BITS, ED_L - 1)
+    px, py = bld.fixed_base_mul(w_xbit, C_N_BITS)
+    c = bld.hash2(px, py)
+    asset = bld.hash2([(w_amount, 1)], [(w_token, 1)])
+    leaf = bld.hash2([(c, 1)], [(asset, 1)])
+    bld.hash2([(w_x, 1)], [(0, 1)], out_wire=w_nh)
+    bld.merkle_walk(leaf, w_sib, w_bit, depth, w_root)
+
+
+# send -- public: root, nullifier_hash, chain_id, pay_leaf, change_leaf (transfer's list); private: x, amount, token, pay_commitment,
+# pay_amount, change_commitment, change, the path
+SN_N_PUB, SN_N_REC, SN_N_BITS = 5, 8, 128
+(SNW_ROOT, SNW_NH, SNW_CHAIN, SNW_PAY_LEAF, SNW_CHANGE_LEAF, SNW_X, SNW_AMOUNT, SNW_TOKEN, SNW_PAY_COMMITMENT, SNW_PAY_AMOUNT, SNW_CHANGE_COMMITMENT,
+ SNW_CHANGE) = range(1, 13)
+
+
+def send_shape(depth):
+    """(n_wires, n_constraints): (31182, 31282) at depth 32"""
+    return 1886 + 3 * depth + (8 + depth) * 730, 2018 + 2 * depth + (8 + depth) * 730
+
+
+def send_r1cs(mimc7_constants, depth=32):
+    """the send statement as an R1CS (the same gadget builder as the withdraw circuit); no padding gates"""
+    assert depth >= 1 and len(mimc7_constants) == N_ROUNDS
+    n_wires, n_constraints = send_shape(depth)
+    bld = _Builder([int(c) for c in mimc7_constants])
+    bld.alloc(1 + SN_N_PUB + 7)
+    w_sib = bld.alloc(depth)
+    w_bit = bld.alloc(depth)
+    w_csq = bld.alloc()
+    w_pbit = bld.alloc(SN_N_BITS)
+    w_cbit = bld.alloc(SN_N_BITS)
+    w_xbit = bld.alloc(C_N_BITS)
+    bld.enforce([(SNW_CHAIN, 1)], [(SNW_CHAIN, 1)], [(w_csq, 1)])
+    bld.enforce([(SNW_PAY_AMOUNT, 1), (SNW_CHANGE, 1)], [(0, 1)], [(SNW_AMOUNT, 1)])
+    bld.range_check(SNW_PAY_AMOUNT, w_pbit, SN_N_BITS)
+    bld.range_check(SNW_CHANGE, w_cbit, SN_N_BITS)
+    _owned_front(bld, SNW_X, SNW_AMOUNT, SNW_TOKEN, SNW_NH, w_xbit, w_sib, w_bit, depth, SNW_ROOT)
+    pay_asset = bld.hash2([(SNW_PAY_AMOUNT, 1)], [(SNW_TOKEN, 1)])
+    bld.hash2([(SNW_PAY_COMMITMENT, 1)], [(pay_asset, 1)], out_wire=SNW_PAY_LEAF)
+    change_asset = bld.hash2([(SNW_CHANGE, 1)], [(SNW_TOKEN, 1)])
+    bld.hash2([(SNW_CHANGE_COMMITMENT, 1)], [(change_asset, 1)], out_wire=SNW_CHANGE_LEAF)
+    return _finish(bld, n_wires, SN_N_PUB, n_constraints)
+
+
+def send_r1cs_native(ctx, depth=32):
+    """the same statement built by the library (og_send_r1cs: what a Rust host calls)"""
+    h = C.c_void_p()
+    ctx._check(ctx._lib.og_send_r1cs(ctx._h, depth, C.byref(h)))
+    return _r1cs_from_handle(ctx, h)
+
+
+def pack_send_inputs(x, amount, index, siblings, token=0, chain_id=0, pay_commitment=0, pay_amount=0, change_commitment=0):
+    """one send record: (8 + depth) x 32 B (include/owshen_gpu.h):
+    x | amount | token | chain_id | pay_commitment | pay_amount | change_commitment | index | siblings[depth]"""
+    return _pack([x, amount, token, chain_id, pay_commitment, pay_amount, change_commitment, index] + list(siblings))
+
+
+def send_witness(ctx, depth, inputs_d):
+    """inputs_d: device uint8 [n, 8 + depth, 32] -> device uint8 [n, n_wires, 32] (og_send_witness_d)"""
+    return _records_witness(ctx, "send", SN_N_REC + depth, depth, inputs_d, send_shape(depth), SN_N_PUB)
+
+
+def send_prove(ctx, pk, depth, inputs_d, rs, return_public=False):
+    """inputs_d: device uint8 [n, 8 + depth, 32]; rs: (r, s) pairs or uint8 [n, 64] -> np.uint8 [n, 256] (og_send_prove_batch_d);
+    return_public: also (root, nullifier_hash, chain_id, pay_leaf, change_leaf) of every proof, np.uint8 [n, 5, 32]"""
+    return _records_prove(ctx, pk, "send", SN_N_REC + depth, SN_N_PUB, depth, inputs_d, rs, return_public)
+
+
+def send_leaves(pay_commitment, pay_amount, change_commitment, change, token, ctx):
+    """the ledger's and the payee's side of a send: (pay_leaf, change_leaf), the values of public inputs 4 and 5, what
+    og_mimc7_append_d appends, in this order -- the two leaves of a transfer.  Returns two ints."""
+    return transfer_leaves(pay_commitment, pay_amount, change_commitment, change, token, ctx)
+
+
+# redeem -- public: root, nullifier_hash, recipient, amount_out, token, chain_id, change_leaf (split's list); private: x, amount,
+# change_commitment, change, the path
+RD_N_PUB, RD_N_REC, RD_N_BITS = 7, 8, 128
+(RDW_ROOT, RDW_NH, RDW_RECIPIENT, RDW_AMOUNT_OUT, RDW_TOKEN, RDW_CHAIN, RDW_CHANGE_LEAF, RDW_X, RDW_AMOUNT, RDW_CHANGE_COMMITMENT, RDW_CHANGE) = range(1, 12)
+
+
+def redeem_shape(depth):
+    """(n_wires, n_constraints): (29723, 29823) at depth 32"""
+    return 1887 + 3 * depth + (6 + depth) * 730, 2019 + 2 * depth + (6 + depth) * 730
+
+
+def redeem_r1cs(mimc7_constants, depth=32):
+    """the redeem statement as an R1CS (the same gadget builder as the withdraw circuit); no padding gates"""
+    assert depth >= 1 and len(mimc7_constants) == N_ROUNDS
+    n_wires, n_constraints = redeem_shape(depth)
+    bld = _Builder([int(c) for c in mimc7_constants])
+    bld.alloc(1 + RD_N_PUB + 4)
+    w_sib = bld.alloc(depth)
+    w_bit = bld.alloc(depth)
+    w_rsq = bld.alloc()
+    w_csq = bld.alloc()
+    w_obit = bld.alloc(RD_N_BITS)
+    w_cbit = bld.alloc(RD_N_BITS)
+    w_xbit = bld.alloc(C_N_BITS)
+    bld.enforce([(RDW_RECIPIENT, 1)], [(RDW_RECIPIENT, 1)], [(w_rsq, 1)])
+    bld.enforce([(RDW_CHAIN, 1)], [(RDW_CHAIN, 1)], [(w_csq, 1)])
+    bld.enforce([(RDW_AMOUNT_OUT, 1), (RDW_CHANGE, 1)], [(0, 1)], [(RDW_AMOUNT, 1)])
+    bld.range_check(RDW_AMOUNT_OUT, w_obit, RD_N_BITS)
+    bld.range_check(RDW_CHANGE, w_cbit, RD_N_BITS)
+    _owned_front(bld, RDW_X, RDW_AMOUNT, RDW_TOKEN, RDW_NH, w_xbit, w_sib, w_bit, depth, RDW_ROOT)
+    change_asset = bld.hash2([(RDW_CHANGE, 1)], [(RDW_TOKEN, 1)])
+    bld.hash2([(RDW_CHANGE_COMMITMENT, 1)], [(change_asset, 1)], out_wire=RDW_CHANGE_LEAF)
+    return _finish(bld, n_wires, RD_N_PUB, n_constraints)
+
+
+def redeem_r1cs_native(ctx, depth=32):
+    """the same statement built by the library (og_redeem_r1cs: what a Rust host calls)"""
+    h = C.c_void_p()
+    ctx._check(ctx._lib.og_redeem_r1cs(ctx._h, depth, C.byref(h)))
+    return _r1cs_from_handle(ctx, h)
+
+
+def pack_redeem_inputs(x, amount, recipient, amount_out, index, siblings, token=0, chain_id=0, change_commitment=0):
+    """one redeem record: (8 + depth) x 32 B (include/owshen_gpu.h):
+    x | amount | recipient | amount_out | token | chain_id | change_commitment | index | siblings[depth]"""
+    return _pack([x, amount, recipient, amount_out, token, chain_id, change_commitment, index] + list(siblings))
+
+
+def redeem_witness(ctx, depth, inputs_d):
+    """inputs_d: device uint8 [n, 8 + depth, 32] -> device uint8 [n, n_wires, 32] (og_redeem_witness_d)"""
+    return _records_witness(ctx, "redeem", RD_N_REC + depth, depth, inputs_d, redeem_shape(depth), RD_N_PUB)
+
+
+def redeem_prove(ctx, pk, depth, inputs_d, rs, return_public=False):
+    """inputs_d: device uint8 [n, 8 + depth, 32]; rs: (r, s) pairs or uint8 [n, 64] -> np.uint8 [n, 256] (og_redeem_prove_batch_d);
+    return_public: also (root, nullifier_hash, recipient, amount_out, token, chain_id, change_leaf) of every proof, np.uint8 [n, 7, 32]"""
+    return _records_prove(ctx, pk, "redeem", RD_N_REC + depth, RD_N_PUB, depth, inputs_d, rs, return_public)
+
+
+def redeem_change_leaf(change_commitment, change, token, ctx):
+    """the ledger's side of a redeem: the leaf of the change note, H(change_commitment, H(change, token)) (the value of public input
+    7; what og_mimc7_append_d appends).  Returns an int."""
+    return split_change_leaf(change_commitment, change, token, ctx)
 
 
 class ProveJob:

@@ -808,6 +808,23 @@ int og_claim_prove_batch_d(og_ctx* ctx, const og_pk* pk, int depth, const uint8_
   return record_prove_batch_d(ST_CLAIM, ctx, pk, {depth}, inputs_d, n, rs, proofs_out, public_out);
 }
 
+int og_send_shape(int depth, uint64_t shape[3]) { return record_shape(ST_SEND, {depth}, shape); }
+int og_send_witness_d(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, uint8_t* witness_out_d) {
+  return record_witness_d(ST_SEND, ctx, {depth}, inputs_d, n, witness_out_d);
+}
+int og_send_prove_batch_d(og_ctx* ctx, const og_pk* pk, int depth, const uint8_t* inputs_d, size_t n, const uint8_t* rs, uint8_t* proofs_out,
+                          uint8_t* public_out) {
+  return record_prove_batch_d(ST_SEND, ctx, pk, {depth}, inputs_d, n, rs, proofs_out, public_out);
+}
+int og_redeem_shape(int depth, uint64_t shape[3]) { return record_shape(ST_REDEEM, {depth}, shape); }
+int og_redeem_witness_d(og_ctx* ctx, int depth, const uint8_t* inputs_d, size_t n, uint8_t* witness_out_d) {
+  return record_witness_d(ST_REDEEM, ctx, {depth}, inputs_d, n, witness_out_d);
+}
+int og_redeem_prove_batch_d(og_ctx* ctx, const og_pk* pk, int depth, const uint8_t* inputs_d, size_t n, const uint8_t* rs, uint8_t* proofs_out,
+                            uint8_t* public_out) {
+  return record_prove_batch_d(ST_REDEEM, ctx, pk, {depth}, inputs_d, n, rs, proofs_out, public_out);
+}
+
 int og_transfer_prove_batch_d(og_ctx* ctx, const og_pk* pk, int depth, const uint8_t* inputs_d, size_t n, const uint8_t* rs,
                               uint8_t* proofs_out, uint8_t* public_out) {
   return record_prove_batch_d(ST_TRANSFER, ctx, pk, {depth}, inputs_d, n, rs, proofs_out, public_out);

@@ -8,9 +8,10 @@
 //
 //   og_withdraw_r1cs   constraint rows of the depth-D MiMC7 Merkle withdraw circuit (+ synthetic padding gates, + the two
 //                      optional density rows), CSR, canonical 32-byte coefficients
-//   og_deposit_r1cs / og_split_r1cs / og_join_r1cs / og_transfer_r1cs / og_claim_r1cs   the deposit, the split, the join, the transfer
-//                      and the claim statement, with the same builder (oracle/py/deposit.py, tests/split_spec.py, tests/join_spec.py,
-//                      tests/transfer_spec.py, tests/claim_spec.py)
+//   og_deposit_r1cs / og_split_r1cs / og_join_r1cs / og_transfer_r1cs / og_claim_r1cs / og_send_r1cs / og_redeem_r1cs   the deposit,
+//                      the split, the join, the transfer, the claim, the send and the redeem statement, with the same builder
+//                      (oracle/py/deposit.py, tests/split_spec.py, tests/join_spec.py, tests/transfer_spec.py, tests/claim_spec.py,
+//                      tests/send_spec.py, tests/redeem_spec.py)
 //   og_r1cs_from_csr   any R1CS the caller built
 //   og_setup           Groth16 key generation from (tau, alpha, beta, gamma, delta): Lagrange evaluations, the three
 //                      transposed sparse products, the query scalars and ~3 m + d fixed-base multiplications, all on the
@@ -402,6 +403,66 @@ void claim_r1cs_rows(R1csBuilder& b, int depth) {
   b.hash2(R1csBuilder::one(CW_OUT_COMMITMENT), R1csBuilder::one(asset), (int)CW_OUT_LEAF);  // the SAME asset wire
 }
 
+// the rows send and redeem share behind their own first rows (claim keeps its own text: a one * one row follows its recomposition):
+// x = sum 2^i b_i, x < l, P = x BASE, then the gadgets c, asset, leaf, nullifier_hash = H(x, 1) and the path
+static void owned_front_rows(R1csBuilder& b, uint32_t w_x, uint32_t w_amount, uint32_t w_token, uint32_t w_nh, uint32_t w_xbit, uint32_t w_sib,
+                             uint32_t w_bit, int depth, uint32_t w_root) {
+  constexpr uint32_t C_BITS = EdOrder::BITS;
+  LC sum;
+  for (uint32_t i = 0; i < C_BITS; i++) {
+    HFr p2 = {{0, 0, 0, 0}};
+    p2.v[i >> 6] = 1ull << (i & 63);
+    sum.push_back({w_xbit + i, p2});
+  }
+  b.enforce(sum, R1csBuilder::one(0), R1csBuilder::one(w_x));
+  uint64_t l_minus_1[4];  // (l is odd)
+  for (int k = 0; k < 4; k++) l_minus_1[k] = (uint64_t)EdOrder::L[2 * k] | (uint64_t)EdOrder::L[2 * k + 1] << 32;
+  l_minus_1[0] -= 1;
+  b.less_equal_const(w_xbit, C_BITS, l_minus_1);
+  LC px, py;
+  b.fixed_base_mul(w_xbit, C_BITS, px, py);
+  const uint32_t c = b.hash2(px, py);
+  const uint32_t asset = b.hash2(R1csBuilder::one(w_amount), R1csBuilder::one(w_token));
+  const uint32_t leaf = b.hash2(R1csBuilder::one(c), R1csBuilder::one(asset));
+  b.hash2(R1csBuilder::one(w_x), R1csBuilder::one(0), (int)w_nh);  // H(x, 1), as claim: one spent set for the three owned statements
+  b.merkle_walk(leaf, w_sib, w_bit, depth, w_root);
+}
+
+// the send statement (tests/send_spec.py; witness.hip k_send_core): transfer for an owned note
+void send_r1cs_rows(R1csBuilder& b, int depth) {
+  constexpr uint32_t NW_ROOT = 1, NW_NH = 2, NW_CHAIN = 3, NW_PAY_LEAF = 4, NW_CHANGE_LEAF = 5, NW_X = 6, NW_AMOUNT = 7, NW_TOKEN = 8,
+                     NW_PAY_COMMITMENT = 9, NW_PAY_AMOUNT = 10, NW_CHANGE_COMMITMENT = 11, NW_CHANGE = 12;
+  b.alloc(1 + 5 + 7);
+  const uint32_t w_sib = b.alloc(depth), w_bit = b.alloc(depth), w_csq = b.alloc();
+  const uint32_t w_pbit = b.alloc(128), w_cbit = b.alloc(128), w_xbit = b.alloc(EdOrder::BITS);
+  b.enforce(R1csBuilder::one(NW_CHAIN), R1csBuilder::one(NW_CHAIN), R1csBuilder::one(w_csq));
+  b.enforce(LC{{NW_PAY_AMOUNT, hfr_u64(1)}, {NW_CHANGE, hfr_u64(1)}}, R1csBuilder::one(0), R1csBuilder::one(NW_AMOUNT));  // pay_amount + change = amount
+  b.range128(NW_PAY_AMOUNT, w_pbit);
+  b.range128(NW_CHANGE, w_cbit);
+  owned_front_rows(b, NW_X, NW_AMOUNT, NW_TOKEN, NW_NH, w_xbit, w_sib, w_bit, depth, NW_ROOT);
+  const uint32_t pay_asset = b.hash2(R1csBuilder::one(NW_PAY_AMOUNT), R1csBuilder::one(NW_TOKEN));
+  b.hash2(R1csBuilder::one(NW_PAY_COMMITMENT), R1csBuilder::one(pay_asset), (int)NW_PAY_LEAF);
+  const uint32_t change_asset = b.hash2(R1csBuilder::one(NW_CHANGE), R1csBuilder::one(NW_TOKEN));  // the ONE token wire
+  b.hash2(R1csBuilder::one(NW_CHANGE_COMMITMENT), R1csBuilder::one(change_asset), (int)NW_CHANGE_LEAF);
+}
+
+// the redeem statement (tests/redeem_spec.py; witness.hip k_redeem_core): split for an owned note
+void redeem_r1cs_rows(R1csBuilder& b, int depth) {
+  constexpr uint32_t EW_ROOT = 1, EW_NH = 2, EW_RECIPIENT = 3, EW_AMOUNT_OUT = 4, EW_TOKEN = 5, EW_CHAIN = 6, EW_CHANGE_LEAF = 7, EW_X = 8,
+                     EW_AMOUNT = 9, EW_CHANGE_COMMITMENT = 10, EW_CHANGE = 11;
+  b.alloc(1 + 7 + 4);
+  const uint32_t w_sib = b.alloc(depth), w_bit = b.alloc(depth), w_rsq = b.alloc(), w_csq = b.alloc();
+  const uint32_t w_obit = b.alloc(128), w_cbit = b.alloc(128), w_xbit = b.alloc(EdOrder::BITS);
+  b.enforce(R1csBuilder::one(EW_RECIPIENT), R1csBuilder::one(EW_RECIPIENT), R1csBuilder::one(w_rsq));
+  b.enforce(R1csBuilder::one(EW_CHAIN), R1csBuilder::one(EW_CHAIN), R1csBuilder::one(w_csq));
+  b.enforce(LC{{EW_AMOUNT_OUT, hfr_u64(1)}, {EW_CHANGE, hfr_u64(1)}}, R1csBuilder::one(0), R1csBuilder::one(EW_AMOUNT));  // amount_out + change = amount
+  b.range128(EW_AMOUNT_OUT, w_obit);
+  b.range128(EW_CHANGE, w_cbit);
+  owned_front_rows(b, EW_X, EW_AMOUNT, EW_TOKEN, EW_NH, w_xbit, w_sib, w_bit, depth, EW_ROOT);
+  const uint32_t change_asset = b.hash2(R1csBuilder::one(EW_CHANGE), R1csBuilder::one(EW_TOKEN));
+  b.hash2(R1csBuilder::one(EW_CHANGE_COMMITMENT), R1csBuilder::one(change_asset), (int)EW_CHANGE_LEAF);
+}
+
 static int records_r1cs_build(const Statement& st, const uint8_t* mimc_consts, int depth, og_r1cs* r) {
   const std::string who = "og_" + std::string(st.name) + "_r1cs";
   uint64_t shp[3];
@@ -681,6 +742,8 @@ int og_split_r1cs(og_ctx* ctx, int depth, og_r1cs** out) { return record_r1cs(ST
 int og_join_r1cs(og_ctx* ctx, int depth, og_r1cs** out) { return record_r1cs(ST_JOIN, ctx, depth, out); }
 int og_transfer_r1cs(og_ctx* ctx, int depth, og_r1cs** out) { return record_r1cs(ST_TRANSFER, ctx, depth, out); }
 int og_claim_r1cs(og_ctx* ctx, int depth, og_r1cs** out) { return record_r1cs(ST_CLAIM, ctx, depth, out); }
+int og_send_r1cs(og_ctx* ctx, int depth, og_r1cs** out) { return record_r1cs(ST_SEND, ctx, depth, out); }
+int og_redeem_r1cs(og_ctx* ctx, int depth, og_r1cs** out) { return record_r1cs(ST_REDEEM, ctx, depth, out); }
 
 int og_r1cs_from_csr(uint64_t n_wires, uint64_t n_pub, uint64_t n_constraints, const uint32_t* const ptr[3], const uint32_t* const col[3],
                      const uint8_t* const val[3], og_r1cs** out) {

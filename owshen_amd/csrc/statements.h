@@ -1,13 +1,14 @@
 // The statements between their translation units: what witness.hip (kernels, boundary checks, witness launches), keygen.hip (the R1CS
 // builders), groth16.hip (records -> proofs) and capi.hip (the entry points) call of one another, declared once.
 //
-// withdraw, deposit, split, join, transfer and claim are one descriptor each: a record of n_rec fields and `paths` blocks of `depth` siblings
+// withdraw, deposit, split, join, transfer, claim, send and redeem are one descriptor each: a record of n_rec fields and `paths` blocks of `depth` siblings
 // (deposit: no path, and no depth), a shape that depends on StatementArgs, a boundary check, and one way from checked records to
 // witnesses.  Everything that does not depend on the statement is written once over the descriptor ("adding a statement").
-// split, join, transfer and claim -- the "record statements" -- share their witness entry too (records_witness: a lane-local walk for
-// batches and a wave-wide one for small calls; claim has no wave-wide form, its launch_w9 is NULL and every call walks lane-local)
-// and their R1CS prologue and epilogue; the four members at the end of the descriptor are theirs, and NULL / 0 for withdraw and
-// deposit: only records_witness and keygen.hip's records_r1cs_build read them, and only those four statements are routed there.
+// split, join, transfer, claim, send and redeem -- the "record statements" -- share their witness entry too (records_witness: a
+// lane-local walk for batches and a wave-wide one for small calls; the owned statements claim, send and redeem have no wave-wide form,
+// their launch_w9 is NULL and every call walks lane-local) and their R1CS prologue and epilogue; the four members at the end of the
+// descriptor are theirs, and NULL / 0 for withdraw and deposit: only records_witness and keygen.hip's records_r1cs_build read them, and
+// only those six statements are routed there.
 #pragma once
 #include "ctx.h"
 #include "msm.hip.h"  // arena_get
@@ -28,7 +29,7 @@ struct RecordShape {
 struct R1csBuilder;  // keygen.hip
 
 struct Statement {
-  const char* name;                // "withdraw" | "deposit" | "split" | "join" | "transfer" | "claim": every message is formed from it
+  const char* name;                // "withdraw" | "deposit" | "split" | "join" | "transfer" | "claim" | "send" | "redeem": every message is formed from it
   int n_pub, n_rec, paths;         // public inputs; fields of a record before the siblings; sibling blocks per record (deposit: 0, join: 2)
   const char* const* field_names;  // n_rec names
   const char* invalid_tail;        // how the boundary message ends, after the field's name: what makes a field of this statement invalid
@@ -45,7 +46,7 @@ struct Statement {
   void (*launch_w9)(og_ctx* ctx, int depth, const RecordShape& s, const uint8_t* inputs_d, size_t n, uint32_t* wl, uint32_t* xch);
   void (*r1cs_rows)(R1csBuilder& b, int depth);  // keygen.hip: the statement's wire table and rows
 };
-extern const Statement ST_WITHDRAW, ST_DEPOSIT, ST_SPLIT, ST_JOIN, ST_TRANSFER, ST_CLAIM;  // witness.hip
+extern const Statement ST_WITHDRAW, ST_DEPOSIT, ST_SPLIT, ST_JOIN, ST_TRANSFER, ST_CLAIM, ST_SEND, ST_REDEEM;  // witness.hip
 
 // bytes of one input record: the ONE place the width of a record is computed
 inline size_t record_bytes(const Statement& st, int depth) { return (size_t)(st.n_rec + st.paths * depth) * 32; }
@@ -54,6 +55,8 @@ void split_r1cs_rows(R1csBuilder& b, int depth);  // keygen.hip
 void join_r1cs_rows(R1csBuilder& b, int depth);
 void transfer_r1cs_rows(R1csBuilder& b, int depth);
 void claim_r1cs_rows(R1csBuilder& b, int depth);
+void send_r1cs_rows(R1csBuilder& b, int depth);
+void redeem_r1cs_rows(R1csBuilder& b, int depth);
 
 // does a witness call of n requests walk wave-wide (k_w9_* and its kin)?  OG_WITNESS_W9 = 0 | 1 forces either way, OG_WITNESS_W9_MAX
 // moves the bound (hooks builds only); otherwise calls of at most 512 requests do, a sub-batch of a larger call does not
@@ -65,7 +68,7 @@ int records_check_enqueue(const Statement& st, og_ctx* ctx, const StatementArgs&
 std::string invalid_record_message(const Statement& st, const std::string& who, int depth, size_t g, uint32_t f);
 // OG_ERR_INVALID names the first malformed record and its lowest offending field (`base` = index of record 0 in the caller's batch); blocking
 int records_ok(const Statement& st, og_ctx* ctx, const StatementArgs& a, const uint8_t* inputs_d, size_t n, size_t base);
-// the witness entry of split, join, transfer and claim: the walk witness_walks_wave_wide picks, where the statement has both
+// the witness entry of split, join, transfer, claim, send and redeem: the walk witness_walks_wave_wide picks, where the statement has both
 int records_witness(const Statement& st, og_ctx* ctx, const StatementArgs& a, const uint8_t* inputs_d, size_t n, uint8_t* out_d);
 
 // records -> proofs, slab by slab: check, witnesses, the batched prover                                                               // groth16.hip

@@ -13,6 +13,7 @@
 //                    launches for calls of at most 512 requests
 //   k_claim_core     the claim statement (behind the wave-wide walks): one lane per request, whatever the size of the call -- x BASE walked
 //                    projectively with its coordinates parked in the witness row, one inversion per request
+//   k_send_core / k_redeem_core   the send and the redeem statement (behind claim): claim's walk of the key, then transfer's and split's back
 //   k_sw9_* / k_jw9_*   the wave-wide walk of split and of join (at the end, behind transfer's, whose bodies they share): three launches
 //                    each, for calls of at most 512 requests; k_split_core / k_join_core stay the form for batches
 //
@@ -2004,7 +2005,8 @@ __device__ __forceinline__ bool claim_x_bit(const uint8_t* in, int i) {
 }
 
 // One lane per request, as k_transfer_core: the (5 + depth) MultiMiMC7 gadgets through the one rolled permutation body (gadget_wires);
-// Montgomery values are stored and k_wires_from_mont converts them afterwards, in parallel.
+// Montgomery values are stored and k_wires_from_mont converts them afterwards, in parallel.  The wires of the key -- the bits of x, the
+// comparison, the multiplication -- are owned_key_wires, which k_send_core and k_redeem_core call too (further down).
 // The multiplication's wires are the 251 AFFINE partial sums S_1 .. S_251 of x BASE, bit 0 first.  Two inversions per bit would be ~10^5
 // products a request against ~2.7 10^4 for the 37 hashes; instead the sum is walked projectively through the one addition site of the
 // unified law (the addend taken from the 64 x 16 table of BASE under a select on the bit, as the seal's ladder takes its own: entry
@@ -2014,31 +2016,9 @@ __device__ __forceinline__ bool claim_x_bit(const uint8_t* in, int i) {
 // product of step i - 1, forms 1 / Z_(i+1) and the affine S_(i+1), stores x3 and y3 of its own step and w1, w2, w3 of step i + 1,
 // whose parked values the previous iteration has consumed.  No scratch buffer beyond the witness, no runtime-indexed register array.
 // Z never vanishes: the law is complete on the curve.
-__global__ void __launch_bounds__(64) k_claim_core(const uint32_t* __restrict__ consts, const uint8_t* __restrict__ tab, const uint8_t* __restrict__ inputs,
-                                                  int depth, size_t n_wires, uint32_t first_bit_wire, size_t n, uint8_t* __restrict__ out) {
-  OG_FILLER_PRIO();
-  const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= n) return;
-  const uint8_t* in = inputs + g * (size_t)(C_REC + depth) * 32;
-  uint8_t* z = out + g * n_wires * 32;
-  WireWriterT<false> ww{z, first_bit_wire};
-  const Fr x = fe_to_mont(fe_load<FrParams>(in + C_X));
-  const Fr amount = fe_to_mont(fe_load<FrParams>(in + C_AMOUNT));
-  const Fr token = fe_to_mont(fe_load<FrParams>(in + C_TOKEN));
-  const Fr chain_id = fe_to_mont(fe_load<FrParams>(in + C_CHAIN));
-  const Fr out_commitment = fe_to_mont(fe_load<FrParams>(in + C_OUT_COMMITMENT));
-  const uint64_t index = *reinterpret_cast<const uint64_t*>(in + C_INDEX);
-  ww.put(0, Fr::one());
-  ww.put(3, chain_id);
-  ww.put(5, x);
-  ww.put(6, amount);
-  ww.put(7, token);
-  ww.put(8, out_commitment);
-  for (int l = 0; l < depth; l++) {
-    ww.put(9 + l, fe_to_mont(fe_load<FrParams>(in + (size_t)(C_REC + l) * 32)));
-    ww.put(9 + depth + l, ((index >> l) & 1) ? Fr::one() : Fr::zero());
-  }
-  ww.put(9 + 2 * depth, fe_sqr(chain_id));
+// in: the record, whose field 0 is x in all three owned statements; z: the request's witness row; ww: the writer, whose cursor stands
+// at the first bit wire of x and is left behind the multiplication's last wire; (px, py) <- P = x BASE, affine
+__device__ __forceinline__ void owned_key_wires(const uint8_t* __restrict__ tab, const uint8_t* in, uint8_t* z, WireWriterT<false>& ww, Fr& px, Fr& py) {
 #pragma unroll 1
   for (int i = 0; i < C_BITS; i++) ww.push(claim_x_bit(in, i) ? Fr::one() : Fr::zero());
   {  // the comparison with l - 1, most significant bit first: a wire per 1-bit of l - 1 (wave-uniform: a constant)
@@ -2051,7 +2031,6 @@ __global__ void __launch_bounds__(64) k_claim_core(const uint32_t* __restrict__ 
       }
     }
   }
-  Fr px, py;  // P = x BASE, affine
   {
     const Fr ca = ed_const(168700), cd = ed_const(168696);
     uint8_t* mul = z + (size_t)ww.w * 32;  // step i: w1 | w2 | w3 | x3 | y3 at mul + 160 i
@@ -2105,6 +2084,35 @@ __global__ void __launch_bounds__(64) k_claim_core(const uint32_t* __restrict__ 
     fe_store(mul + 64, Fr::zero());
     ww.w += 5 * C_BITS;
   }
+}
+
+__global__ void __launch_bounds__(64) k_claim_core(const uint32_t* __restrict__ consts, const uint8_t* __restrict__ tab, const uint8_t* __restrict__ inputs,
+                                                  int depth, size_t n_wires, uint32_t first_bit_wire, size_t n, uint8_t* __restrict__ out) {
+  OG_FILLER_PRIO();
+  const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= n) return;
+  const uint8_t* in = inputs + g * (size_t)(C_REC + depth) * 32;
+  uint8_t* z = out + g * n_wires * 32;
+  WireWriterT<false> ww{z, first_bit_wire};
+  const Fr x = fe_to_mont(fe_load<FrParams>(in + C_X));
+  const Fr amount = fe_to_mont(fe_load<FrParams>(in + C_AMOUNT));
+  const Fr token = fe_to_mont(fe_load<FrParams>(in + C_TOKEN));
+  const Fr chain_id = fe_to_mont(fe_load<FrParams>(in + C_CHAIN));
+  const Fr out_commitment = fe_to_mont(fe_load<FrParams>(in + C_OUT_COMMITMENT));
+  const uint64_t index = *reinterpret_cast<const uint64_t*>(in + C_INDEX);
+  ww.put(0, Fr::one());
+  ww.put(3, chain_id);
+  ww.put(5, x);
+  ww.put(6, amount);
+  ww.put(7, token);
+  ww.put(8, out_commitment);
+  for (int l = 0; l < depth; l++) {
+    ww.put(9 + l, fe_to_mont(fe_load<FrParams>(in + (size_t)(C_REC + l) * 32)));
+    ww.put(9 + depth + l, ((index >> l) & 1) ? Fr::one() : Fr::zero());
+  }
+  ww.put(9 + 2 * depth, fe_sqr(chain_id));
+  Fr px, py;  // P = x BASE, affine
+  owned_key_wires(tab, in, z, ww, px, py);
   // gadget 0: c = H(P.x, P.y); 1: asset = H(amount, token); 2: leaf = H(c, asset); 3: nullifier_hash = H(x, 1) -> wire 2; 4 + l: level
   // l of the path (wire 1 = root for the last level); 4 + depth: out_leaf = H(out_commitment, asset) -> wire 4
   Fr cur = Fr::zero(), c = Fr::zero(), asset = Fr::zero();
@@ -2172,11 +2180,261 @@ static void claim_launch_core(og_ctx* ctx, int depth, const RecordShape& s, cons
 }
 
 // the 64 x 16 table of BASE is built on the context's stream by the first call that needs it (eddsa_keys.hip); then the walk of the
-// record statements, which is lane-local for this one whatever n
+// record statements, which is lane-local for the owned statements (claim, send, redeem) whatever n
 static int claim_witness(const Statement& st, og_ctx* ctx, const StatementArgs& a, const uint8_t* inputs_d, size_t n, uint8_t* out_d) {
   const uint8_t* tab = nullptr;
   OG_TRY(eddsa_base_table(ctx, &tab));
   return records_witness(st, ctx, a, inputs_d, n, out_d);
+}
+
+// ---- the send and the redeem statement: an owned note spent directly, as transfer and as split spend an ordinary one ---------------------
+// Specs: tests/send_spec.py, tests/redeem_spec.py.  Both have claim's front -- x = sum 2^i b_i over 251 boolean wires, x < l, P = x BASE,
+// c = H(P.x, P.y), asset = H(amount, token), leaf = H(c, asset) under root, nullifier_hash = H(x, 1): the SAME hash claim publishes, so
+// the ledger's one spent set stops a note that was claimed from also being sent or redeemed -- without claim's one * one row, and then
+//   send:    transfer's back.  public: root, nullifier_hash, chain_id, pay_leaf, change_leaf (n_pub = 5); pay_amount + change = amount
+//            with both below 2^128, pay_leaf = H(pay_commitment, H(pay_amount, token)), change_leaf = H(change_commitment, H(change, token))
+//   redeem:  split's back.  public: root, nullifier_hash, recipient, amount_out, token, chain_id, change_leaf (n_pub = 7); amount_out +
+//            change = amount with both below 2^128, change_leaf = H(change_commitment, H(change, token))
+// The commitments are unconstrained: an ordinary c' or the c of an owned or view note.  No reference counterpart.
+// Input records, (8 + depth) x 32 B canonical LE:
+//   send:    x | amount | token | chain_id | pay_commitment | pay_amount | change_commitment | index (u64 in the low bytes) | siblings[depth]
+//   redeem:  x | amount | recipient | amount_out | token | chain_id | change_commitment | index | siblings[depth]
+// Wires of send:
+//   0 one | 1 root | 2 nullifier_hash | 3 chain_id | 4 pay_leaf | 5 change_leaf
+//   6 x | 7 amount | 8 token | 9 pay_commitment | 10 pay_amount | 11 change_commitment | 12 change
+//   13.. siblings[D] | index bits[D] | chain_id^2 | pay_amount bits[128] (LSB first) | change bits[128] | x bits[251] | the comparison's 114
+//   wires | the multiplication's 5 x 251 wires (as in claim) | the gadgets: c, asset, leaf, nullifier_hash (out = wire 2), level 0..D-1
+//   (the last one's out = wire 1), pay_asset, pay_leaf (out = wire 4), change_asset, change_leaf (out = wire 5)
+// Wires of redeem:
+//   0 one | 1 root | 2 nullifier_hash | 3 recipient | 4 amount_out | 5 token | 6 chain_id | 7 change_leaf
+//   8 x | 9 amount | 10 change_commitment | 11 change
+//   12.. siblings[D] | index bits[D] | recipient^2 | chain_id^2 | amount_out bits[128] | change bits[128] | x bits[251] | the comparison's
+//   114 wires | the multiplication's wires | the gadgets: c, asset, leaf, nullifier_hash (out = wire 2), level 0..D-1 (the last one's
+//   out = wire 1), change_asset, change_leaf (out = wire 7)
+// One walk each, one lane per request: k_send_core, k_redeem_core.  The wires of the key are claim's, from owned_key_wires.  What the
+// back of the walk needs of the record it loads where it needs it, as every walk loads its siblings, so that no more values live
+// across the multiplication than in k_claim_core.  NOT built: a wave-wide walk, host chains.
+constexpr int SN_PUB = 5, RD_PUB = 7;
+constexpr int SN_REC = 8, RD_REC = 8;  // fields of a record before the siblings
+constexpr int OW_RANGE = 128;          // bits of an amount
+// byte offsets of the records' fields (x is field 0 of both, as of claim's: claim_x_bit)
+constexpr int SN_X = 0, SN_AMOUNT = 32, SN_TOKEN = 64, SN_CHAIN = 96, SN_PAY_COMMITMENT = 128, SN_PAY_AMOUNT = 160, SN_CHANGE_COMMITMENT = 192,
+              SN_INDEX = 224;
+constexpr int RD_X = 0, RD_AMOUNT = 32, RD_RECIPIENT = 64, RD_AMOUNT_OUT = 96, RD_TOKEN = 128, RD_CHAIN = 160, RD_CHANGE_COMMITMENT = 192,
+              RD_INDEX = 224;
+static_assert(SN_X == C_X && RD_X == C_X, "claim_x_bit reads field 0");
+
+// both shapes: `fields` wires before the siblings (one, the public and the private inputs), `squares` wires behind the index bits,
+// `rows` rows before the range rows, `back` hashes behind the path, `pub_outs` of all hashes with a public output wire
+static RecordShape owned_spend_shape(int depth, int fields, int squares, int rows, int back, int pub_outs) {
+  RecordShape s{};
+  const uint64_t hashes = 4 + (uint64_t)depth + back;
+  s.first_bit_wire = fields + 2 * (uint64_t)depth + squares;  // the first range bit; the bits of x follow the 256 range bits
+  s.first_gadget_wire = s.first_bit_wire + 2 * OW_RANGE + C_BITS + C_CMP + 5 * C_BITS;
+  s.n_wires = s.first_gadget_wire + depth + hashes * 730 - pub_outs;  // a `left` per level
+  s.n_constraints = rows + 2 * (OW_RANGE + 1) + 1 + C_BITS + 6 * C_BITS + 2 * (uint64_t)depth + hashes * 730;
+  return s;
+}
+static RecordShape send_shape(const StatementArgs& a) { return owned_spend_shape(a.depth, 1 + SN_PUB + 7, 1, 2, 4, 4); }
+static RecordShape redeem_shape(const StatementArgs& a) { return owned_spend_shape(a.depth, 1 + RD_PUB + 4, 2, 3, 2, 3); }
+
+// change = amount - part (pay_amount, amount_out) on the record's integer words, as transfer_change: the records are checked first,
+// part <= amount < 2^128, so the difference does not borrow.  transfer_bit_wire gives the 256 range bits.
+__device__ __forceinline__ TransferChange owned_change(const uint8_t* in, int amount_off, int part_off) {
+  const uint64_t a_lo = *reinterpret_cast<const uint64_t*>(in + amount_off), a_hi = *reinterpret_cast<const uint64_t*>(in + amount_off + 8);
+  TransferChange c;
+  c.p_lo = *reinterpret_cast<const uint64_t*>(in + part_off);
+  c.p_hi = *reinterpret_cast<const uint64_t*>(in + part_off + 8);
+  c.c_lo = a_lo - c.p_lo;
+  c.c_hi = a_hi - c.p_hi - (a_lo < c.p_lo ? 1u : 0u);
+  return c;
+}
+__device__ __forceinline__ Fr rec_field(const uint8_t* in, int off) { return fe_to_mont(fe_load<FrParams>(in + off)); }
+
+__global__ void __launch_bounds__(64) k_send_core(const uint32_t* __restrict__ consts, const uint8_t* __restrict__ tab, const uint8_t* __restrict__ inputs,
+                                                 int depth, size_t n_wires, uint32_t first_bit_wire, size_t n, uint8_t* __restrict__ out) {
+  OG_FILLER_PRIO();
+  const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= n) return;
+  const uint8_t* in = inputs + g * (size_t)(SN_REC + depth) * 32;
+  uint8_t* z = out + g * n_wires * 32;
+  WireWriterT<false> ww{z, first_bit_wire};
+  const uint64_t index = *reinterpret_cast<const uint64_t*>(in + SN_INDEX);
+  {
+    const Fr chain_id = rec_field(in, SN_CHAIN);
+    const TransferChange chg = owned_change(in, SN_AMOUNT, SN_PAY_AMOUNT);
+    ww.put(0, Fr::one());
+    ww.put(3, chain_id);
+    ww.put(6, rec_field(in, SN_X));
+    ww.put(7, rec_field(in, SN_AMOUNT));
+    ww.put(8, rec_field(in, SN_TOKEN));
+    ww.put(9, rec_field(in, SN_PAY_COMMITMENT));
+    ww.put(10, rec_field(in, SN_PAY_AMOUNT));
+    ww.put(11, rec_field(in, SN_CHANGE_COMMITMENT));
+    ww.put(12, chg.value());
+    for (int l = 0; l < depth; l++) {
+      ww.put(13 + l, rec_field(in, (SN_REC + l) * 32));
+      ww.put(13 + depth + l, ((index >> l) & 1) ? Fr::one() : Fr::zero());
+    }
+    ww.put(13 + 2 * depth, fe_sqr(chain_id));
+#pragma unroll 1
+    for (int i = 0; i < 2 * OW_RANGE; i++) ww.push(transfer_bit_wire(chg, i));  // the bits of pay_amount, then of change, LSB first
+  }
+  Fr px, py;  // P = x BASE, affine
+  owned_key_wires(tab, in, z, ww, px, py);
+  // gadget 0: c = H(P.x, P.y); 1: asset = H(amount, token); 2: leaf = H(c, asset); 3: nullifier_hash = H(x, 1) -> wire 2; 4 + l: level
+  // l of the path (wire 1 = root for the last level); 4 + depth: pay_asset = H(pay_amount, token); 5 + depth: pay_leaf =
+  // H(pay_commitment, pay_asset) -> wire 4; 6 + depth: change_asset = H(change, token); 7 + depth: change_leaf = H(change_commitment,
+  // change_asset) -> wire 5
+  const Fr token = rec_field(in, SN_TOKEN);
+  Fr cur = Fr::zero(), c = Fr::zero();
+#pragma unroll 1
+  for (int h = 0; h < 8 + depth; h++) {
+    Fr l_in, r_in;
+    int out_wire = -1;
+    if (h == 0) {
+      l_in = px; r_in = py;
+    } else if (h == 1) {
+      l_in = rec_field(in, SN_AMOUNT); r_in = token;
+    } else if (h == 2) {
+      l_in = c; r_in = cur;
+    } else if (h == 3) {
+      l_in = rec_field(in, SN_X); r_in = Fr::one(); out_wire = 2;
+    } else if (h < 4 + depth) {
+      const int lvl = h - 4;
+      const Fr sib = rec_field(in, (SN_REC + lvl) * 32);
+      const bool right_child = (index >> lvl) & 1;
+      l_in = right_child ? sib : cur;
+      r_in = right_child ? cur : sib;
+      ww.push(l_in);  // the `left` selector wire
+      if (lvl == depth - 1) out_wire = 1;
+    } else if (h == 4 + depth) {
+      l_in = rec_field(in, SN_PAY_AMOUNT); r_in = token;
+    } else if (h == 5 + depth) {
+      l_in = rec_field(in, SN_PAY_COMMITMENT); r_in = cur; out_wire = 4;
+    } else if (h == 6 + depth) {
+      l_in = owned_change(in, SN_AMOUNT, SN_PAY_AMOUNT).value(); r_in = token;
+    } else {
+      l_in = rec_field(in, SN_CHANGE_COMMITMENT); r_in = cur; out_wire = 5;
+    }
+    const Fr hout = gadget_wires(consts, ww, l_in, r_in);
+    if (out_wire < 0) ww.push(hout); else ww.put((uint32_t)out_wire, hout);
+    if (h == 0) c = hout;
+    if (h != 3) cur = hout;
+  }
+}
+
+__global__ void __launch_bounds__(64) k_redeem_core(const uint32_t* __restrict__ consts, const uint8_t* __restrict__ tab, const uint8_t* __restrict__ inputs,
+                                                   int depth, size_t n_wires, uint32_t first_bit_wire, size_t n, uint8_t* __restrict__ out) {
+  OG_FILLER_PRIO();
+  const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= n) return;
+  const uint8_t* in = inputs + g * (size_t)(RD_REC + depth) * 32;
+  uint8_t* z = out + g * n_wires * 32;
+  WireWriterT<false> ww{z, first_bit_wire};
+  const uint64_t index = *reinterpret_cast<const uint64_t*>(in + RD_INDEX);
+  {
+    const Fr recipient = rec_field(in, RD_RECIPIENT), chain_id = rec_field(in, RD_CHAIN);
+    const TransferChange chg = owned_change(in, RD_AMOUNT, RD_AMOUNT_OUT);
+    ww.put(0, Fr::one());
+    ww.put(3, recipient);
+    ww.put(4, rec_field(in, RD_AMOUNT_OUT));
+    ww.put(5, rec_field(in, RD_TOKEN));
+    ww.put(6, chain_id);
+    ww.put(8, rec_field(in, RD_X));
+    ww.put(9, rec_field(in, RD_AMOUNT));
+    ww.put(10, rec_field(in, RD_CHANGE_COMMITMENT));
+    ww.put(11, chg.value());
+    for (int l = 0; l < depth; l++) {
+      ww.put(12 + l, rec_field(in, (RD_REC + l) * 32));
+      ww.put(12 + depth + l, ((index >> l) & 1) ? Fr::one() : Fr::zero());
+    }
+    ww.put(12 + 2 * depth, fe_sqr(recipient));
+    ww.put(13 + 2 * depth, fe_sqr(chain_id));
+#pragma unroll 1
+    for (int i = 0; i < 2 * OW_RANGE; i++) ww.push(transfer_bit_wire(chg, i));  // the bits of amount_out, then of change, LSB first
+  }
+  Fr px, py;  // P = x BASE, affine
+  owned_key_wires(tab, in, z, ww, px, py);
+  // gadget 0: c = H(P.x, P.y); 1: asset = H(amount, token); 2: leaf = H(c, asset); 3: nullifier_hash = H(x, 1) -> wire 2; 4 + l: level
+  // l of the path (wire 1 = root for the last level); 4 + depth: change_asset = H(change, token); 5 + depth: change_leaf =
+  // H(change_commitment, change_asset) -> wire 7
+  const Fr token = rec_field(in, RD_TOKEN);
+  Fr cur = Fr::zero(), c = Fr::zero();
+#pragma unroll 1
+  for (int h = 0; h < 6 + depth; h++) {
+    Fr l_in, r_in;
+    int out_wire = -1;
+    if (h == 0) {
+      l_in = px; r_in = py;
+    } else if (h == 1) {
+      l_in = rec_field(in, RD_AMOUNT); r_in = token;
+    } else if (h == 2) {
+      l_in = c; r_in = cur;
+    } else if (h == 3) {
+      l_in = rec_field(in, RD_X); r_in = Fr::one(); out_wire = 2;
+    } else if (h < 4 + depth) {
+      const int lvl = h - 4;
+      const Fr sib = rec_field(in, (RD_REC + lvl) * 32);
+      const bool right_child = (index >> lvl) & 1;
+      l_in = right_child ? sib : cur;
+      r_in = right_child ? cur : sib;
+      ww.push(l_in);  // the `left` selector wire
+      if (lvl == depth - 1) out_wire = 1;
+    } else if (h == 4 + depth) {
+      l_in = owned_change(in, RD_AMOUNT, RD_AMOUNT_OUT).value(); r_in = token;
+    } else {
+      l_in = rec_field(in, RD_CHANGE_COMMITMENT); r_in = cur; out_wire = 7;
+    }
+    const Fr hout = gadget_wires(consts, ww, l_in, r_in);
+    if (out_wire < 0) ww.push(hout); else ww.put((uint32_t)out_wire, hout);
+    if (h == 0) c = hout;
+    if (h != 3) cur = hout;
+  }
+}
+
+// Boundary check of the send and of the redeem records, one lane per field as k_check_claim_records: every field canonical (< r),
+// x < l (field 0), amount < 2^128 (field 1), the part that is paid below 2^128 and at most amount (field PART: 5 pay_amount in a send
+// record, 3 amount_out in a redeem record), the index inside the tree (field 7) -- compared on the integer words, not in the field.
+// bad[g] = lowest offending field of record g (the caller initialises it to 0xffffffff); 8 + l is sibling l.
+template <int PART>
+__global__ void __launch_bounds__(64) k_check_owned_spend_records(const uint8_t* __restrict__ inputs, int depth, size_t n, uint32_t* __restrict__ bad) {
+  OG_FILLER_PRIO();
+  static_assert(SN_REC == RD_REC && SN_AMOUNT == RD_AMOUNT && SN_INDEX == RD_INDEX, "one kernel text for both records");
+  const size_t g = blockIdx.y;
+  const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= n || f >= (uint32_t)(SN_REC + depth)) return;
+  const uint8_t* rec = inputs + g * (size_t)(SN_REC + depth) * 32;
+  const uint8_t* p = rec + (size_t)f * 32;
+  bool ok = fe_lt_modulus(fe_load<FrParams>(p));
+  const uint32_t* w = reinterpret_cast<const uint32_t*>(p);
+  if (f == 0) {
+    const uint32_t xw[8] = {w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7]};
+    ok = ok && ed_below_order(xw);
+  }
+  if (f == 1 || f == PART) ok = ok && rec_amount_ok(w);
+  if (f == PART) ok = ok && rec_le(w, reinterpret_cast<const uint32_t*>(rec + SN_AMOUNT));  // the part <= amount
+  if (f == SN_INDEX / 32) ok = ok && rec_index_ok(w, depth);
+  if (!ok) atomicMin(&bad[g], f);
+}
+
+static void send_launch_check(og_ctx* ctx, const StatementArgs& a, const uint8_t* inputs_d, size_t n, uint32_t* bad_d) {
+  hipLaunchKernelGGL(k_check_owned_spend_records<SN_PAY_AMOUNT / 32>, dim3(grid_for(SN_REC + a.depth, 64), (unsigned)n), dim3(64), 0, ctx->stream,
+                     inputs_d, a.depth, n, bad_d);
+}
+static void redeem_launch_check(og_ctx* ctx, const StatementArgs& a, const uint8_t* inputs_d, size_t n, uint32_t* bad_d) {
+  hipLaunchKernelGGL(k_check_owned_spend_records<RD_AMOUNT_OUT / 32>, dim3(grid_for(RD_REC + a.depth, 64), (unsigned)n), dim3(64), 0, ctx->stream,
+                     inputs_d, a.depth, n, bad_d);
+}
+
+// (claim_witness, which is their witness entry too, has asked for the table of BASE before records_witness gets here)
+static void send_launch_core(og_ctx* ctx, int depth, const RecordShape& s, const uint8_t* inputs_d, size_t n, uint8_t* out_d) {
+  hipLaunchKernelGGL(k_send_core, dim3(grid_for(n, 64)), dim3(64), 0, ctx->stream, (const uint32_t*)ctx->mimc_consts_d, (const uint8_t*)ctx->ed_tab_d,
+                     inputs_d, depth, (size_t)s.n_wires, (uint32_t)s.first_bit_wire, n, out_d);
+}
+static void redeem_launch_core(og_ctx* ctx, int depth, const RecordShape& s, const uint8_t* inputs_d, size_t n, uint8_t* out_d) {
+  hipLaunchKernelGGL(k_redeem_core, dim3(grid_for(n, 64)), dim3(64), 0, ctx->stream, (const uint32_t*)ctx->mimc_consts_d, (const uint8_t*)ctx->ed_tab_d,
+                     inputs_d, depth, (size_t)s.n_wires, (uint32_t)s.first_bit_wire, n, out_d);
 }
 
 // ---- the statements: one descriptor each, and the host code they share (statements.h) --------------------------------------------------
@@ -2188,6 +2446,8 @@ static const char* const JOIN_FIELDS[J_REC] = {"nullifier_a", "secret_a", "amoun
 static const char* const TRANSFER_FIELDS[T_REC] = {"nullifier", "secret", "amount", "index", "token", "chain_id", "pay_commitment", "pay_amount",
                                                    "change_commitment"};
 static const char* const CLAIM_FIELDS[C_REC] = {"x", "amount", "token", "chain_id", "out_commitment", "index"};
+static const char* const SEND_FIELDS[SN_REC] = {"x", "amount", "token", "chain_id", "pay_commitment", "pay_amount", "change_commitment", "index"};
+static const char* const REDEEM_FIELDS[RD_REC] = {"x", "amount", "recipient", "amount_out", "token", "chain_id", "change_commitment", "index"};
 #define OG_RECORD_TAIL(what) "is not a valid value (>= r, an index outside the tree, an amount >= 2^128, " what ")"
 #ifndef __HIP_DEVICE_COMPILE__  // (host data: the device pass would emit the tables too, and has none of the functions they name)
 const Statement ST_WITHDRAW = {"withdraw", W_PUB, W_REC, 1, WITHDRAW_FIELDS, "is not a canonical value (>= r, or an index outside the tree)",
@@ -2204,6 +2464,10 @@ const Statement ST_TRANSFER = {"transfer", T_PUB, T_REC, 1, TRANSFER_FIELDS, OG_
                                transfer_r1cs_rows};
 const Statement ST_CLAIM = {"claim", C_PUB, C_REC, 1, CLAIM_FIELDS, OG_RECORD_TAIL("or x >= l"), "this claim-statement shape", claim_shape,
                             claim_launch_check, claim_witness, 0, claim_launch_core, nullptr, claim_r1cs_rows};
+const Statement ST_SEND = {"send", SN_PUB, SN_REC, 1, SEND_FIELDS, OG_RECORD_TAIL("x >= l, or pay_amount > amount"), "this send-statement shape",
+                           send_shape, send_launch_check, claim_witness, 0, send_launch_core, nullptr, send_r1cs_rows};
+const Statement ST_REDEEM = {"redeem", RD_PUB, RD_REC, 1, REDEEM_FIELDS, OG_RECORD_TAIL("x >= l, or amount_out > amount"), "this redeem-statement shape",
+                             redeem_shape, redeem_launch_check, claim_witness, 0, redeem_launch_core, nullptr, redeem_r1cs_rows};
 #endif
 
 // the argument checks every call of a statement with a path makes (deposit has neither a depth nor a bound on its flat check grid)
@@ -2258,7 +2522,7 @@ int records_ok(const Statement& st, og_ctx* ctx, const StatementArgs& a, const u
 
 // The wave-wide walk for the calls witness_walks_wave_wide names -- its limb buffer is n x n_wires x 36 B from the arena --, the lane-local
 // kernel for batches: there a wave per permutation would be paid out of the prover's accumulations.  A statement without a wave-wide
-// form (claim) walks lane-local whatever n
+// form (claim, send, redeem) walks lane-local whatever n
 int records_witness(const Statement& st, og_ctx* ctx, const StatementArgs& a, const uint8_t* inputs_d, size_t n, uint8_t* out_d) {
   OG_TRY(statement_args_ok(st, a));
   OG_REQUIRE(n <= 65535, std::string(st.name) + ": at most 65535 witnesses per call");
